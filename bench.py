@@ -1,9 +1,16 @@
 # -*- coding: utf-8 -*-
 """bench.py -- ssq_cwt throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+                    [--full [--no-cpu]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line (value, ms_per_step, roofline from the same timed
+region). `--full` adds what takes runs of its own: `stages_us_per_transform` and
+`dominant_kernel` (three more steps with the plan's HIP-event stage timing on) and, unless
+--no-cpu, `cpu_baseline`.
 
 Workload = BASELINE.json configs[1]: ssq_cwt('gmw'), N=160 000, 300 scales
 (`process_scales('log', N, wavelet, nv=32)[:300]`), float32,
@@ -19,7 +26,7 @@ Prints ONE JSON line on rank 0: transforms/s (whole job), ms per step, plus
                HBM3E peak. Measured with HIP events on the launch stream over the
                timed region, for the whole transform (all of its kernels); `traffic` is
                the PMC figure of the same command (profiles/pmc_traffic.json).
-  dominant_kernel
+  dominant_kernel (--full)
                the column-tile kernel (interpolation + reassignment, ~2/3 of the time; round 4:
                ssq::tile2_kernel -- float64 tile, unordered ds_add_f64; SSQ_TILE_ORDER=ordered in the
                environment selects the ticketed ssq::tile_kernel): its own bytes / its own time
@@ -28,10 +35,13 @@ Prints ONE JSON line on rank 0: transforms/s (whole job), ms per step, plus
   per_gpu      transforms/s, signals and output bytes per step and GPU (--batch 64 is
                BASELINE config 4's per-GPU shape: 49 GB of Tx + Wx per step).
 `--scales log-piecewise` runs the reference's default scales (float64 per-row weights) instead.
-  cpu_baseline the CPU oracle pipeline (scipy.fft on 64 threads + the OpenMP C
+  cpu_baseline (--full) the CPU oracle pipeline (scipy.fft on 64 threads + the OpenMP C
                restatement of the reference's loop nests, oracle/) on a bounded sample of
                the same workload, same box, core count stated (kind "port").
 `--gpus N` without a launcher starts the N ranks itself (torch.distributed.run).
+`--dump-outputs DIR` writes what the last timed step returned (rank 0's signals) as DIR/<name>.npy,
+float32 / float64, about 32 MB in all (`dump_outputs`); the inputs depend on the arguments only, so
+two builds can be compared output for output.
 """
 import argparse
 import json
@@ -46,6 +56,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md)
+DUMP_POINTS = 1 << 21        # sampled points per (B, na, N) output of --dump-outputs: 16 MB each
 
 
 def two_chirps(N, seed, noise=0.1):
@@ -115,6 +126,33 @@ def cpu_baseline(N, na, seconds_budget=25.0):
                       % (runs, N, na, fft_workers, cores)}
 
 
+def dump_outputs(outdir, out, seed=0):
+    """`ssq_cwt`'s return (Tx, Wx, ssq_freqs, scales) of one step as outdir/<name>.npy:
+      Tx_sample, Wx_sample   DUMP_POINTS points of the (B, na, N) complex64 arrays at flat indices
+                             drawn by numpy.random.default_rng(seed) (the same for the same shape),
+                             sorted; (points, 2) float32, real and imaginary part
+      Tx_abs_sum, Wx_abs_sum sum over time of |Tx|, |Wx| per signal and row, (B, na) float64:
+                             every point of the outputs counts in these
+      ssq_freqs, scales      as returned, float64"""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    Tx, Wx, ssq_freqs, scales = out[:4]
+    n = Tx.numel()
+    idx = np.sort(np.random.default_rng(seed).integers(0, n, size=min(DUMP_POINTS, n)))
+    idx = torch.as_tensor(idx, device=Tx.device)
+    arrays = {}
+    for name, a in (('Tx', Tx), ('Wx', Wx)):
+        arrays[name + '_sample'] = torch.view_as_real(a.reshape(-1)[idx]).cpu().numpy().astype(np.float32)
+        rows = a.reshape(-1, a.shape[-1])
+        arrays[name + '_abs_sum'] = np.concatenate([
+            rows[r:r + 512].abs().sum(dim=-1, dtype=torch.float64).cpu().numpy()
+            for r in range(0, rows.shape[0], 512)]).reshape(a.shape[:-1])
+    arrays['ssq_freqs'] = np.asarray(ssq_freqs, dtype=np.float64)
+    arrays['scales'] = np.asarray(scales, dtype=np.float64).reshape(-1)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -127,7 +165,12 @@ def main():
                     help="'log' = BASELINE config 2 (the first --na of nv=32 log scales); "
                          "'log-piecewise' = the reference's default scales (ssq_cwt(x) without "
                          "arguments; float64 per-row reassignment weights; --na is ignored)")
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what takes runs of its own: per-stage times, the dominant '
+                         'kernel, the CPU baseline')
+    ap.add_argument('--no-cpu', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument('--gather-tx', action='store_true',
                     help='N > 1: also time one step followed by an all_gather of the full Tx '
                          '(reported separately; `value` never includes it)')
@@ -222,6 +265,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall, gpu_ms = t.tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # optional: what a caller pays to collect every rank's Tx on every rank (SURVEY 8e:
     # config 4's Tx is 24.6 GB per GPU, so the gather -- per-link xGMI bound -- not the
@@ -247,12 +292,12 @@ def main():
         dist.all_reduce(tg, op=dist.ReduceOp.MAX)
         gather_ms = tg.item() * 1e3
 
-    # per-stage times of the same workload, HIP events inside the plan on the launch
+    from ssqueezepy_amd._cwt import _PLAN_CACHE
+    plan = next(iter(_PLAN_CACHE.values()))
+    # --full: per-stage times of the same workload, HIP events inside the plan on the launch
     # stream (outside the timed region: the plan synchronises while it measures)
     stages = None
-    if rank == 0:
-        from ssqueezepy_amd._cwt import _PLAN_CACHE
-        plan = next(iter(_PLAN_CACHE.values()))
+    if rank == 0 and args.full:
         plan.timing(1)
         for _ in range(3):
             out = step()
@@ -335,7 +380,7 @@ def main():
                 "bytes_moved": acc_bytes,
                 "GBps": acc_bytes / (stages["reassignment_us"] * 1e-6) / 1e9,
                 "frac_of_hbm_peak": acc_bytes / (stages["reassignment_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS}
-        if world == 1 and not args.no_cpu and args.scales == 'log':
+        if args.full and world == 1 and not args.no_cpu and args.scales == 'log':
             try:
                 line["cpu_baseline"] = cpu_baseline(N, na)
             except Exception as e:              # never lose the GPU number

@@ -44,10 +44,37 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests',
 os.makedirs(OUT, exist_ok=True)
 
 
+PART_BYTES = 1000000      # no committed file passes 1 MiB: a larger fixture goes into parts
+
+
 def save(name, **arrays):
-    path = os.path.join(OUT, name + '.npz')
-    np.savez_compressed(path, **arrays)
-    print("wrote %-28s %7.1f KB" % (name + '.npz', os.path.getsize(path) / 1e3))
+    """name.npz, continued in name-1.npz, name-2.npz, ... (members in order, each part under
+    PART_BYTES; tests/conftest.py:golden reads them as one)."""
+    import io
+
+    def size(d):
+        b = io.BytesIO()
+        np.savez_compressed(b, **d)
+        return b.tell()
+    parts, cur = [], {}
+    for k, a in arrays.items():
+        if cur and size(dict(cur, **{k: a})) > PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = a
+    parts.append(cur)
+    for part in parts:           # (a single member can still be too large: it cannot be split)
+        if size(part) > 1 << 20:
+            raise ValueError("%s: member(s) %s compress to %d bytes, over 1 MiB; shrink the fixture"
+                             % (name, list(part), size(part)))
+    k = 1
+    while os.path.isfile(os.path.join(OUT, '%s-%d.npz' % (name, k))):     # parts of an earlier run
+        os.remove(os.path.join(OUT, '%s-%d.npz' % (name, k)))
+        k += 1
+    for i, part in enumerate(parts):
+        fname = name + ('.npz' if i == 0 else '-%d.npz' % i)
+        np.savez_compressed(os.path.join(OUT, fname), **part)
+        print("wrote %-28s %7.1f KB" % (fname, os.path.getsize(os.path.join(OUT, fname)) / 1e3))
 
 
 def two_chirps(N, seed=0, noise=0.1, f0=None, f1=None):

@@ -34,8 +34,32 @@ def compute_module():
     yield ssqueezepy_amd
 
 
+class Golden:
+    """The arrays of one fixture: name.npz and, where it would pass 1 MiB as one file, its
+    continuation parts name-1.npz, name-2.npz, ... (oracle/gen_golden.py:save), read lazily."""
+
+    def __init__(self, parts):
+        self._where = {k: z for z in parts for k in z.files}
+
+    @property
+    def files(self):
+        return list(self._where)
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __iter__(self):
+        return iter(self._where)
+
+
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + '.npz'))
+    parts = [np.load(os.path.join(GOLDEN, name + '.npz'))]
+    while os.path.isfile(os.path.join(GOLDEN, '%s-%d.npz' % (name, len(parts)))):
+        parts.append(np.load(os.path.join(GOLDEN, '%s-%d.npz' % (name, len(parts)))))
+    return Golden(parts)
 
 
 def two_chirps(N, seed=0, noise=0.1):

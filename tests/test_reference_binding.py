@@ -7,8 +7,10 @@ two-step) compare its serial CPU functions with its parallel ones at its own thr
 (1e-8 float32 / 1e-16 float64). Here the parallel entries of the reference's function table are
 bound to libssq_hip's C ABI by tests/refbinding/ssq_hip_binding.py -- the binding
 INTEGRATION.md describes -- and the reference's tests are run unmodified, in a process of their
-own, against the CPU emulation of the kernels (tests/emu). Skipped where /root/reference does
-not exist (the GPU box)."""
+own, against the CPU emulation of the kernels (tests/emu).
+
+A known external dependency: both tests run the reference's own code from a checkout of it (the
+directory SSQ_REFERENCE names), which cannot be committed here, and skip where it is absent."""
 import json
 import os
 import subprocess

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 run() {  # label, env assignments...
     local label=$1; shift
     local v
-    v=$(env "$@" python bench.py --steps 10 --warmup 3 --no-cpu 2>/dev/null | tail -1 |
+    v=$(env "$@" python bench.py --full --steps 10 --warmup 3 --no-cpu 2>/dev/null | tail -1 |
         python -c 'import sys, json; d = json.loads(sys.stdin.read()); print("%.1f  stages=%s" % (d["value"], {k: round(v, 1) for k, v in d.get("stages_us_per_transform", {}).items()}))')
     printf '%-28s %s\n' "$label" "$v"
 }

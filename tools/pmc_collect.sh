@@ -2,7 +2,10 @@
 # Collect rocprofv3 PMC counters for the bench, one counter group per pass
 # (gfx950: FETCH_SIZE and WRITE_SIZE cannot share a pass; never combined with tracing
 # beyond --kernel-trace). Usage: tools/pmc_collect.sh <outdir> [bench args...]
+# Each pass runs `bench.py --full --no-cpu`: warm-up + timed + 3 stage-timing steps of --batch signals
+# (--steps 3, defaults otherwise: (3+3+3) x 16 transforms -- the count tools/pmc_traffic.py divides by).
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(realpath -m "$1"); shift
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
@@ -12,6 +15,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   rocprofv3 --kernel-trace --pmc $grp -d "$OUT/pass$i" -o pmc --output-format csv -- \
-      python "$GRAFT_REPO_ROOT/bench.py" --no-cpu "$@" > "$OUT/pass$i.log" 2>&1
-  echo "pass $i ($grp): rc=$?"
+      python "$ROOT/bench.py" --full --no-cpu "$@" > "$OUT/pass$i.log" 2>&1
+  rc=$?; echo "pass $i ($grp): rc=$rc"
+  [ $rc -eq 0 ] || exit $rc           # (a failed pass ends the collection)
 done

@@ -1,6 +1,8 @@
 #!/bin/bash
-# SQ counter passes only (two passes), for kernel tuning. Usage: tools/pmc_sq.sh <outdir> [bench args]
+# SQ counter passes only (three passes), for kernel tuning. Usage: tools/pmc_sq.sh <outdir> [bench args]
+# Each pass runs `bench.py --full --no-cpu` (as tools/pmc_collect.sh): warm-up + timed + 3 stage-timing steps.
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$(realpath -m "$1"); shift
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
@@ -10,6 +12,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_INSTS_SMEM SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_INSTS_BRANCH SQ_INSTS_SENDMSG"; do
   i=$((i+1))
   rocprofv3 --kernel-trace --pmc $grp -d "$OUT/pass$i" -o pmc --output-format csv -- \
-      python "$GRAFT_REPO_ROOT/bench.py" --no-cpu "$@" > "$OUT/pass$i.log" 2>&1
-  echo "pass $i ($grp): rc=$?"
+      python "$ROOT/bench.py" --full --no-cpu "$@" > "$OUT/pass$i.log" 2>&1
+  rc=$?; echo "pass $i ($grp): rc=$rc"
+  [ $rc -eq 0 ] || exit $rc           # (a failed pass ends the collection)
 done

@@ -5,7 +5,7 @@ python tools/r4/atomic_vs_ordered.py 160000 300 4 > $O/atomic_vs_ordered.json 2>
 SSQ_TILE_ORDER=ordered timeout 600 python -m pytest tests/test_gpu_00_configs.py tests/test_gpu_edge_cases.py -x -q -m gpu -k "config2 or every_instantiation or few_scales or default_arguments" 2>&1 | tail -3 | cut -c1-200
 run() { # label env...
   local label=$1; shift
-  echo -n "$label "; env "$@" timeout 120 python bench.py --no-cpu --steps 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
+  echo -n "$label "; env "$@" timeout 120 python bench.py --full --no-cpu --steps 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
 }
 L=/root/repo/ssqueezepy_amd
 for rep in 1 2; do

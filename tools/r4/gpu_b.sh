@@ -4,7 +4,7 @@ cd /root/repo; O=gpurun_out/r4b; mkdir -p $O
 timeout 120 tools/probes/lds_atomic_probe > $O/lds_atomic_probe.txt 2>&1; cat $O/lds_atomic_probe.txt
 run() { # label env...
   local label=$1; shift
-  echo -n "$label "; env "$@" timeout 120 python bench.py --no-cpu --steps 6 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
+  echo -n "$label "; env "$@" timeout 120 python bench.py --full --no-cpu --steps 6 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
 }
 L=/root/repo/ssqueezepy_amd
 export SSQ_TILE_ORDER=ordered

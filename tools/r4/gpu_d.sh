@@ -3,7 +3,7 @@
 cd /root/repo; O=gpurun_out/r4d; mkdir -p $O
 run() { # label env...
   local label=$1; shift
-  echo -n "$label "; env "$@" timeout 120 python bench.py --no-cpu --steps 6 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
+  echo -n "$label "; env "$@" timeout 120 python bench.py --full --no-cpu --steps 6 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
 }
 L=/root/repo/ssqueezepy_amd
 for g in 256 224 192 160 128 96 64; do run grid$g SSQ_DEBUG_TILE_GRID=$g; done 2>&1 | tee $O/grid.txt

@@ -6,7 +6,7 @@ timeout 200 python tools/r4/atomic_vs_ordered.py 20011 40 3 2>&1 | tail -1
 timeout 200 python tools/r4/atomic_vs_ordered.py 100003 456 2 2>&1 | tail -1
 run() { # label env...
   local label=$1; shift
-  echo -n "$label "; env "$@" timeout 120 python bench.py --no-cpu --steps 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
+  echo -n "$label "; env "$@" timeout 120 python bench.py --full --no-cpu --steps 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"
 }
 for rep in 1 2; do
 run ordered SSQ_TILE_ORDER=ordered

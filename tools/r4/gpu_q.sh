@@ -2,7 +2,7 @@
 cd /root/repo; O=gpurun_out/r4q; mkdir -p $O
 timeout 200 python tools/r4/atomic_vs_ordered.py 160000 300 4 2>/dev/null | tail -1 | cut -c1-200
 run() { local label=$1; shift
-  echo -n "$label "; env "$@" timeout 120 python bench.py --no-cpu --steps 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
+  echo -n "$label "; env "$@" timeout 120 python bench.py --full --no-cpu --steps 8 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
 for rep in 1 2; do
 run f64 A=1
 run ordered SSQ_TILE_ORDER=ordered

@@ -5,7 +5,7 @@
 # without the ds_add_f64 / tap arithmetic only
 cd /root/repo; O=gpurun_out/r4u; mkdir -p $O
 run() { local label=$1; shift
-  echo -n "$label "; timeout 200 python bench.py --no-cpu --steps 8 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
+  echo -n "$label "; timeout 200 python bench.py --full --no-cpu --steps 8 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
 for v in base a b c d e f g h i base; do
   export SSQ_HIP_LIB=/root/repo/ssqueezepy_amd/libssq_hip_$v.so
   run "lib=$v"

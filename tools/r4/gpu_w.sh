@@ -3,7 +3,7 @@
 # tiles -- 16 wavefronts, and 8 wavefronts x two workgroups per CU (one's tile end overlaps the other's arithmetic)
 cd /root/repo; O=gpurun_out/r4w; mkdir -p $O
 run() { local label=$1; shift
-  echo -n "$label "; timeout 200 python bench.py --no-cpu --steps 8 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
+  echo -n "$label "; timeout 200 python bench.py --full --no-cpu --steps 8 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
 for rep in 1 2; do
 run "cols32/nw16"
 SSQ_DEBUG_TILE2_COLS=16 run "cols16/nw16"

@@ -3,7 +3,7 @@
 # (the multi-class kernel's occupancy), and the multi-class launch walked from its heaviest items
 cd /root/repo; O=gpurun_out/${OUT:-r5w}; mkdir -p $O
 run() { local label=$1; shift
-  echo -n "$label "; timeout 200 python bench.py --no-cpu --steps ${STEPS:-8} "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
+  echo -n "$label "; timeout 200 python bench.py --full --no-cpu --steps ${STEPS:-8} "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
 for i in 1 2; do
   run "multi"
   SSQ_DEBUG_CWT_BLOCKS_MULTI=0 run "per-class"

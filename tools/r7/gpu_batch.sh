@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6 (second session): why 64 signals per step run 3.7 % faster than 16 -- signals per step x signals per launch group, one box
 cd /root/repo; O=gpurun_out/r7a; mkdir -p $O
-run() { label=$1; shift; echo -n "$label "; timeout 200 python bench.py --no-cpu "$@" 2>$O/err_$label.txt | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['ms_per_step'],3), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
+run() { label=$1; shift; echo -n "$label "; timeout 200 python bench.py --full --no-cpu "$@" 2>$O/err_$label.txt | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(round(d['value']), round(d['ms_per_step'],3), {k: round(v,1) for k,v in d['stages_us_per_transform'].items()})"; }
 for rep in 1 2; do
 run b16 --batch 16 --steps 20
 run b32 --batch 32 --steps 10
