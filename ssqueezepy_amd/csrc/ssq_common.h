@@ -57,7 +57,7 @@ typedef float ssq_f2 __attribute__((ext_vector_type(2)));
 // complex product d = a b of two (re, im) register pairs in two packed instructions:
 //   t = (a.x b.x, a.x b.y);  d = (-a.y b.y + t.x, a.y b.x + t.y)
 // (hipcc spells a complex product out as two multiplies and two multiply-adds, or as packed
-// operations fed by v_mov shuffles; -DSSQ_NO_CMUL_PK restores that form for A/B builds).
+// operations fed by v_mov shuffles).
 // The s_nop is the wait state gfx950 requires between a transcendental instruction (v_sin_f32,
 // v_cos_f32: twiddles) and a vector instruction that reads its result: the compiler inserts it for
 // its own instructions and cannot see into this block -- without it the product read stale

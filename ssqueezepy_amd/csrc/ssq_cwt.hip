@@ -234,8 +234,7 @@ int ssq_cwt_plan_create(ssq_cwt_plan** out, const ssq_cwt_desc* desc) {
     {
         // default: up to 16 signals per launch (measured at config 2: 16 -> +1 % over 8), bin maps
         // bounded to ~2 GiB
-        int64_t g = std::min<int64_t>(16, std::max<int64_t>(1, ((int64_t)1 << 30) / (d.na * d.n)));
-        if (const char* e = getenv("SSQ_DEBUG_CWT_GROUP")) g = atoi(e);
+        const int64_t g = std::min<int64_t>(16, std::max<int64_t>(1, ((int64_t)1 << 30) / (d.na * d.n)));
         pl->group = (int)std::max<int64_t>(1, std::min<int64_t>(g, pl->d.max_batch));
     }
     TRY(dev_alloc((void**)&pl->kidx, ((size_t)pl->group * d.na * d.n + 64) * 2, pl->bytes));
@@ -440,9 +439,8 @@ static int cwt_execute_t(ssq_cwt_plan* pl, const void* x, int64_t batch, void* W
     const bool use_tiles = use_blocks && pl->tile && pl->tile->usable() && Tx && !w && sizeof(T) == 4;
     // The first launch group's decimated samples need the spectra xh and nothing else: their kernels go to the side stream
     // HERE, beside the analytic signal and the block spectra, not only beside the block rows (a short signal's ssq_cwt:
-    // their three launches are the longer branch). SSQ_DEBUG_EARLY_FORK=0: forked behind the block spectra, as before.
-    static const bool early_ok = !(getenv("SSQ_DEBUG_EARLY_FORK") && atoi(getenv("SSQ_DEBUG_EARLY_FORK")) == 0);
-    const bool early = early_ok && use_tiles && pl->tile->side && !tm;
+    // their three launches are the longer branch).
+    const bool early = use_tiles && pl->tile->side && !tm;
     if (early) {
         SSQ_CHECK_HIP(hipEventRecord(pl->tile->ev_fork, stream));
         SSQ_CHECK_HIP(hipStreamWaitEvent(pl->tile->side, pl->tile->ev_fork, 0));

@@ -184,11 +184,8 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     // work-item's first column twiddle and the band's three loads per point -- is issued up front, into registers,
     // and only then are the staged values written to LDS and the barrier taken: the band's latency runs under the
     // staging instead of starting behind its barrier. Block rows 69.4 -> 64.0 us (an ablation without the band's
-    // loads runs at 51.8: profiles/r5_ab_history.txt). -DSSQ_BLOCK_EARLY=0: loads where they are used, as before.
-#ifndef SSQ_BLOCK_EARLY
-#define SSQ_BLOCK_EARLY 1
-#endif
-    constexpr bool EARLY = !STAGE && SSQ_BLOCK_EARLY && (R1 * G <= NT);
+    // loads runs at 51.8: profiles/r5_ab_history.txt).
+    constexpr bool EARLY = !STAGE && (R1 * G <= NT);
     float e_p[EARLY ? PPT : 1], e_m[EARLY ? PPT : 1];
     c32 e_X[EARLY ? PPT : 1], e_cw[EARLY ? PPT / R1 : 1];
     if constexpr (EARLY) {

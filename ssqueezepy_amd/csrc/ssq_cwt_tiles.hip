@@ -92,7 +92,6 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
         const TileRow* rw = reinterpret_cast<const TileRow*>(d.rows);
         const TileSeg* sg = reinterpret_cast<const TileSeg*>(d.segs);
         cols2 = tile2_lds_bytes(na, 32) <= 160 * 1024 ? 32 : 16;
-        if (const char* e = getenv("SSQ_DEBUG_TILE2_COLS")) if (atoi(e) == 16) cols2 = 16;     // (tuning aid)
         SSQ_REQUIRE(tile2_lds_bytes(na, cols2) <= 160 * 1024, "na = %lld: the Tx tile exceeds the LDS", (long long)na);
         lgr_max2 = 0;
         for (int i = 0; i < nsegs; ++i) if (sg[i].kind) lgr_max2 = std::max(lgr_max2, (int)sg[i].lgR);
@@ -142,8 +141,7 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
                 //   1. the interpolated items, class by class, are cut into `nw` chunks minimising the largest
                 //      (a chunk of several classes pays `chg_cost` per class: the weights are re-read per tile);
                 //   2. the items of rows read back need no weights: each goes to the wavefront with the least work;
-                //   3. the wavefronts w, w + 4, w + 8, ... share a SIMD: the lists are dealt so that the SIMDs' sums agree;
-                //   4. the item table is permuted so that a wavefront's list is contiguous (chunk, then rows read back).
+                //   3. the item table is permuted so that a wavefront's list is contiguous (chunk, then rows read back).
                 std::vector<int> iin, irb;
                 for (int it = 0; it < n_items; ++it) (icls[it] ? iin : irb).push_back(it);
                 const int ni = (int)iin.size();
@@ -158,19 +156,10 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
                 // youngest taking a third longer per item. speed[w]: what wavefront w gets done relative to the mean, by its
                 // age rank w / 4 -- chunk k goes to wavefront k, and "largest" above means largest time = cost / speed.)
                 // (measured at config 2, one box: skew 0 / 0.1 / 0.2 / 0.3 -> 193-196 / 187 / 184-186 / 191 us with 16 wavefronts;
-                // no gain with 12)
-                float skew = nw == 16 ? 0.2f : 0.f;
-                if (const char* e = getenv("SSQ_DEBUG_TILE3_SKEW")) skew = (float)atof(e);
-                std::vector<double> speed(nw, 1.0);
-                {
-                    const int nr = nw / 4;
-                    for (int w = 0; w < nw; ++w) speed[w] = 1.0 + skew * (nr > 1 ? 1.0 - 2.0 * (w / 4) / (double)(nr - 1) : 0.0);
-                    if (const char* e = getenv("SSQ_DEBUG_TILE3_SPEEDS")) {     // (A/B: a speed per age rank, "1.2,1.07,0.93,0.8")
-                        double v[8]; int n = 0;
-                        for (const char* q = e; *q && n < 8; ) { v[n++] = atof(q); while (*q && *q != ',' && *q != '/') ++q; if (*q) ++q; }
-                        if (n == nr) for (int w = 0; w < nw; ++w) speed[w] = v[w / 4];
-                    }
-                }
+                // no gain with 12) -- four age ranks, skew 0.2: 1.2 .. 0.8
+                static_assert(TILE3_NW == 16, "the speeds are those of four wavefronts per SIMD");
+                std::vector<double> speed(nw);
+                for (int w = 0; w < nw; ++w) speed[w] = 1.0 + 0.2f * (1.0 - 2.0 * (w / 4) / 3.0);
                 std::vector<std::vector<double>> f(nw + 1, std::vector<double>(ni + 1, 1e30));
                 std::vector<std::vector<int>> arg(nw + 1, std::vector<int>(ni + 1, 0));
                 f[0][0] = 0.0;
@@ -201,26 +190,11 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
                         load[best] += rb_cost;
                     }
                 }
-                // the SIMDs: heaviest list first, each to the SIMD with the least work that still has a slot
-                const int nsimd = 4, per = nw / nsimd;
-                std::vector<int> order(nw), slot_of(nw, -1);
-                for (int w = 0; w < nw; ++w) order[w] = w;
-                std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return load[a] > load[b]; });
-                std::vector<double> ssum(nsimd, 0.0);
-                std::vector<int> scnt(nsimd, 0);
-                for (int w : order) {
-                    int g = -1;
-                    for (int q = 0; q < nsimd; ++q) if (scnt[q] < per && (g < 0 || ssum[q] < ssum[g] - 1e-12)) g = q;
-                    slot_of[w] = scnt[g] * nsimd + g;
-                    ssum[g] += load[w]; ++scnt[g];
-                }
-                if (skew != 0.f) for (int w = 0; w < nw; ++w) slot_of[w] = w;      // (the speeds were the slots')
+                // (list k is wavefront k's: the speeds above are those of the wavefronts' slots)
                 std::vector<int32_t> hp((size_t)n_items * 8, 0), wrec((size_t)nw * 4, 0);
                 int pos = 0;
-                std::vector<int> list_of_slot(nw, 0);
-                for (int w = 0; w < nw; ++w) list_of_slot[slot_of[w]] = w;
                 for (int sl = 0; sl < nw; ++sl) {
-                    const std::vector<int>& L = lists[list_of_slot[sl]];
+                    const std::vector<int>& L = lists[sl];
                     const int first = pos;
                     int isp = -1;
                     for (size_t q = 0; q < L.size(); ++q) {
@@ -235,11 +209,6 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
                     wrec[4 * sl] = first; wrec[4 * sl + 1] = pos; wrec[4 * sl + 2] = isp; wrec[4 * sl + 3] = 0;
                 }
                 if (pos != n_items) ok = false;
-                if (getenv("SSQ_DEBUG_TILE_PLAN_PRINT")) {
-                    for (int sl = 0; sl < nw; ++sl)
-                        fprintf(stderr, "tile3 wave %2d (simd %d): items %3d..%3d second class at %3d, load %.2f\n", sl, sl % nsimd,
-                                wrec[4 * sl], wrec[4 * sl + 1], wrec[4 * sl + 2], load[list_of_slot[sl]]);
-                }
                 if ((rcb = up(items_dev, hp.data(), hp.size() * 4))) return rcb;
                 return up((void**)waves_dev, wrec.data(), wrec.size() * 4);
             }
@@ -285,15 +254,12 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
         };
         if ((rc = build(64 / cols2, TILE2_NW, false, 0.7f, -1.f, 2, &items2, &wave_first2, n_items2, tile2_ok))) return rc;
         tile3_ok = false;
-        if (cols2 == 32 && TILE_G == 4) {
+        if (cols2 == 32) {
             // (measured with shader-clock stamps, round 6: an item of rows read back costs 0.45 of an interpolated one,
             // re-reading a class's weights 0.65)
-            float rb3 = 0.45f, chg3 = 0.65f;
-            if (const char* e = getenv("SSQ_DEBUG_TILE3_RB")) if (atof(e) > 0) rb3 = (float)atof(e);
-            if (const char* e = getenv("SSQ_DEBUG_TILE3_CHG")) if (atof(e) >= 0) chg3 = (float)atof(e);
-            if ((rc = build(4, TILE3_NW, true, rb3, chg3, 1 << 20, &items3, &wave_first3, n_items3, tile3_ok))) return rc;
+            if ((rc = build(4, TILE3_NW, true, 0.45f, 0.65f, 1 << 20, &items3, &wave_first3, n_items3, tile3_ok))) return rc;
             // (the 16 lanes of a sub-row hold the sample window of the tile's 32 columns: (31 >> lgR) + 8 + 1 <= 16 needs
-            // a decimation of 4 or more -- R_MIN of _tiles.py; SSQ_DEBUG_TILE_RMIN=2 plans go to tile2_kernel)
+            // a decimation of 4 or more -- R_MIN of _tiles.py; plans with a smaller one go to tile2_kernel)
             for (int i = 0; i < nsegs; ++i) if (sg[i].kind && sg[i].lgR < 2) tile3_ok = false;
         }
     }

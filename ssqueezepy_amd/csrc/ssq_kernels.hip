@@ -370,119 +370,6 @@ __global__ __launch_bounds__(64 * (TC / (64 / RL)), WPS) void accumulate_tile16_
     }
 }
 
-// ------------------------------------------- accumulate, LDS-tile form, quad variant
-// Same tile and same exactness contract as accumulate_tile16_kernel, organised the
-// other way round: one wavefront owns the whole 16-column tile, lane = 4*col + rl, so
-// the four rows of a step that belong to one column are a DPP quad. A step therefore
-// needs only 3 pair tests (quad_perm moves) instead of 15, loads and stores are full
-// 128-byte row segments (4 rows per instruction), and the per-step instruction count
-// drops ~2.5x. The price is one wavefront per SIMD (4 tiles per CU), so memory latency
-// is covered by a deep rolling prefetch (4*U rows in flight per column) rather than by
-// other waves.
-template <typename T, int BINSRC, bool STFT, bool CST64, int U>
-__global__ __launch_bounds__(64, 1) void accumulate_quad_kernel(
-    const T* __restrict__ Wx, const void* __restrict__ src, const T* __restrict__ Sfs,
-    T* __restrict__ Tx, const void* __restrict__ cst, SsqParams sp, int64_t na64, int64_t n64,
-    int32_t* __restrict__ kmap) {
-    constexpr int RL = 4, TC = 16;
-    using TM = Term<T, CST64>;
-    using term_t = typename TM::type;
-    using w_t = typename TM::wtype;
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    T* tile = reinterpret_cast<T*>(lds_raw);       // [na][16][2], cells skewed
-    const int na = (int)na64, n = (int)n64;        // host guarantees na * n < 2^31
-    const int lane = threadIdx.x;
-    const int c = lane >> 2, rl = lane & 3;
-    const int per = gridDim.x >> 3;                // grid.x is a multiple of 8
-    const int tile_id = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    if (tile_id * TC >= n) return;
-    const int j = tile_id * TC + c;
-    const bool col_ok = j < n;
-    const int64_t omax = na - 1;
-    const size_t boff = (size_t)blockIdx.y * (size_t)na * (size_t)n;
-    const T* Wb = Wx + 2 * boff;
-    T* Tb = Tx + 2 * boff;
-    int32_t* kb = kmap ? kmap + boff : nullptr;
-    const char* sb = (const char*)src + boff * SideVal<T, BINSRC>::stride;
-
-    for (int t = lane; t < na * TC; t += 64) { tile[2 * t] = T(0); tile[2 * t + 1] = T(0); }
-    __builtin_amdgcn_wave_barrier();
-
-    T zc[U], zd[U];
-    w_t wt[U];
-    SideVal<T, BINSRC> sv[U];
-    const bool uni = sp.cst_uniform != 0;          // scalar weight: one load per kernel
-    const w_t w0 = ((const w_t*)cst)[0];
-    // Loads are unconditional (row and column clamped into the array, the point is
-    // discarded at its use when it lies outside): with a branch around them the compiler
-    // loses count of the loads in flight and drains them all (s_waitcnt vmcnt(0)) before
-    // every use, which turns the rolling prefetch into one batch at a time.
-    const int jc = col_ok ? j : n - 1;
-    auto request = [&](int u, int i) {
-        const int ic = i < na ? i : na - 1;
-        const unsigned q = (unsigned)ic * (unsigned)n + (unsigned)jc;
-        zc[u] = Wb[2 * (size_t)q];
-        zd[u] = Wb[2 * (size_t)q + 1];
-        sv[u].load(sb, q, ic, jc, na);
-        if (!uni) wt[u] = ((const w_t*)cst)[ic];
-    };
-#pragma unroll
-    for (int u = 0; u < U; ++u) request(u, u * RL + rl);
-
-    for (int i0 = 0; i0 < na; i0 += RL * U) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * RL + rl;
-            int k = -1;
-            if (col_ok && i < na) {
-                k = (int)point_bin<T, BINSRC, STFT>(zc[u], zd[u], sv[u], i, Sfs, sp, omax);
-                if (kb) kb[(unsigned)i * (unsigned)n + (unsigned)j] = k;
-            }
-            term_t tr = term_t(0), ti = term_t(0);
-            T ore = T(0), oim = T(0);
-            T* cell = tile;
-            if (k >= 0) {
-                const w_t wsel = uni ? w0 : wt[u];
-                tr = TM::make(zc[u], wsel);
-                ti = TM::make(zd[u], wsel);
-                cell = tile + 2 * (k * TC + ((c + k) & 15));
-                ore = cell[0]; oim = cell[1];
-            }
-            request(u, i + RL * U);                 // refill the slot
-            // lower rows of this column, ascending: quad lanes rl-3, rl-2, rl-1
-            // (quad_perm [0,0,0,0], [0,0,0,1], [0,0,1,2]); -1 never matches a valid bin
-            const int k3 = dpp_mov<0x00>(-1, k), k2 = dpp_mov<0x40>(-1, k), k1 = dpp_mov<0x90>(-1, k);
-            const term_t r3 = dpp_mov<0x00>(term_t(0), tr), i3 = dpp_mov<0x00>(term_t(0), ti);
-            const term_t r2 = dpp_mov<0x40>(term_t(0), tr), i2 = dpp_mov<0x40>(term_t(0), ti);
-            const term_t r1 = dpp_mov<0x90>(term_t(0), tr), i1 = dpp_mov<0x90>(term_t(0), ti);
-            if (rl >= 3 && k3 == k) { ore = TM::fold(ore, r3); oim = TM::fold(oim, i3); }
-            if (rl >= 2 && k2 == k) { ore = TM::fold(ore, r2); oim = TM::fold(oim, i2); }
-            if (rl >= 1 && k1 == k) { ore = TM::fold(ore, r1); oim = TM::fold(oim, i1); }
-            ore = TM::fold(ore, tr); oim = TM::fold(oim, ti);
-            // a higher row of the quad hitting the same cell writes it instead
-            // (quad_perm [1,2,3,3], [2,3,3,3], [3,3,3,3])
-            const int h1 = dpp_mov<0xF9>(-1, k), h2 = dpp_mov<0xFE>(-1, k), h3 = dpp_mov<0xFF>(-1, k);
-            const bool last = !((rl <= 2 && h1 == k) || (rl <= 1 && h2 == k) || (rl == 0 && h3 == k));
-            if (k >= 0 && last) { cell[0] = ore; cell[1] = oim; }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    {
-        const int cc = lane & 15, rr = lane >> 4;
-        const int jj = tile_id * TC + cc;
-        if (jj < n) {
-#pragma unroll 4
-            for (int k = rr; k < na; k += 4) {
-                const T* cell = tile + 2 * (k * TC + ((cc + k) & 15));
-                size_t q = (size_t)((unsigned)k * (unsigned)n + (unsigned)jj);
-                Tb[2 * q] = cell[0];
-                Tb[2 * q + 1] = cell[1];
-            }
-        }
-    }
-}
-
 // --------------------------------- accumulate from a bin map, float64 tile, unordered
 // The bins are known (2-byte map written by the producer), so a point costs two LDS float64
 // adds (ds_add_f64, no return value) into a tile of `na` x COLS float64 cells held as a real and
@@ -591,11 +478,11 @@ template <typename T> static int f64_tile_cols(int64_t na, size_t lds_cap) {
     return 0;
 }
 
-template <typename T, bool CST64, int NW>
-static int launch_accumulate_f64_w(const void* Wx, const void* kidx, void* Tx, const void* cst,
-                                   const SsqParams& sp, int64_t batch, int64_t na, int64_t n,
-                                   int cols, hipStream_t stream) {
-    constexpr int U = 4;
+template <typename T, bool CST64>
+static int launch_accumulate_f64(const void* Wx, const void* kidx, void* Tx, const void* cst,
+                                 const SsqParams& sp, int64_t batch, int64_t na, int64_t n,
+                                 int cols, hipStream_t stream) {
+    constexpr int NW = 8, U = 4;                   // wavefronts per tile, rows in flight per lane
     const size_t lds = (size_t)na * cols * 16;
     dim3 grid((unsigned)(((n + cols - 1) / cols + 7) / 8 * 8), (unsigned)batch);
 #define SSQ_ACC64(C)                                                                               \
@@ -607,21 +494,12 @@ static int launch_accumulate_f64_w(const void* Wx, const void* kidx, void* Tx, c
                            (const unsigned short*)kidx, (T*)Tx, cst, (int)sp.cst_uniform, (int)na, \
                            (int)n);                                                                \
     }
-    if (cols == 32) SSQ_ACC64(32) else if (cols == 16) SSQ_ACC64(16) else SSQ_ACC64(8)
+    if (cols == 32) SSQ_ACC64(32)
+    else if (cols == 16) SSQ_ACC64(16)
+    else if constexpr (sizeof(T) == 8) SSQ_ACC64(8)      // (8 columns: float64 data only, see f64_tile_cols)
 #undef SSQ_ACC64
     SSQ_LAUNCH_CHECK();
     return 0;
-}
-
-template <typename T, bool CST64>
-static int launch_accumulate_f64(const void* Wx, const void* kidx, void* Tx, const void* cst,
-                                 const SsqParams& sp, int64_t batch, int64_t na, int64_t n,
-                                 int cols, hipStream_t stream) {
-    // wavefronts per tile (SSQ_DEBUG_ACC64_NW = 4 / 8 / 16, tuning aid; default 8)
-    static const int nw = getenv("SSQ_DEBUG_ACC64_NW") ? atoi(getenv("SSQ_DEBUG_ACC64_NW")) : 8;
-    if (nw == 16) return launch_accumulate_f64_w<T, CST64, 16>(Wx, kidx, Tx, cst, sp, batch, na, n, cols, stream);
-    if (nw == 4) return launch_accumulate_f64_w<T, CST64, 4>(Wx, kidx, Tx, cst, sp, batch, na, n, cols, stream);
-    return launch_accumulate_f64_w<T, CST64, 8>(Wx, kidx, Tx, cst, sp, batch, na, n, cols, stream);
 }
 
 // ---------------------------------------------- accumulate, global fallback
@@ -659,9 +537,7 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
     if constexpr (BINSRC == BIN_FROM_KIDX) {
         // known bins: the unordered float64 tile (see accumulate_f64_kernel) unless the caller
         // asked for the ordered sums or wants the bin map back
-        int cols = f64_tile_cols<T>(na, lds_cap);
-        static const int cols_env = getenv("SSQ_DEBUG_ACC64_COLS") ? atoi(getenv("SSQ_DEBUG_ACC64_COLS")) : 0;   // (tuning aid)
-        if ((cols_env == 8 || cols_env == 16 || cols_env == 32) && (size_t)na * cols_env * 16 <= lds_cap) cols = cols_env;
+        const int cols = f64_tile_cols<T>(na, lds_cap);
         if (!reassign_ordered() && !kmap && cols && (size_t)na * (size_t)n < ((size_t)1 << 31))
             return launch_accumulate_f64<T, CST64>(Wx, src, Tx, cst, sp, batch, na, n, cols, stream);
     }
@@ -682,24 +558,19 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
         size_t lds = (size_t)na * 16 * cell;
         if ((size_t)na * (size_t)n < ((size_t)1 << 31)) {      // 32-bit offsets inside
             dim3 grid((unsigned)(((n + 15) / 16 + 7) / 8 * 8), (unsigned)batch);
-            static const int variant = getenv("SSQ_DEBUG_ACC_VARIANT") ? atoi(getenv("SSQ_DEBUG_ACC_VARIANT")) : 0;
-            if (variant != 2) {        // row-lane layouts (variant 2: one wavefront per tile, quads)
-                // Row batches in flight per lane. Measured (config 2, float32), 16 row-lanes:
-                // U = 2: 257 us, 3: 263, 4: 259, 8: 278; 8 row-lanes: U = 1: 314, 2: 246, 3: 240,
-                // 4: 243, 8: 267 -- the resident wavefronts cover most of the latency, and a
-                // deep prefetch spreads each wavefront's requests over more DRAM pages.
-                constexpr int U = sizeof(T) == 4 ? 2 : 4;       // 16 row-lanes
-                constexpr int U8 = 3;                           // 8 row-lanes
-                // float32 with a tall tile (na * 32 cells over half the LDS): 8 row-lanes x 8 columns
-                // per wavefront, 2 wavefronts per 16-column tile (240 us at config 2 vs 250 with 16
-                // row-lanes); float64 -> 16 row-lanes x 4 columns, 4 wavefronts (config 5: 22.7 vs
-                // 23.6 ms).
-                // SSQ_DEBUG_ACC_VARIANT = 1 / 3 force the 16- / 8-lane layout.
-                if ((variant == 0 || variant == 9) && sizeof(T) == 4 &&
-                    (size_t)na * 32 * cell <= lds_cap / 2) {
-                    // float32 default: 32-column tiles of four 8-lane wavefronts (256-byte row
-                    // segments per workgroup, 2 workgroups per CU): 232 us at config 2 vs 240 with
-                    // 16-column tiles (64-column tiles, one workgroup per CU: 231)
+            // Row batches in flight per lane. Measured (config 2, float32), 16 row-lanes:
+            // U = 2: 257 us, 3: 263, 4: 259, 8: 278; 8 row-lanes: U = 1: 314, 2: 246, 3: 240,
+            // 4: 243, 8: 267 -- the resident wavefronts cover most of the latency, and a
+            // deep prefetch spreads each wavefront's requests over more DRAM pages.
+            // float32: 8 row-lanes x 8 columns per wavefront, 2 wavefronts per 16-column tile (240 us
+            // at config 2 vs 250 with 16 row-lanes); float64: 16 row-lanes x 4 columns, 4 wavefronts
+            // (config 5: 22.7 vs 23.6 ms).
+            if constexpr (sizeof(T) == 4) {
+                constexpr int U8 = 3;
+                if ((size_t)na * 32 * cell <= lds_cap / 2) {
+                    // 32-column tiles of four 8-lane wavefronts (256-byte row segments per workgroup,
+                    // 2 workgroups per CU): 232 us at config 2 vs 240 with 16-column tiles (64-column
+                    // tiles, one workgroup per CU: 231)
                     auto kern = accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U8, 2, 8, 32>;
                     const size_t lds32 = (size_t)na * 32 * cell;
                     SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -707,26 +578,19 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
                     dim3 grid32((unsigned)(((n + 31) / 32 + 7) / 8 * 8), (unsigned)batch);
                     hipLaunchKernelGGL(kern, grid32, dim3(256), lds32, stream, (const T*)Wx, src, (const T*)Sfs,
                                        (T*)Tx, cst, sp, na, n, kmap);
-                } else
-                if (variant == 3 || (variant == 0 && sizeof(T) == 4)) {
+                } else {
                     auto kern = accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U8, 2, 8>;
                     SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                     hipLaunchKernelGGL(kern, grid, dim3(128), lds, stream, (const T*)Wx, src, (const T*)Sfs,
                                        (T*)Tx, cst, sp, na, n, kmap);
-                } else {
+                }
+            } else {
+                constexpr int U = 4;
                 auto kern = accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U, 4, 16>;
                 SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)Wx, src, (const T*)Sfs,
-                                   (T*)Tx, cst, sp, na, n, kmap);
-                }
-            } else {                   // SSQ_DEBUG_ACC_VARIANT=2: one wave per tile, quads (tuning aid)
-                constexpr int U = sizeof(T) == 4 ? 16 : 8;
-                auto kern = accumulate_quad_kernel<T, BINSRC, STFT, CST64, U>;
-                SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, grid, dim3(64), lds, stream, (const T*)Wx, src, (const T*)Sfs,
                                    (T*)Tx, cst, sp, na, n, kmap);
             }
             SSQ_LAUNCH_CHECK();
@@ -751,15 +615,17 @@ template <typename T, int BINSRC>
 static int launch_accumulate_b(const void* Wx, const void* src, const void* Sfs, void* Tx,
                                const void* cst, const SsqParams& sp, int64_t batch,
                                int64_t na, int64_t n, int32_t* kmap, hipStream_t stream) {
-    const bool c64 = sp.cst_f64 && sizeof(T) == 4;
-    if (Sfs) {
-        if constexpr (BINSRC == BIN_FROM_DWX) {
-            return c64 ? launch_accumulate_t<T, BINSRC, true, true>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream)
-                       : launch_accumulate_t<T, BINSRC, true, false>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
+    // (a float64 weight vector changes the product for float32 data only: float64 data multiplies in float64 anyway)
+    if constexpr (sizeof(T) == 4) {
+        if (sp.cst_f64) {
+            if constexpr (BINSRC == BIN_FROM_DWX)
+                if (Sfs) return launch_accumulate_t<T, BINSRC, true, true>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
+            return launch_accumulate_t<T, BINSRC, false, true>(Wx, src, nullptr, Tx, cst, sp, batch, na, n, kmap, stream);
         }
     }
-    return c64 ? launch_accumulate_t<T, BINSRC, false, true>(Wx, src, nullptr, Tx, cst, sp, batch, na, n, kmap, stream)
-               : launch_accumulate_t<T, BINSRC, false, false>(Wx, src, nullptr, Tx, cst, sp, batch, na, n, kmap, stream);
+    if constexpr (BINSRC == BIN_FROM_DWX)
+        if (Sfs) return launch_accumulate_t<T, BINSRC, true, false>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
+    return launch_accumulate_t<T, BINSRC, false, false>(Wx, src, nullptr, Tx, cst, sp, batch, na, n, kmap, stream);
 }
 
 int launch_accumulate(int dtype, int binsrc, const void* Wx, const void* src, const void* Sfs,

@@ -23,14 +23,10 @@ template <typename R> __device__ __forceinline__ cx<R> cmul(cx<R> a, cx<R> b) {
 // the same product for operands that live in registers (twiddles from tables, data): float32 in two
 // packed instructions (SSQ_CMUL_PK; rounds the a.x products first, where `cmul` rounds the a.y ones)
 __device__ __forceinline__ cx<float> cmul_v(cx<float> a, cx<float> b) {
-#ifdef SSQ_NO_CMUL_PK
-    return cmul(a, b);
-#else
     ssq_f2 av, bv, dv;
     av.x = a.x; av.y = a.y; bv.x = b.x; bv.y = b.y;
     SSQ_CMUL_PK(dv, av, bv);
     return {dv.x, dv.y};
-#endif
 }
 __device__ __forceinline__ cx<double> cmul_v(cx<double> a, cx<double> b) { return cmul(a, b); }
 template <typename R> __device__ __forceinline__ cx<R> cadd(cx<R> a, cx<R> b) { return {a.x + b.x, a.y + b.y}; }

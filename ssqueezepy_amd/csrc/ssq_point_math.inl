@@ -277,7 +277,6 @@ __device__ __forceinline__ int bin_of_point_stft(float a, float b, float c, floa
 // difference (cancellation: the bound is absolute, on the products' magnitudes), the reciprocal, 2 pi as a float.
 __device__ __forceinline__ int64_t bin_of_point(double a, double b, double c, double d, bool stft,
                                                 double sfs, const SsqParams& sp, int64_t omax) {
-#ifndef SSQ_F64_NO_SCREEN
     {
         const float af = (float)a, bf = (float)b, cf = (float)c, df = (float)d;
         const float p1 = bf * cf, p2 = af * df, num = p1 - p2;
@@ -299,7 +298,6 @@ __device__ __forceinline__ int64_t bin_of_point(double a, double b, double c, do
             if (k != -2) return k;
         }
     }
-#endif
     double r = phase_ratio(a, b, c, d);
     double w = stft ? fabs(sfs - r) : fabs(r);
     return bin_from_w(w, sp, omax);

@@ -26,12 +26,6 @@ namespace ssq {
 
 #include "ssq_point_math.inl"
 
-#ifdef STFT_STAMPS
-__device__ unsigned long long g_stft_prof[16];
-#define ST_STAMP(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (threadIdx.x == 0) atomicAdd(&g_stft_prof[i], t_ - tprev); tprev = t_; } while (0)
-#else
-#define ST_STAMP(i) do {} while (0)
-#endif
 typedef float ssq_f4 __attribute__((ext_vector_type(4)));
 typedef float ssq_f4a4 __attribute__((ext_vector_type(4), aligned(4)));     // 16 bytes at a sample's 4-byte boundary
 
@@ -102,9 +96,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
         item = (item & 7) * per + (item >> 3);
     }
     if (item >= total) return;
-#ifdef STFT_STAMPS
-    unsigned long long tprev = __builtin_amdgcn_s_memtime();
-#endif
     {
         const int b = (int)(item / ng), c0 = (int)(item % ng) * G;
         const int t0 = A.hop * c0 - A.n1;                      // the first sample's index in the signal
@@ -138,7 +129,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
                 }
             }
             __syncthreads();
-            ST_STAMP(0);
 #pragma unroll
             for (int it = 0; it < NB; ++it) {
                 const int idx = tid + it * NT, g = idx % G, u = idx / G;
@@ -152,7 +142,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
                 }
             }
             __syncthreads();                                   // the samples are in registers: the buffer is the FFT's
-            ST_STAMP(1);
         } else {
             const float* xp = A.xp + (int64_t)b * A.padlen;
             const float* xs = A.x + (int64_t)b * A.n - A.n1;
@@ -179,9 +168,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
                     z[it * R1 + k] = {a, -bb};
                 }
             }
-#ifdef STFT_STAMPS
-            __builtin_amdgcn_s_waitcnt(0); ST_STAMP(1);
-#endif
         }
         // the rows' frequencies of the epilogue's points (and the weight of the reference's linear grid -- a weight
         // vector is read where it is used) are asked for here, a transform ahead of their use
@@ -194,7 +180,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
         // (FRESH: a barrier has just passed; the twiddles asked for ahead of each pass' barrier measured no gain here)
         lds_ifft<L, G, R1, R2, R3, false, true>(z, buf, A.ftw, tid);
         __syncthreads();                              // last pass' LDS reads are done
-        ST_STAMP(2);
         {
             constexpr int NB = PPT / RL, STR = L / RL;
 #pragma unroll
@@ -205,7 +190,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
             }
         }
         __syncthreads();
-        ST_STAMP(3);
         const int64_t base = (int64_t)b * A.rows * A.n_hops;
         if constexpr (!REASSIGN) {
             for (int i = tid; i < (L / 2 + 1) * G; i += NT) {
@@ -252,11 +236,9 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
                 vr[it] = sr; vi[it] = si;
                 if (it % 3 == 2) SSQ_SCHED_FENCE();            // (three points' LDS reads in flight, not all nine)
             }
-            ST_STAMP(4);
             __syncthreads();                              // the buffer's last read
             for (int i = tid; i < 2 * CELLS; i += NT) txt[i] = 0.0;
             __syncthreads();
-            ST_STAMP(5);
 #pragma unroll
             for (int it = 0; it < NI; ++it) {
                 if (kq[it] == 0xFFFFu) continue;
@@ -270,17 +252,11 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
                 SSQ_LDS_ADD_F64(txt, off + (unsigned)CELLS * 8u, ti);
             }
             __syncthreads();
-            ST_STAMP(6);
             for (int i = tid; i < (L / 2 + 1) * G; i += NT) {
                 const int f = i / G, g = i % G, c = c0 + g;
                 if (c >= A.n_hops) continue;
                 A.Tx[base + (int64_t)f * A.n_hops + c] = make_float2((float)txt[i], (float)txt[CELLS + i]);
             }
-            ST_STAMP(7);
-#ifdef STFT_STAMPS
-            __builtin_amdgcn_s_waitcnt(0);
-            ST_STAMP(8);
-#endif
         }
     }
 }
@@ -289,11 +265,10 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
 template <int L, int G, int R1, int R2, int R3>
 static int launch_stft_fused(const StftFusedArgs& A, const SsqParams& sp, int64_t batch, hipStream_t stream) {
     SSQ_REQUIRE(!A.Tx || A.rows == L / 2 + 1, "fused reassignment: %lld rows, transform of %d", (long long)A.rows, L);
-    static const bool remap = [] { const char* e = getenv("SSQ_DEBUG_STFT_XCD"); return !e || atoi(e) != 0; }();
     StftFusedArgs B = A;
     B.batch = (int)batch;
     int64_t total = (int64_t)((A.n_hops + G - 1) / G) * batch;
-    B.xcd = remap && total >= 64;
+    B.xcd = total >= 64;
     if (B.xcd) total = (total + 7) & ~(int64_t)7;
     // (grid.x a multiple of 8 when the items are remapped, so that the product is one too)
     const int64_t gx = std::min<int64_t>(total, (int64_t)1 << 20), gy = (total + gx - 1) / gx;
@@ -406,9 +381,7 @@ int ssq_stft_plan_create(ssq_stft_plan** out, const ssq_stft_desc* desc) {
     TRYA(pl->xp, (size_t)pl->d.max_batch * pl->padlen * rs);
 #undef TRYA
     const bool pow2 = (d.n_fft & (d.n_fft - 1)) == 0;
-    // (SSQ_DEBUG_STFT_MIXED=1: the mixed-radix kernel for the powers of two as well -- A/B aid)
-    const bool prefer_mixed = getenv("SSQ_DEBUG_STFT_MIXED") && atoi(getenv("SSQ_DEBUG_STFT_MIXED")) != 0;
-    if (d.dtype == SSQ_F32 && pow2 && d.n_fft >= 128 && d.n_fft <= 2048 && !getenv("SSQ_DEBUG_STFT_GENERIC") && !prefer_mixed) {
+    if (d.dtype == SSQ_F32 && pow2 && d.n_fft >= 128 && d.n_fft <= 2048 && !getenv("SSQ_DEBUG_STFT_GENERIC")) {
         std::vector<float> tw((size_t)2 * d.n_fft);
         for (int64_t q = 0; q < d.n_fft; ++q) {
             double ang = 2.0 * 3.14159265358979323846 * (double)q / (double)d.n_fft;
@@ -488,11 +461,6 @@ int ssq_stft_plan_set_ssq(ssq_stft_plan* pl, const void* Sfs, int grid, const do
     return 0;
 }
 
-#ifdef STFT_STAMPS
-int ssq_debug_stft_prof(unsigned long long* out) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ssq::g_stft_prof), sizeof(unsigned long long) * 16);
-}
-#endif
 const char* ssq_stft_plan_algo(const ssq_stft_plan* pl) {
     return !pl ? "" : pl->fused ? "fused" : pl->generic_fused ? "fused-mixed-radix" : "rocfft";
 }

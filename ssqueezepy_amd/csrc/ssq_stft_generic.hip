@@ -251,9 +251,7 @@ bool stft_generic_plan(int64_t n, int* radix, int* npass, int* G) {
     int g = 16;
     // Four workgroups per CU (39 KB each) where at least four frames still fit, two (78 KB) for the longer transforms:
     // n_fft = 598 at G = 4 instead of 8 measured 0.87 -> 0.78 ms at hop 1 ("r6y15"; G = 2, eight workgroups: 1.21 ms).
-    // (SSQ_DEBUG_STFT_GEN_LDS=<KB> moves the first limit -- A/B aid)
-    static const int64_t soft_cap = [] { const char* e = getenv("SSQ_DEBUG_STFT_GEN_LDS"); return e && atoi(e) > 0 ? (int64_t)atoi(e) * 1024 : (int64_t)GEN_LDS_BYTES / 2; }();
-    while (g > 4 && n * g * 16 > std::min<int64_t>(soft_cap, GEN_LDS_BYTES)) g >>= 1;
+    while (g > 4 && n * g * 16 > GEN_LDS_BYTES / 2) g >>= 1;
     while (g > 1 && n * g * 16 > GEN_LDS_BYTES) g >>= 1;
     *npass = np; *G = g;
     return true;
@@ -261,7 +259,6 @@ bool stft_generic_plan(int64_t n, int* radix, int* npass, int* G) {
 
 int launch_stft_generic(const StftFusedArgs& A, const SsqParams& sp, const c32* tw, int n, const int* radix,
                                int npass, int G, int64_t batch, hipStream_t stream) {
-    static const bool remap = [] { const char* e = getenv("SSQ_DEBUG_STFT_XCD"); return !e || atoi(e) != 0; }();
     StftGenArgs B;
     B.F = A; B.tw = tw; B.n = n; B.G = G; B.npass = npass;
     B.lgG = 0; while ((1 << B.lgG) < G) ++B.lgG;
@@ -275,7 +272,7 @@ int launch_stft_generic(const StftFusedArgs& A, const SsqParams& sp, const c32* 
         }
     }
     unsigned nb = (unsigned)((A.n_hops + G - 1) / G);
-    B.F.xcd = remap && nb >= 64;
+    B.F.xcd = nb >= 64;
     if (B.F.xcd) nb = (nb + 7u) & ~7u;
     const size_t lds = (size_t)2 * n * G * sizeof(c32);
     SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_generic_kernel),

@@ -7,14 +7,10 @@ constexpr int TILE_W = 8;         // taps
 constexpr int TILE_NOBIN = 0xFFFF;
 
 __device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-#ifdef SSQ_NO_CMUL_PK
-    return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
-#else
     ssq_f2 av, bv, dv;
     av.x = a.x; av.y = a.y; bv.x = b.x; bv.y = b.y;
     SSQ_CMUL_PK(dv, av, bv);
     return make_float2(dv.x, dv.y);
-#endif
 }
 
 // bin of a point the float32 screens could not decide (flipped as Tx wants it), or -1 when it

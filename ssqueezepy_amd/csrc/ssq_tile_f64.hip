@@ -16,7 +16,7 @@
 // the gather, the modulation or the bin arithmetic are taken out, it is the same on 64 and on 256
 // CUs (per tile), and LDS *float32* atomics, the obvious way around the tickets, take 193 cycles
 // per wavefront instruction -- while ds_add_f64 takes 13.6 and ds_add_u64 10.8
-// (tools/probes/lds_atomic_probe.hip).
+// (tools/probes/lds_rmw_probe.hip).
 //
 // So the tile is kept in float64 and every wavefront adds its terms as soon as it has them
 // (ds_add_f64, no return value): 16 bytes per cell, hence COLS = 32 columns per tile (16 when

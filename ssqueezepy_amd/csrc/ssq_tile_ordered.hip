@@ -74,7 +74,7 @@ struct TileArgs {
 // read in the same round trip as the ticket); the language-level ordering costs one more LDS round trip per step.
 __device__ __forceinline__ void lds_release_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); }
 __device__ __forceinline__ void lds_acquire_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
-__device__ __forceinline__ void lds_store_release(int* p, int v) {
+__device__ __forceinline__ void lds_release_write(int* p, int v) {
     lds_release_fence();
     __scoped_atomic_store_n(p, v, __ATOMIC_RELAXED, __MEMORY_SCOPE_WRKGRP);
 }
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(64 * NW) void tile_kernel(TileArgs A, SsqParams sp)
             const int before = __scoped_atomic_fetch_add(wdone, 1, __ATOMIC_RELAXED, __MEMORY_SCOPE_WRKGRP);
             lds_acquire_fence();                               // (... and every other wavefront's, before the tickets reopen)
             if (before + 1 == NW * (itl + 1)) {
-                lds_store_release(turn, boundary + 1);
+                lds_release_write(turn, boundary + 1);
                 if (A.counters) __scoped_atomic_fetch_add(A.counters, 1ull, __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE);
             }
         }

@@ -49,10 +49,7 @@ struct AnalyticFft {
 
 // ---- geometry both tile kernels and the plan agree on
 constexpr int TILE_COLS = 64;           // ordered kernel: columns per tile (one per lane)
-#ifndef SSQ_TILE_G
-#define SSQ_TILE_G 4
-#endif
-constexpr int TILE_G = SSQ_TILE_G;      // rows per step of the host's tables (_tiles.py: RSUB)
+constexpr int TILE_G = 4;      // rows per step of the host's tables (_tiles.py: RSUB)
 constexpr int TILE2_NW = 16;            // tile2_kernel: wavefronts per workgroup (one workgroup per CU)
 constexpr int TILE3_NW = 16;            // tile3_kernel: the same
 // LDS of a workgroup: the ordered kernel's (na + 1) x 64 float32 pairs + ticket words; the default kernel's

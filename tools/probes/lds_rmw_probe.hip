@@ -1,10 +1,10 @@
-// lds_atomic_probe.hip -- how fast does one CU's LDS perform read-modify-write operations on a tile
+// lds_rmw_probe.hip -- how fast does one CU's LDS perform read-modify-write operations on a tile
 // shared by 12 wavefronts? (round 4: the unordered reassignment with ds_add_f32 measured 2.5x slower
 // than the ticketed one; this probe separates the instruction's own rate from everything else.)
 // One 768-thread workgroup per CU, 154 KB of LDS, every wavefront issues ITER operations of one kind
 // on cells (bin * 64 + lane) -- lane = column, as in the tile kernel -- with `bin` either random per
 // lane, the same for the wavefront, or the same for all wavefronts.
-//   hipcc --offload-arch=gfx950 -O3 tools/probes/lds_atomic_probe.hip -o tools/probes/lds_atomic_probe
+//   hipcc --offload-arch=gfx950 -O3 tools/probes/lds_rmw_probe.hip -o tools/probes/lds_rmw_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
