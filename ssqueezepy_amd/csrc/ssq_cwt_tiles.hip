@@ -1,12 +1,13 @@
 // ssq_cwt_tiles.hip -- the column-tile path of the fused ssq_cwt form (float32, gfx950): the plan object.
 //
-// Math and planning: ssqueezepy_amd/_tiles.py. The device code lives in three translation units:
+// Math and planning: ssqueezepy_amd/_tiles.py. The device code lives in four translation units:
 //   ssq_tile_fft.hip      the intermediates (decimated baseband samples of the interpolated rows; the analytic signal)
-//   ssq_tile_f64.hip      tile2_kernel -- float64 Tx tile in LDS, unordered ds_add_f64: the default
+//   ssq_tile_pair.hip     tile3_kernel -- float64 Tx tile in LDS, unordered ds_add_f64, two columns per lane: the default
+//   ssq_tile_f64.hip      tile2_kernel -- the same with one column per lane (16-column tiles for 319 .. 511 rows)
 //   ssq_tile_ordered.hip  tile_kernel  -- float32 tile, terms added in the reference's row order by a ticket
 //                         (SSQ_TILE_ORDER=ordered: Tx bit for bit the CPU loop's)
-// Here: the tables both kernels walk (TilePlan::create), the choice between them (usable / tile_cols / run), what
-// executed (tiles_done).
+// (ssq_tile_dev.h: the device pieces they share.) Here: the tables the kernels walk (TilePlan::create), the choice
+// between them (tile_kernel), the arguments and grid of tile2_kernel / tile3_kernel, what executed (tiles_done).
 #include "ssq_common.h"
 #include "ssq_tiles.h"
 #include <algorithm>
@@ -15,6 +16,179 @@
 namespace ssq {
 
 int tile_rows_per_step() { return TILE_G; }
+
+// The default kernels' items: `rpi` consecutive rows of a step, one record of 8 words per item:
+// row0 | padded sub-rows << 9 | kind << 12 | lgR << 13 (| the weights' table offset << 18: tile3_kernel),
+// samples of sub-row 0 (class offset + row in class * L), row0 * N * 8, entries between two signals' rows of the
+// class, centre bins. tile2_kernel (ssq_tile_f64.hip): rpi = 64 / columns per tile; tile3_kernel
+// (ssq_tile_pair.hip): 4 rows x 32 columns, two columns per lane.
+struct ItemTable {
+    int n = 0;
+    std::vector<int32_t> rec;       // [n][8]
+    std::vector<int32_t> cls;       // per item: 0 rows read back, 1 + lgR interpolated
+    std::vector<int32_t> woff;      // per item: the weights' table offset (interpolated)
+    bool ok = true;                 // the records can hold the tables (sub-rows consecutive, offsets in range)
+};
+static ItemTable pack_items(const TileSeg* sg, int nsegs, const TileRow* rw, int nsteps, int64_t M, int64_t N, int rpi,
+                            bool woff_in_record) {
+    ItemTable t;
+    t.n = nsteps * TILE_G / rpi;
+    t.rec.assign((size_t)t.n * 8, 0); t.cls.assign((size_t)t.n, 0); t.woff.assign((size_t)t.n, 0);
+    for (int i = 0; i < nsegs; ++i) {
+        const int64_t L = (int64_t)M >> sg[i].lgR;
+        if (sg[i].kind && (sg[i].wtab_off >= (woff_in_record ? 16384 : 65536) || sg[i].sig_stride % L)) t.ok = false;
+        for (int s = 0; s < sg[i].nsteps * TILE_G / rpi; ++s) {
+            const size_t it = (size_t)sg[i].first * TILE_G / rpi + s;
+            const TileRow* r = rw + it * rpi;
+            int32_t* q = &t.rec[8 * it];
+            int npad = 0;
+            for (int k = 0; k < rpi; ++k) {
+                if (r[k].row < 0) ++npad;
+                else if (npad) t.ok = false;                      // padding trails
+                // the sub-rows are consecutive rows of the class (the padding repeats the last one)
+                if (r[k].row >= 0 && ((r[k].row & 0xFFFF) != (r[0].row & 0xFFFF) + k
+                                      || (sg[i].kind && r[k].ubase != r[0].ubase + k * L))) t.ok = false;
+                q[4 + k] = r[k].kc;
+            }
+            const int32_t row0 = r[0].row & 0xFFFF;
+            q[0] = row0 | (npad << 9) | (sg[i].kind << 12) | (sg[i].lgR << 13)
+                   | (woff_in_record && sg[i].kind ? (int32_t)((uint32_t)sg[i].wtab_off << 18) : 0);
+            q[1] = sg[i].kind ? sg[i].cls_base + r[0].ubase : 0;
+            q[2] = (int32_t)(uint32_t)((int64_t)row0 * N * 8);
+            q[3] = sg[i].kind ? sg[i].sig_stride : 0;
+            t.cls[it] = sg[i].kind ? 1 + sg[i].lgR : 0;
+            t.woff[it] = sg[i].kind ? sg[i].wtab_off : 0;
+        }
+    }
+    return t;
+}
+
+// tile2_kernel: contiguous, cost-balanced blocks of items per wavefront, each spanning at most TWO classes (kind /
+// decimation): the kernel keeps the weights of (up to) two classes in registers. waves: [nw][4] = first item, end,
+// first item of the second class, the weights' table offsets of the two classes (16 bits each). rb_cost: what an
+// item of rows read back costs next to an interpolated one. Returns whether the kernel can take the items (t.ok, and
+// they cut that way).
+static bool cut_item_blocks(const ItemTable& t, int nw, float rb_cost, std::vector<int32_t>& waves) {
+    const int n_items = t.n;
+    bool ok = t.ok;
+    std::vector<int> run_start;                        // maximal runs of one class
+    for (int it = 0; it < n_items; ++it)
+        if (it == 0 || t.cls[it] != t.cls[it - 1]) run_start.push_back(it);
+    const int nruns = (int)run_start.size();
+    run_start.push_back(n_items);
+    std::vector<double> pre((size_t)n_items + 1, 0.0);
+    for (int it = 0; it < n_items; ++it) pre[it + 1] = pre[it] + (t.cls[it] ? 1.0f : rb_cost);
+    waves.clear();
+    // (round 4 also sized the blocks by the wavefronts' measured speeds -- the older wavefronts of a SIMD finish the
+    // same work 10-19 % sooner -- to no effect: 221 +- 3 us for every weighting; a SIMD's total is what counts)
+    int cur = 0;
+    const double stot = nw;
+    double sacc = 0;
+    for (int w = 0; w < nw; ++w) {
+        sacc += 1.0;
+        if (cur >= n_items) { waves.insert(waves.end(), {n_items, n_items, n_items, 0}); continue; }
+        int r0 = 0;
+        while (run_start[r0 + 1] <= cur) ++r0;
+        const int maxe = run_start[std::min(r0 + 2, nruns)];          // at most the rest of this run and the next
+        const int rem = nw - w - 1;
+        const int rmin = std::max(r0, nruns - 2 * rem);               // the rest must fit the remaining wavefronts
+        int mine = rem == 0 ? n_items : run_start[std::min(rmin, nruns)];
+        mine = std::max(mine, cur + 1);
+        int e = cur;
+        const double want = pre[n_items] * sacc / stot;
+        while (e < n_items && pre[e + 1] <= want + 1e-9) ++e;
+        e = std::min(std::max(e, mine), maxe);
+        if (rem == 0) { e = n_items; if (e > maxe) ok = false; }
+        const int isp = run_start[r0 + 1] < e ? run_start[r0 + 1] : e;
+        waves.insert(waves.end(), {cur, e, isp, t.woff[cur] | (t.woff[std::min(isp, n_items - 1)] << 16)});
+        cur = e;
+    }
+    return ok && cur >= n_items;
+}
+
+// tile3_kernel: per-wavefront LISTS instead of contiguous row blocks. Round 6's stamps showed the wavefronts waiting
+// 22 % of their time at the tile's end for the slowest of them (4-row items: a block is 4 or 5 items). So:
+//   1. the interpolated items, class by class, are cut into `nw` chunks minimising the largest (a chunk of several
+//      classes pays `chg_cost` items per class: the weights are re-read per tile);
+//   2. the items of rows read back (`rb_cost` items each) need no weights: each goes to the wavefront with the least
+//      work;
+//   3. the item table is permuted so that a wavefront's list is contiguous (chunk, then rows read back).
+// dealt: the permuted records; waves: [nw][4] = first item, end, first item of the list's second class (or of its
+// rows read back, or its end), 0. Returns whether the kernel can take the items (t.ok -- else no list is dealt --
+// and every item dealt).
+static bool deal_item_lists(const ItemTable& t, int nw, float rb_cost, float chg_cost, std::vector<int32_t>& dealt,
+                            std::vector<int32_t>& waves) {
+    const int n_items = t.n;
+    const std::vector<int32_t>& icls = t.cls;
+    bool ok = t.ok;
+    std::vector<int> iin, irb;
+    for (int it = 0; it < n_items; ++it) (icls[it] ? iin : irb).push_back(it);
+    const int ni = (int)iin.size();
+    auto chunk_cost = [&](int a, int b) -> double {        // interpolated items [a, b) of `iin`
+        if (b <= a) return 0.0;
+        int ncl = 1;
+        for (int j = a + 1; j < b; ++j) if (icls[iin[j]] != icls[iin[j - 1]]) ++ncl;
+        return (double)(b - a) + (ncl > 1 ? chg_cost * ncl : 0.0);
+    };
+    // (the wavefronts of a SIMD do not run at one speed: the arbiter serves the oldest first, and the stamps show the
+    // youngest taking a third longer per item. speed[w]: what wavefront w gets done relative to the mean, by its
+    // age rank w / 4 -- chunk k goes to wavefront k, and "largest" above means largest time = cost / speed.)
+    // (measured at config 2, one box: skew 0 / 0.1 / 0.2 / 0.3 -> 193-196 / 187 / 184-186 / 191 us with 16 wavefronts;
+    // no gain with 12) -- four age ranks, skew 0.2: 1.2 .. 0.8
+    static_assert(TILE3_NW == 16, "the speeds are those of four wavefronts per SIMD");
+    std::vector<double> speed(nw);
+    for (int w = 0; w < nw; ++w) speed[w] = 1.0 + 0.2f * (1.0 - 2.0 * (w / 4) / 3.0);
+    std::vector<std::vector<double>> f(nw + 1, std::vector<double>(ni + 1, 1e30));
+    std::vector<std::vector<int>> arg(nw + 1, std::vector<int>(ni + 1, 0));
+    f[0][0] = 0.0;
+    for (int k = 1; k <= nw; ++k)
+        for (int j = 0; j <= ni; ++j)
+            for (int a = 0; a <= j; ++a) {
+                if (f[k - 1][a] >= 1e30) continue;
+                const double c = std::max(f[k - 1][a], chunk_cost(a, j) / speed[k - 1]);
+                // (ties: the later cut -- chunks of equal size rather than one long and one empty)
+                if (c < f[k][j] - 1e-12 || (c <= f[k][j] + 1e-12 && a >= arg[k][j])) { f[k][j] = c; arg[k][j] = a; }
+            }
+    if (f[nw][ni] >= 1e30) ok = false;
+    std::vector<std::vector<int>> lists(nw);
+    std::vector<double> load(nw, 0.0);
+    if (ok) {
+        int j = ni;
+        for (int k = nw; k >= 1; --k) {
+            const int a = arg[k][j];
+            for (int q = a; q < j; ++q) lists[k - 1].push_back(iin[q]);
+            load[k - 1] = chunk_cost(a, j);
+            j = a;
+        }
+        for (int it : irb) {
+            int best = 0;
+            for (int w = 1; w < nw; ++w)
+                if ((load[w] + rb_cost) / speed[w] < (load[best] + rb_cost) / speed[best] - 1e-12) best = w;
+            lists[best].push_back(it);
+            load[best] += rb_cost;
+        }
+    }
+    // (list k is wavefront k's: the speeds above are those of the wavefronts' slots)
+    dealt.assign((size_t)n_items * 8, 0);
+    waves.assign((size_t)nw * 4, 0);
+    int pos = 0;
+    for (int sl = 0; sl < nw; ++sl) {
+        const std::vector<int>& L = lists[sl];
+        const int first = pos;
+        int isp = -1;
+        for (size_t q = 0; q < L.size(); ++q) {
+            if (q > 0 && icls[L[q]] && icls[L[q - 1]] && icls[L[q]] != icls[L[q - 1]] && isp < 0) isp = pos;
+            memcpy(&dealt[(size_t)pos * 8], &t.rec[(size_t)L[q] * 8], 32);
+            ++pos;
+        }
+        int e_int = first;
+        for (size_t q = 0; q < L.size(); ++q) if (icls[L[q]]) e_int = first + (int)q + 1;
+        if (isp < 0) isp = e_int;
+        waves[4 * sl] = first; waves[4 * sl + 1] = pos; waves[4 * sl + 2] = isp;
+    }
+    return ok && pos == n_items;
+}
+
 int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_t n1_, int64_t na_, int group_,
                      double dt_, int64_t& bytes) {
     M = M_; N = N_; n1 = n1_; na = na_; group = group_; dt = dt_;
@@ -28,7 +202,7 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
         SSQ_CHECK_HIP(hipGetDeviceProperties(&pr, dev));
         ncu = pr.multiProcessorCount;
         if (const char* e = getenv("SSQ_DEBUG_TILE_GRID")) if (atoi(e) > 0) ncu = atoi(e);
-        // both tile kernels keep a tile of up to 160 KB in a workgroup's LDS (gfx950); a device with
+        // the tile kernels keep a tile of up to 160 KB in a workgroup's LDS (gfx950); a device with
         // less refuses the tile path here instead of failing at the first launch
         SSQ_REQUIRE((size_t)pr.maxSharedMemoryPerMultiProcessor >= 160 * 1024,
                     "the tile path needs 160 KB of LDS per workgroup, the device has %zu",
@@ -82,182 +256,31 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
         }
         if ((rc = up((void**)&rows, hp.data(), hp.size() * 4))) return rc;
     }
-    {   // the default kernels' items: `rpi` consecutive rows of a step, one record of 8 words per item:
-        // row0 | padded sub-rows << 9 | kind << 12 | lgR << 13 (| the weights' table offset << 18: tile3_kernel),
-        // samples of sub-row 0 (class offset + row in class * L), row0 * N * 8, entries between two signals' rows of
-        // the class, centre bins -- and the wavefronts' blocks of items, [nw][4] = first item, end, first item of the
-        // second class, the weights' table offsets of the two classes (16 bits each).
-        // tile2_kernel (ssq_tile_f64.hip): rpi = 64 / columns per tile; tile3_kernel (ssq_tile_pair.hip): 4 rows x 32
-        // columns, two columns per lane.
+    {   // the default kernels' items (see pack_items) and the wavefronts' shares of them
         const TileRow* rw = reinterpret_cast<const TileRow*>(d.rows);
         const TileSeg* sg = reinterpret_cast<const TileSeg*>(d.segs);
         cols2 = tile2_lds_bytes(na, 32) <= 160 * 1024 ? 32 : 16;
         SSQ_REQUIRE(tile2_lds_bytes(na, cols2) <= 160 * 1024, "na = %lld: the Tx tile exceeds the LDS", (long long)na);
         lgr_max2 = 0;
         for (int i = 0; i < nsegs; ++i) if (sg[i].kind) lgr_max2 = std::max(lgr_max2, (int)sg[i].lgR);
-        // (what a row read back costs next to an interpolated one when the rows are dealt to the wavefronts; measured
-        // 0.5 .. 1.2: 221 / 223 / 222 / 228 / 225 us, round 4)
-        // chg_cost < 0: tile2_kernel's contiguous blocks; >= 0: tile3_kernel's dealt lists (see below), a class change
-        // inside a wavefront's list costing that many items (max_cls = 2: both classes' weights resident, no cost)
-        auto build = [&](int rpi, int nw, bool woff_in_record, float rb_cost, float chg_cost, int max_cls,
-                         void** items_dev, int32_t** waves_dev, int& n_items, bool& ok) -> int {
-            SSQ_REQUIRE(TILE_G % rpi == 0, "tile tables: %d rows per step, %d per item", TILE_G, rpi);
-            n_items = nsteps * TILE_G / rpi;
-            std::vector<int32_t> hi8((size_t)n_items * 8, 0);
-            std::vector<float> cost((size_t)n_items, 0.f);
-            std::vector<int32_t> icls((size_t)n_items, 0), woff((size_t)n_items, 0);
-            ok = true;
-            for (int i = 0; i < nsegs; ++i) {
-                const int64_t L = (int64_t)M >> sg[i].lgR;
-                if (sg[i].kind && (sg[i].wtab_off >= (woff_in_record ? 16384 : 65536) || sg[i].sig_stride % L)) ok = false;
-                for (int t = 0; t < sg[i].nsteps * TILE_G / rpi; ++t) {
-                    const size_t it = (size_t)sg[i].first * TILE_G / rpi + t;
-                    const TileRow* r = rw + it * rpi;
-                    int npad = 0;
-                    for (int k = 0; k < rpi; ++k) {
-                        if (r[k].row < 0) ++npad;
-                        else if (npad) ok = false;                        // padding trails
-                        // the sub-rows are consecutive rows of the class (the padding repeats the last one)
-                        if (r[k].row >= 0 && ((r[k].row & 0xFFFF) != (r[0].row & 0xFFFF) + k
-                                              || (sg[i].kind && r[k].ubase != r[0].ubase + k * L))) ok = false;
-                        hi8[8 * it + 4 + k] = r[k].kc;
-                    }
-                    const int32_t row0 = r[0].row & 0xFFFF;
-                    hi8[8 * it] = row0 | (npad << 9) | (sg[i].kind << 12) | (sg[i].lgR << 13)
-                                  | (woff_in_record && sg[i].kind ? (int32_t)((uint32_t)sg[i].wtab_off << 18) : 0);
-                    hi8[8 * it + 1] = sg[i].kind ? sg[i].cls_base + r[0].ubase : 0;
-                    hi8[8 * it + 2] = (int32_t)(uint32_t)((int64_t)row0 * N * 8);
-                    hi8[8 * it + 3] = sg[i].kind ? sg[i].sig_stride : 0;
-                    cost[it] = sg[i].kind ? 1.0f : rb_cost;           // what rows read back cost next to interpolated ones
-                    icls[it] = sg[i].kind ? 1 + sg[i].lgR : 0;
-                    woff[it] = sg[i].kind ? sg[i].wtab_off : 0;
-                }
-            }
-            int rcb;
-            if (chg_cost >= 0.f) {
-                // tile3_kernel: per-wavefront LISTS instead of contiguous row blocks. Round 6's stamps showed the
-                // wavefronts waiting 22 % of their time at the tile's end for the slowest of them (4-row items: a block
-                // is 4 or 5 items, a class change costs 0.65 of one, rows read back 0.45). So:
-                //   1. the interpolated items, class by class, are cut into `nw` chunks minimising the largest
-                //      (a chunk of several classes pays `chg_cost` per class: the weights are re-read per tile);
-                //   2. the items of rows read back need no weights: each goes to the wavefront with the least work;
-                //   3. the item table is permuted so that a wavefront's list is contiguous (chunk, then rows read back).
-                std::vector<int> iin, irb;
-                for (int it = 0; it < n_items; ++it) (icls[it] ? iin : irb).push_back(it);
-                const int ni = (int)iin.size();
-                auto chunk_cost = [&](int a, int b) -> double {        // interpolated items [a, b) of `iin`
-                    if (b <= a) return 0.0;
-                    int ncl = 1;
-                    for (int j = a + 1; j < b; ++j) if (icls[iin[j]] != icls[iin[j - 1]]) ++ncl;
-                    if (ncl > max_cls) return 1e30;
-                    return (double)(b - a) + (ncl > 1 && max_cls > 2 ? chg_cost * ncl : 0.0);
-                };
-                // (the wavefronts of a SIMD do not run at one speed: the arbiter serves the oldest first, and the stamps show the
-                // youngest taking a third longer per item. speed[w]: what wavefront w gets done relative to the mean, by its
-                // age rank w / 4 -- chunk k goes to wavefront k, and "largest" above means largest time = cost / speed.)
-                // (measured at config 2, one box: skew 0 / 0.1 / 0.2 / 0.3 -> 193-196 / 187 / 184-186 / 191 us with 16 wavefronts;
-                // no gain with 12) -- four age ranks, skew 0.2: 1.2 .. 0.8
-                static_assert(TILE3_NW == 16, "the speeds are those of four wavefronts per SIMD");
-                std::vector<double> speed(nw);
-                for (int w = 0; w < nw; ++w) speed[w] = 1.0 + 0.2f * (1.0 - 2.0 * (w / 4) / 3.0);
-                std::vector<std::vector<double>> f(nw + 1, std::vector<double>(ni + 1, 1e30));
-                std::vector<std::vector<int>> arg(nw + 1, std::vector<int>(ni + 1, 0));
-                f[0][0] = 0.0;
-                for (int k = 1; k <= nw; ++k)
-                    for (int j = 0; j <= ni; ++j)
-                        for (int a = 0; a <= j; ++a) {
-                            if (f[k - 1][a] >= 1e30) continue;
-                            const double c = std::max(f[k - 1][a], chunk_cost(a, j) / speed[k - 1]);
-                            // (ties: the later cut -- chunks of equal size rather than one long and one empty)
-                            if (c < f[k][j] - 1e-12 || (c <= f[k][j] + 1e-12 && a >= arg[k][j])) { f[k][j] = c; arg[k][j] = a; }
-                        }
-                if (f[nw][ni] >= 1e30) ok = false;
-                std::vector<std::vector<int>> lists(nw);
-                std::vector<double> load(nw, 0.0);
-                if (ok) {
-                    int j = ni;
-                    for (int k = nw; k >= 1; --k) {
-                        const int a = arg[k][j];
-                        for (int q = a; q < j; ++q) lists[k - 1].push_back(iin[q]);
-                        load[k - 1] = chunk_cost(a, j);
-                        j = a;
-                    }
-                    for (int it : irb) {
-                        int best = 0;
-                        for (int w = 1; w < nw; ++w)
-                            if ((load[w] + rb_cost) / speed[w] < (load[best] + rb_cost) / speed[best] - 1e-12) best = w;
-                        lists[best].push_back(it);
-                        load[best] += rb_cost;
-                    }
-                }
-                // (list k is wavefront k's: the speeds above are those of the wavefronts' slots)
-                std::vector<int32_t> hp((size_t)n_items * 8, 0), wrec((size_t)nw * 4, 0);
-                int pos = 0;
-                for (int sl = 0; sl < nw; ++sl) {
-                    const std::vector<int>& L = lists[sl];
-                    const int first = pos;
-                    int isp = -1;
-                    for (size_t q = 0; q < L.size(); ++q) {
-                        if (q > 0 && icls[L[q]] && icls[L[q - 1]] && icls[L[q]] != icls[L[q - 1]] && isp < 0) isp = pos;
-                        memcpy(&hp[(size_t)pos * 8], &hi8[(size_t)L[q] * 8], 32);
-                        ++pos;
-                    }
-                    // (isp: the first item of the list's second class -- or of its rows read back, or its end)
-                    int e_int = first;
-                    for (size_t q = 0; q < L.size(); ++q) if (icls[L[q]]) e_int = first + (int)q + 1;
-                    if (isp < 0) isp = e_int;
-                    wrec[4 * sl] = first; wrec[4 * sl + 1] = pos; wrec[4 * sl + 2] = isp; wrec[4 * sl + 3] = 0;
-                }
-                if (pos != n_items) ok = false;
-                if ((rcb = up(items_dev, hp.data(), hp.size() * 4))) return rcb;
-                return up((void**)waves_dev, wrec.data(), wrec.size() * 4);
-            }
-            if ((rcb = up(items_dev, hi8.data(), hi8.size() * 4))) return rcb;
-            // Contiguous, cost-balanced blocks of items per wavefront, each spanning at most TWO classes
-            // (kind / decimation): the kernels keep the weights of (up to) two classes in registers.
-            std::vector<int> run_start;                        // maximal runs of one class
-            for (int it = 0; it < n_items; ++it)
-                if (it == 0 || icls[it] != icls[it - 1]) run_start.push_back(it);
-            const int nruns = (int)run_start.size();
-            run_start.push_back(n_items);
-            std::vector<double> pre((size_t)n_items + 1, 0.0);
-            for (int it = 0; it < n_items; ++it) pre[it + 1] = pre[it] + cost[it];
-            std::vector<int32_t> wt_;
-            // (round 4 also sized the blocks by the wavefronts' measured speeds -- the older wavefronts of a SIMD finish the
-            // same work 10-19 % sooner -- to no effect: 221 +- 3 us for every weighting; a SIMD's total is what counts)
-            {
-                int cur = 0;
-                const double stot = nw;
-                double sacc = 0;
-                for (int w = 0; w < nw; ++w) {
-                    sacc += 1.0;
-                    if (cur >= n_items) { wt_.insert(wt_.end(), {n_items, n_items, n_items, 0}); continue; }
-                    int r0 = 0;
-                    while (run_start[r0 + 1] <= cur) ++r0;
-                    const int maxe = run_start[std::min(r0 + 2, nruns)];          // at most the rest of this run and the next
-                    const int rem = nw - w - 1;
-                    const int rmin = std::max(r0, nruns - 2 * rem);               // the rest must fit the remaining wavefronts
-                    int mine = rem == 0 ? n_items : run_start[std::min(rmin, nruns)];
-                    mine = std::max(mine, cur + 1);
-                    int e = cur;
-                    const double want = pre[n_items] * sacc / stot;
-                    while (e < n_items && pre[e + 1] <= want + 1e-9) ++e;
-                    e = std::min(std::max(e, mine), maxe);
-                    if (rem == 0) { e = n_items; if (e > maxe) ok = false; }
-                    const int isp = run_start[r0 + 1] < e ? run_start[r0 + 1] : e;
-                    wt_.insert(wt_.end(), {cur, e, isp, woff[cur] | (woff[std::min(isp, n_items - 1)] << 16)});
-                    cur = e;
-                }
-                if (cur < n_items) ok = false;
-            }
-            return up((void**)waves_dev, wt_.data(), wt_.size() * 4);
-        };
-        if ((rc = build(64 / cols2, TILE2_NW, false, 0.7f, -1.f, 2, &items2, &wave_first2, n_items2, tile2_ok))) return rc;
+        std::vector<int32_t> waves;
+        // tile2_kernel: rpi = 64 / columns per tile. (What a row read back costs next to an interpolated one when the
+        // rows are dealt to the wavefronts; measured 0.5 .. 1.2: 221 / 223 / 222 / 228 / 225 us, round 4)
+        ItemTable t2 = pack_items(sg, nsegs, rw, nsteps, M, N, 64 / cols2, false);
+        tile2_ok = cut_item_blocks(t2, TILE2_NW, 0.7f, waves);
+        n_items2 = t2.n;
+        if ((rc = up(&items2, t2.rec.data(), t2.rec.size() * 4))) return rc;
+        if ((rc = up((void**)&wave_first2, waves.data(), waves.size() * 4))) return rc;
         tile3_ok = false;
         if (cols2 == 32) {
-            // (measured with shader-clock stamps, round 6: an item of rows read back costs 0.45 of an interpolated one,
-            // re-reading a class's weights 0.65)
-            if ((rc = build(4, TILE3_NW, true, 0.45f, 0.65f, 1 << 20, &items3, &wave_first3, n_items3, tile3_ok))) return rc;
+            // tile3_kernel: 4 rows x 32 columns, two columns per lane. (Measured with shader-clock stamps, round 6: an
+            // item of rows read back costs 0.45 of an interpolated one, re-reading a class's weights 0.65)
+            ItemTable t3 = pack_items(sg, nsegs, rw, nsteps, M, N, 4, true);
+            std::vector<int32_t> dealt;
+            tile3_ok = deal_item_lists(t3, TILE3_NW, 0.45f, 0.65f, dealt, waves);
+            n_items3 = t3.n;
+            if ((rc = up(&items3, dealt.data(), dealt.size() * 4))) return rc;
+            if ((rc = up((void**)&wave_first3, waves.data(), waves.size() * 4))) return rc;
             // (the 16 lanes of a sub-row hold the sample window of the tile's 32 columns: (31 >> lgR) + 8 + 1 <= 16 needs
             // a decimation of 4 or more -- R_MIN of _tiles.py; plans with a smaller one go to tile2_kernel)
             for (int i = 0; i < nsegs; ++i) if (sg[i].kind && sg[i].lgR < 2) tile3_ok = false;
@@ -371,33 +394,68 @@ void TilePlan::destroy() {
 }
 
 // SSQ_TILE_ORDER = ordered: the ticketed kernel (float32 sums in the reference's order, bit for bit; na <=
-// 318); default: tile2_kernel (float64 tile, unordered adds: the same bins, sums rounded once)
+// 318); default: tile3_kernel, or tile2_kernel (float64 tile, unordered adds: the same bins, sums rounded once)
 bool tile_ordered() { return reassign_ordered(); }
-// tile3_kernel (two columns per lane): 32-column tiles (up to 318 rows); SSQ_DEBUG_TILE_PAIR=0 keeps tile2_kernel (read at
-// every call)
-bool TilePlan::pair_ok() const {
-    if (!tile3_ok || cols2 != 32 || N < 64) return false;
-    const char* e = getenv("SSQ_DEBUG_TILE_PAIR");
-    return !(e && atoi(e) == 0);
-}
-bool TilePlan::usable() const {
-    if (!tile_ordered() && (tile2_ok || pair_ok())) return true;
-    return tile_lds_bytes(na) <= 160 * 1024;
-}
 int TilePlan::tile_kernel() const {
-    if (!usable()) return 0;
-    if (tile_ordered()) return 1;
-    return pair_ok() ? 3 : (tile2_ok ? 2 : 1);
+    const int ordered = tile_lds_bytes(na) <= 160 * 1024 ? 1 : 0;    // (its 64-column float32 tile fits the LDS)
+    if (tile_ordered()) return ordered;
+    // tile3_kernel (two columns per lane): 32-column tiles (up to 318 rows); SSQ_DEBUG_TILE_PAIR=0 keeps tile2_kernel
+    const char* e = getenv("SSQ_DEBUG_TILE_PAIR");
+    if (tile3_ok && cols2 == 32 && N >= 64 && !(e && atoi(e) == 0)) return 3;
+    return tile2_ok ? 2 : ordered;
 }
-int TilePlan::tile_cols() const { return !usable() ? 0 : (tile_ordered() || !(tile2_ok || pair_ok())) ? TILE_COLS : cols2; }
+int TilePlan::tile_cols() const {
+    switch (tile_kernel()) {
+    case 1: return TILE_COLS;
+    case 2: return cols2;
+    case 3: return 32;
+    default: return 0;
+    }
+}
 
 int TilePlan::run(int sig, int nsig, float* Wx, float* dWx, float* Tx, const unsigned short* kidx,
                   const void* cst, float cst0, const SsqParams& sp, hipStream_t stream, unsigned short* kdump) {
-    SSQ_REQUIRE(usable(), "na = %lld: no tile kernel can run in this mode (the executor asks usable() first)", (long long)na);
-    if (!tile_ordered() && pair_ok()) return run_pair(sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, stream, kdump);
-    if (!tile_ordered() && tile2_ok) return run_f64(sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, stream, kdump);
-    SSQ_REQUIRE(!kdump, "bin dump: the default tile kernel only (unset SSQ_TILE_ORDER)");
-    return run_ordered(sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, stream);
+    switch (tile_kernel()) {
+    case 3: return run_pair(sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, stream, kdump);
+    case 2: return run_f64(sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, stream, kdump);
+    case 1:
+        SSQ_REQUIRE(!kdump, "bin dump: the default tile kernels only (unset SSQ_TILE_ORDER)");
+        return run_ordered(sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, stream);
+    default:
+        set_error("na = %lld: no tile kernel can run in this mode (the executor asks usable() first)", (long long)na);
+        return -1;
+    }
+}
+
+TileWalkArgs TilePlan::walk_args(const void* items, const int32_t* waves, int sig, int nsig, float* Wx, float* dWx,
+                                 float* Tx, const unsigned short* kidx, const void* cst, float cst0,
+                                 const SsqParams& sp, unsigned short* kdump) const {
+    TileWalkArgs A{};
+    A.items = reinterpret_cast<const int*>(items); A.waves = reinterpret_cast<const int4*>(waves);
+    A.wtab = (const float4*)wtab; A.U = (const float2*)U; A.cst = cst;
+    A.Wx = (float2*)Wx; A.dWx = (float2*)dWx; A.Tx = (float2*)Tx; A.kidx = kidx; A.kdump = kdump;
+    A.N = N; A.na = na; A.n1 = (int)n1; A.mmask = (int)(M - 1);
+    A.lgM = 0; while (((int64_t)1 << A.lgM) < M) ++A.lgM;
+    A.sig0 = sig; A.nsig = nsig; A.carry = 0; A.xcd = 0;
+    A.inv_m = 1.0f / (float)M; A.theta_scale = (float)(6.283185307179586 / ((double)M * dt)); A.cst0 = cst0;
+    A.counters = counters; A.gamma = sp.gamma;
+    return A;
+}
+
+int TilePlan::walk_grid(int64_t ntx, int cols, int per_cu, TileWalkArgs& A) const {
+    // Persistent workgroups, workgroup b walks tiles b, b + G, ... of every signal. The kernels keep a lane's
+    // interpolation weights for the whole launch, so the columns of a workgroup's tiles must agree mod R for every
+    // class: G * cols a multiple of the largest R (or a single tile per signal and workgroup).
+    const int64_t cap = (int64_t)ncu * per_cu;
+    const int64_t q = std::max<int64_t>(1, ((int64_t)1 << lgr_max2) / cols);
+    const int64_t G = ntx <= cap ? ntx : std::max<int64_t>(q, cap / q * q);
+    // ... and through the signals' boundaries when a signal's tile count keeps that phase too
+    // (SSQ_DEBUG_TILE2_CARRY=0: every signal's walk starts at the workgroup's own tile)
+    const char* ce = getenv("SSQ_DEBUG_TILE2_CARRY");
+    A.carry = (!(ce && atoi(ce) == 0) && ntx > G && ntx % q == 0) ? 1 : 0;
+    const char* xe = getenv("SSQ_DEBUG_TILE2_XCD");
+    A.xcd = !(xe && atoi(xe) == 0) && G >= 16;
+    return (int)G;
 }
 
 int64_t TilePlan::tiles_done(hipStream_t stream) {

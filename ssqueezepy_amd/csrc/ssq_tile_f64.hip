@@ -48,27 +48,6 @@ namespace ssq {
 #include "ssq_point_math.inl"
 #include "ssq_tile_dev.h"
 
-template <int COLS> struct Tile2Geo {
-    static constexpr int RPI = 64 / COLS;              // rows per wavefront instruction
-    static constexpr int LGC = COLS == 32 ? 5 : 4;
-};
-struct Tile2Args {
-    const int* items;        // [n_items][8]: row0 | npad << 9 | kind << 12 | lgR << 13, samples' offset of sub-row 0
-                             // (class + row), row0 * N * 8, entries between two signals' rows of the class, kc of the sub-rows
-    const int4* waves;       // [NW]: first item, end, first item of the wavefront's second class (= end: none), 0
-    const float4* wtab; const float2* U;
-    const void* cst;
-    float2* Wx; float2* dWx; float2* Tx; const unsigned short* kidx;
-    unsigned short* kdump;   // STORE_K builds: the bin of every point as it is consumed, (signal, row, column); else null
-    int64_t N, na;
-    int n_items, n1, mmask, lgM, sig0, nsig, group;
-    int carry;                                       // the walk b, b + G, ... runs through the signals' boundaries
-    int xcd;                                         // first tiles permuted per XCD (see the kernel)
-    float inv_m, theta_scale, cst0;
-    unsigned long long* counters;
-    double gamma;
-};
-
 // Both tile kernels are bound by the instructions they issue, of every kind (round 4,
 // profiles/r4_ab_history.txt: one instruction per cycle and CU; 210 per 64 points in the ticketed
 // kernel). This one is built to issue few:
@@ -84,9 +63,9 @@ struct Tile2Args {
 // STORE_K (diagnostic builds, ssq_cwt_plan_set_bin_dump): every point's bin index goes to A.kdump as the
 // reassignment consumes it -- what pins the kernel's index work as integers against the oracle's map.
 template <int GRID, bool STORE_D, int NW, int CSTK, int COLS, bool STORE_K = false>
-__global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams sp) {
+__global__ __launch_bounds__(64 * NW) void tile2_kernel(TileWalkArgs A, SsqParams sp) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    constexpr int RPI = Tile2Geo<COLS>::RPI, LGC = Tile2Geo<COLS>::LGC;
+    constexpr int RPI = 64 / COLS, LGC = COLS == 32 ? 5 : 4;   // rows per wavefront instruction, log2 COLS
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & (COLS - 1), h = lane >> LGC, hb4 = (lane & ~(COLS - 1)) * 4;
@@ -101,20 +80,10 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
     const int scratch16 = na * COLS * 16 + c16;
     const int full_rounds = na / (NW * RPI);                   // write-out rounds (NW * RPI rows each) that are complete
 
-    const int ntx = (int)((N + COLS - 1) / COLS);
-    const int G = (int)gridDim.x;
-    // Workgroup b walks tiles b, b + G, ... -- of each signal (then a signal's last round is short for the
-    // workgroups past ntx mod G, launch after launch: 304 against 320 tiles at config 2), or, A.carry, of the
-    // signals laid end to end (the launcher allows it when the lanes' weights survive the boundary).
-    // Workgroup b runs on XCD b mod 8 (each XCD has its own L2). The workgroup's FIRST tile is permuted so that the 32
-    // workgroups of an XCD walk 32 ADJACENT tiles at a time: neighbouring tiles read overlapping windows of the decimated
-    // samples (8 taps of halo; for R >= 64 the very same samples), which then meet in one L2 instead of being fetched
-    // from HBM once per tile. The stride between a workgroup's tiles stays G, so the lanes' weight phase is kept.
-    // (SSQ_DEBUG_TILE2_XCD=0 in the launcher's environment: the identity.)
-    const int bid = (A.xcd && (G & 7) == 0) ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-    const int per_sig = bid < ntx ? (ntx - bid + G - 1) / G : 0;
-    const int ntl = A.carry ? (int)(((int64_t)A.nsig * ntx - bid + G - 1) / G)
-                            : per_sig * A.nsig;                // tiles of this workgroup
+    // the walk over the tiles (ssq_tile_dev.h; SSQ_DEBUG_TILE2_CARRY=0 / SSQ_DEBUG_TILE2_XCD=0 in the launcher's
+    // environment: no carry through the signals' boundaries / no XCD permutation); the tiles start at column 0
+    constexpr int sh = 0;
+    TILE_WALK_TILES(COLS, sh);
     const auto* waves = SSQ_CONST_PTR(int4, A.waves);
     const int i0 = waves[wv].x, i1 = waves[wv].y, isp = waves[wv].z, ni = i1 - i0;
     // The wavefronts of a SIMD compete for its issue slots and the oldest wins: left alone, the four
@@ -186,44 +155,21 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
                 }
             }
         }
-        if (threadIdx.x == 0 && A.counters)
-            __scoped_atomic_fetch_add(A.counters, 1ull, __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE);
+        tile_count(A.counters);
         SSQ_WG_BARRIER();
     };
 
     if (ni <= 0) {                                             // more wavefronts than items: write-outs only
-        int tx = bid, sg = 0;
-        for (int j = 0; j < ntl; ++j) {
-            finish_tile(tx, sg);
-            tx += G;
-            if (tx >= ntx) { tx = A.carry ? tx - ntx : bid; ++sg; }
-        }
+        TILE_WALK_FINISH_ONLY(finish_tile);
         return;
     }
 
     // ---- the wavefront's sequence of (tile, item) positions, software-pipelined over a ring of three
     // data slots (the loop is unrolled three times, the slots are compile-time): while position p is
-    // computed, the data of p + 2 go out. Two cursors walk the same sequence, the loads' two positions
-    // ahead of the arithmetic's; each is an item index and the tile as the kernel uses it: n of the
-    // tile's first column (n1 + first column), the signal, and the byte offset of (signal, row 0, first
-    // column) in Wx -- moved by constants when the cursor's item index wraps (no 64-bit products, and no
-    // position records copied around per item). Past the last tile the loads' cursor stays on it (all
+    // computed, the data of p + 2 go out. Two cursors walk the same sequence (TILE_WALK_CURSORS), the
+    // loads' two positions ahead of the arithmetic's. Past the last tile the loads' cursor stays on it (all
     // loads unconditional, see the note in tile_kernel: what they fetch there is valid and unused).
-    struct Pos { int nabs0, sg; int64_t off8; };
-    const int nabs_step = G * COLS, nabs_first = A.n1 + bid * COLS, nabs_last = A.n1 + (ntx - 1) * COLS;
-    const int64_t off8_step = (int64_t)G * COLS * 8;
-    // (a signal's end: back to the workgroup's first tile, or -- carry -- on by the same stride into the next signal)
-    const int64_t off8_wrap = A.carry ? ((int64_t)na * N + (int64_t)(G - ntx) * COLS) * 8
-                                      : ((int64_t)na * N - (int64_t)(per_sig - 1) * G * COLS) * 8;
-    const int nabs_back = ntx * COLS;
-    auto next_tile = [&](Pos q) {
-        Pos r = q;
-        r.nabs0 += nabs_step;
-        const bool wrap = r.nabs0 > nabs_last;
-        r.off8 += wrap ? off8_wrap : off8_step;
-        if (wrap) { r.nabs0 = A.carry ? r.nabs0 - nabs_back : nabs_first; ++r.sg; }
-        return (wrap && r.sg >= A.nsig) ? q : r;               // (the tile after the last: the last)
-    };
+    TILE_WALK_CURSORS(COLS, A.n1);
     const int total = ntl * ni;                                // positions of this wavefront
     typedef int int8v __attribute__((ext_vector_type(8)));
     const auto* items = SSQ_CONST_PTR(int8v, A.items);
@@ -237,14 +183,10 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
     const char* const U8 = reinterpret_cast<const char*>(A.U);
     const char* const WX8 = reinterpret_cast<const char*>(A.Wx) + (size_t)((int64_t)A.sig0 * na * N) * 8u;
     const char* const KX8 = reinterpret_cast<const char*>(A.kidx);
-    // (ANY0: the wavefront's block holds rows read back; a wavefront of interpolated rows only -- most
-    // are -- runs a loop without the bin load and the kind tests: one vector-memory instruction less per
-    // item, and the CU's vector-memory path takes one wavefront instruction per ~20 cycles)
-    auto load_data = [&](auto any0, const int8v R, const Pos& q) {
-        constexpr bool ANY0 = decltype(any0)::value;
+    auto load_data = [&](const int8v R, const Pos& q) {
         Data d;
         const int w0 = R[0];
-        const int kind = ANY0 ? (w0 >> 12) & 1 : 1;
+        const int kind = (w0 >> 12) & 1;
         const char* base; unsigned voff;
         const char* kbase = reinterpret_cast<const char*>(A.items); unsigned koff = (unsigned)lane * 2u;
         if (kind) {                                            // (wave-uniform; the loads themselves stay outside)
@@ -274,8 +216,7 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
         d.u = *reinterpret_cast<const float2*>(base + (size_t)voff);
         // (the bin: a load either way, from a harmless address for interpolated rows -- a conditional
         // load costs the compiler its count of loads in flight)
-        if constexpr (ANY0) d.kq = (int)*reinterpret_cast<const unsigned short*>(kbase + (size_t)koff);
-        else d.kq = 0;
+        d.kq = (int)*reinterpret_cast<const unsigned short*>(kbase + (size_t)koff);
         return d;
     };
     // the weights of the wavefront's (up to) two classes, for the lane's column phase: once
@@ -294,12 +235,13 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
     load_wt(wta, i0, waves[wv].w & 0xFFFF);
     load_wt(wtb, isp < i1 ? isp : i0, (int)((unsigned)waves[wv].w >> 16));
 
-    using Yes = std::true_type; using No = std::false_type;
-    auto run = [&](auto any0) {
-    constexpr bool ANY0 = decltype(any0)::value;
+    // (the loop below sits in a lambda called once, after the test `has0`, whose answer nothing reads: as they were
+    // when a second, kind-free loop existed beside it. Inlined straight into the kernel, or without the test, the
+    // same code compiles to other instructions -- other registers, or s_bitcmp0 for the kind test.)
+    auto run = [&]() {
     Data D[3];
     Pos tc, tl;                                                // the tile of the arithmetic's cursor, of the loads'
-    tc.nabs0 = nabs_first; tc.sg = 0; tc.off8 = (int64_t)bid * COLS * 8;
+    TILE_WALK_FIRST(tc, COLS, sh);
     tl = tc;
     if (total <= 0) return;
     int it_c = i0, it_l = i0;
@@ -309,13 +251,13 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
     // the records of the position in hand and of the one whose data go out next: asked for (through
     // the scalar cache) at the end of the position before, so that they are there when it starts
     int8v Rc = items[i0];
-    D[0] = load_data(any0, Rc, tl);
+    D[0] = load_data(Rc, tl);
     step_loads();
-    D[1] = load_data(any0, items[it_l], tl);
+    D[1] = load_data(items[it_l], tl);
     step_loads();
     // (the third slot: position 0 again -- a load like the loop's, so that the compiler's count of the loads in
     // flight at the loop's head is the loop's own; a plain copy made the first body wait for one load too many)
-    D[2] = load_data(any0, Rc, tc);
+    D[2] = load_data(Rc, tc);
     int8v Rn = items[it_l];
     // the per-row reassignment weights of the position in hand (scalar loads, asked for with its records)
     w_t csn[RPI];
@@ -333,11 +275,11 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
         constexpr int k0 = decltype(KK)::value, k1 = (k0 + 1) % 3, k2 = (k0 + 2) % 3;
         const Pos pc = tc;
         rotate_priority();
-        D[k2] = load_data(any0, Rn, tl);                       // the data of p + 2
+        D[k2] = load_data(Rn, tl);                       // the data of p + 2
         step_loads();
         const Data dc = D[k0];
         const int w0 = Rc[0];
-        const int npad = (w0 >> 9) & 7, kind = ANY0 ? (w0 >> 12) & 1 : 1;
+        const int npad = (w0 >> 9) & 7, kind = (w0 >> 12) & 1;
         const int nabs = pc.nabs0 + c;                         // (lanes past the last column: results unused)
         // (every lane's point counts, except in a class's last item -- padded sub-rows -- and in the last
         // tile of a signal when N is not a multiple of the tile: a wave-uniform test keeps the rest free)
@@ -358,21 +300,9 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
             const int baddr = (((nabs >> lgR) - qb3) << 2) + hb4;
             ssq_f2 A2, D2;
             {
-                int fr[TILE_W], fi[TILE_W];
-                int ur = __float_as_int(dc.u.x), ui = __float_as_int(dc.u.y);
-                SSQ_BPERMUTE_OFF(fr[0], baddr, ur, 0);  SSQ_BPERMUTE_OFF(fi[0], baddr, ui, 0);
-                SSQ_BPERMUTE_OFF(fr[1], baddr, ur, 4);  SSQ_BPERMUTE_OFF(fi[1], baddr, ui, 4);
-                SSQ_BPERMUTE_OFF(fr[2], baddr, ur, 8);  SSQ_BPERMUTE_OFF(fi[2], baddr, ui, 8);
-                SSQ_BPERMUTE_OFF(fr[3], baddr, ur, 12); SSQ_BPERMUTE_OFF(fi[3], baddr, ui, 12);
-                SSQ_BPERMUTE_OFF(fr[4], baddr, ur, 16); SSQ_BPERMUTE_OFF(fi[4], baddr, ui, 16);
-                SSQ_BPERMUTE_OFF(fr[5], baddr, ur, 20); SSQ_BPERMUTE_OFF(fi[5], baddr, ui, 20);
-                SSQ_BPERMUTE_OFF(fr[6], baddr, ur, 24); SSQ_BPERMUTE_OFF(fi[6], baddr, ui, 24);
-                SSQ_BPERMUTE_OFF(fr[7], baddr, ur, 28); SSQ_BPERMUTE_OFF(fi[7], baddr, ui, 28);
-                SSQ_LDS_WAIT();
-                // (A2 = (a_re, a_im), D2 = (a'_re, a'_im): the pairs the modulation multiplies)
                 ssq_f2 sv[TILE_W];
-#pragma unroll
-                for (int t = 0; t < TILE_W; ++t) { sv[t].x = __int_as_float(fr[t]); sv[t].y = __int_as_float(fi[t]); }
+                gather8(sv, baddr, dc.u.x, dc.u.y);
+                // (A2 = (a_re, a_im), D2 = (a'_re, a'_im): the pairs the modulation multiplies)
                 if (it_c < isp) {   // (wave-uniform: the wavefront's first or second class)
                     SSQ_TAPS8(A2, D2, wta, sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7]);
                 } else {
@@ -402,13 +332,7 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
                 if (livept) *reinterpret_cast<float2*>(dwx8 + (size_t)lane_row8) = Dv;
             }
             // phase transform and bin: as emit_point<LEAN> of the block kernels
-            const float cc = Wv.x, dd = Wv.y, aa = Dv.x, bb = Dv.y;
-            const float m2 = cc * cc + dd * dd, num = bb * cc - aa * dd;
-            const bool above = m2 > m2hi, below = m2 < m2lo;
-            const float w32 = fabsf(num * __builtin_amdgcn_rcpf(m2 * 6.2831855f));
-            bool ok;
-            const int kb = bin_screen_cwt<GRID>(w32, sp, omax, ok);
-            const int kf = (kb ^ fx) + fa;
+            TILE_BIN_SCREEN(GRID, Wv, Dv);
             int kout = (above && livept) ? kf : -1;
             const bool pend = livept && !(below | (above & ok));
             if (pend) kout = exact_bin(Wv, Dv, sp, omax, A.gamma);
@@ -448,87 +372,29 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(Tile2Args A, SsqParams s
         body(K2{}); if (!more) break;
     }
     };
-    // (a block spans at most two classes: its first item and the first of its second class tell)
-    const bool has0 = !((items[i0][0] >> 12) & 1) || (isp < i1 && !((items[isp][0] >> 12) & 1));
-    // (measured: a second loop without the bin load and the kind tests for the wavefronts of interpolated
+    // (does the block hold rows read back? It spans at most two classes: its first item and the first of its second
+    // class tell. Measured: a second loop without the bin load and the kind tests for the wavefronts of interpolated
     // rows only -- one vector-memory instruction and ten scalar ones less per item -- is SLOWER, 230 vs 220 us)
+    const bool has0 = !((items[i0][0] >> 12) & 1) || (isp < i1 && !((items[isp][0] >> 12) & 1));
     (void)has0;
-    run(Yes{});
+    run();
 }
 
 // ---------------------------------------------------------------------------- host side
-// ---- tile2_kernel launch
-template <int GRID, bool STORE_D, int NW, int CSTK, int COLS, bool STORE_K = false>
-static int launch_tile2_c(const TilePlan& P, const Tile2Args& A, const SsqParams& sp, hipStream_t stream) {
-    auto kern = tile2_kernel<GRID, STORE_D, NW, CSTK, COLS, STORE_K>;
-    const size_t lds = tile2_lds_bytes(P.na, COLS);
-    // (set at every launch: the attribute belongs to the function ON THE CURRENT DEVICE, a flag per instantiation
-    // would leave a second device of the process without it)
-    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const int64_t ntx = (P.N + COLS - 1) / COLS;
-    // Persistent workgroups: as many as fit a CU's LDS side by side, workgroup b walks tiles b, b + G,
-    // ... of every signal. The kernel keeps a lane's interpolation weights for the whole launch, so
-    // the columns of a workgroup's tiles must agree mod R for every class: G * COLS a multiple of the
-    // largest R (or a single tile per signal and workgroup).
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(32 / NW)));
-    const int64_t cap = (int64_t)P.ncu * per_cu;
-    const int64_t q = std::max<int64_t>(1, ((int64_t)1 << P.lgr_max2) / COLS);
-    const int64_t G = ntx <= cap ? ntx : std::max<int64_t>(q, cap / q * q);
-    // ... and through the signals' boundaries when a signal's tile count keeps that phase too
-    // (SSQ_DEBUG_TILE2_CARRY=0: every signal's walk starts at the workgroup's own tile)
-    const char* ce = getenv("SSQ_DEBUG_TILE2_CARRY");              // (read per launch: tests switch it)
-    const bool carry_on = !(ce && atoi(ce) == 0);
-    Tile2Args B = A;
-    B.carry = (carry_on && ntx > G && ntx % q == 0) ? 1 : 0;
-    const char* xe = getenv("SSQ_DEBUG_TILE2_XCD");                 // (read per launch)
-    B.xcd = !(xe && atoi(xe) == 0) && G >= 16;
-    hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64 * NW), lds, stream, B, sp);
-    SSQ_LAUNCH_CHECK();
-    return 0;
-}
-template <int GRID, bool STORE_D, int NW, int COLS>
-static int launch_tile2_k(const TilePlan& P, const Tile2Args& A, const SsqParams& sp, hipStream_t stream) {
-    const int cstk = sp.cst_f64 ? 2 : (sp.cst_uniform ? 0 : 1);
-    if (A.kdump) {
-        // the diagnostic builds exist for one weight per transform (the bins do not depend on the weights:
-        // 'log' scales, what the full-size index test runs)
-        SSQ_REQUIRE(cstk == 0, "bin dump: built for uniform reassignment weights ('log' scales)");
-        return launch_tile2_c<GRID, STORE_D, NW, 0, COLS, true>(P, A, sp, stream);
-    }
-    if (cstk == 0) return launch_tile2_c<GRID, STORE_D, NW, 0, COLS>(P, A, sp, stream);
-    if (cstk == 1) return launch_tile2_c<GRID, STORE_D, NW, 1, COLS>(P, A, sp, stream);
-    return launch_tile2_c<GRID, STORE_D, NW, 2, COLS>(P, A, sp, stream);
-}
-template <int GRID, bool STORE_D>
-static int launch_tile2(const TilePlan& P, Tile2Args& A, const SsqParams& sp, hipStream_t stream) {
-    // 16 wavefronts = one workgroup of 1024 work-items per CU (measured, round 4: 12 wavefronts 235 us against 220;
-    // 16-column tiles with 16 wavefronts 245 us, with 8 wavefronts and two workgroups per CU 260-275 us --
-    // profiles/r4_ab_history.txt)
-    A.waves = reinterpret_cast<const int4*>(P.wave_first2);
-    if (P.cols2 == 32) return launch_tile2_k<GRID, STORE_D, TILE2_NW, 32>(P, A, sp, stream);
-    return launch_tile2_k<GRID, STORE_D, TILE2_NW, 16>(P, A, sp, stream);
-}
-
 int TilePlan::run_f64(int sig, int nsig, float* Wx, float* dWx, float* Tx, const unsigned short* kidx,
                       const void* cst, float cst0, const SsqParams& sp, hipStream_t stream, unsigned short* kdump) {
-    SSQ_REQUIRE(tile2_ok, "the tile tables do not split into row blocks of at most two classes");
-    Tile2Args B;
-    B.kdump = kdump;
-    B.items = reinterpret_cast<const int*>(items2); B.waves = nullptr;
-    B.wtab = (const float4*)wtab; B.U = (const float2*)U; B.cst = cst;
-    B.Wx = (float2*)Wx; B.dWx = (float2*)dWx; B.Tx = (float2*)Tx; B.kidx = kidx;
-    B.N = N; B.na = na; B.n_items = n_items2; B.n1 = (int)n1; B.mmask = (int)(M - 1);
-    B.lgM = 0; while (((int64_t)1 << B.lgM) < M) ++B.lgM;
-    B.sig0 = sig; B.nsig = nsig; B.group = group; B.inv_m = 1.0f / (float)M;
-    B.theta_scale = (float)(6.283185307179586 / ((double)M * dt)); B.cst0 = cst0;
-    B.counters = counters; B.gamma = sp.gamma; B.carry = 0;
-#define TILE2_LAUNCH(G)                                                                     \
-    return dWx ? launch_tile2<G, true>(*this, B, sp, stream) : launch_tile2<G, false>(*this, B, sp, stream);
-    if (sp.grid == SSQ_GRID_LOG) { TILE2_LAUNCH(SSQ_GRID_LOG) }
-    if (sp.grid == SSQ_GRID_LOG_PIECEWISE) { TILE2_LAUNCH(SSQ_GRID_LOG_PIECEWISE) }
-    TILE2_LAUNCH(SSQ_GRID_LIN)
-#undef TILE2_LAUNCH
+    TileWalkArgs A = walk_args(items2, wave_first2, sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, kdump);
+    // 16 wavefronts = one workgroup of 1024 work-items per CU (measured, round 4: 12 wavefronts 235 us against 220;
+    // 16-column tiles with 16 wavefronts 245 us, with 8 wavefronts and two workgroups per CU 260-275 us --
+    // profiles/r4_ab_history.txt); as many workgroups per CU as fit its LDS side by side, up to 2
+    const size_t lds = tile2_lds_bytes(na, cols2);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(32 / TILE2_NW)));
+    const int G = walk_grid((N + cols2 - 1) / cols2, cols2, per_cu, A);
+    return tile_dispatch(sp, dWx != nullptr, kdump != nullptr, [&](auto grid, auto d, auto cstk, auto k) {
+        if (cols2 == 32)
+            return tile_launch(tile2_kernel<grid(), d(), TILE2_NW, cstk(), 32, k()>, G, TILE2_NW, lds, A, sp, stream);
+        return tile_launch(tile2_kernel<grid(), d(), TILE2_NW, cstk(), 16, k()>, G, TILE2_NW, lds, A, sp, stream);
+    });
 }
 
 }  // namespace ssq

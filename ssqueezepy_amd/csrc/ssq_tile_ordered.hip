@@ -190,10 +190,10 @@ __global__ __launch_bounds__(64 * NW) void tile_kernel(TileArgs A, SsqParams sp)
     // one extra ticket per tile, during which the finished tile is written out.
     const int ntx = (int)((N + TILE_COLS - 1) / TILE_COLS);
     const int ntot = ntx * A.nsig;
-    // (first tiles permuted per XCD -- workgroup b runs on XCD b mod 8 -- so that the workgroups of one XCD walk adjacent
-    // tiles and their sample windows meet in one L2, as in tile2_kernel: ssq_tile_f64.hip)
+    // (first tiles permuted per XCD so that the workgroups of one XCD walk adjacent tiles and their sample windows meet
+    // in one L2: ssq_tile_dev.h)
     const int G_ = (int)gridDim.x;
-    const int bid = ((G_ & 7) == 0 && G_ >= 16) ? ((int)blockIdx.x & 7) * (G_ >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+    const int bid = TILE_FIRST_IF((G_ & 7) == 0 && G_ >= 16, G_);
     const int ntl = ntot > bid ? (ntot - bid + G_ - 1) / G_ : 0;
     const int nst = A.nsteps;
     const int total = nst * ntl;
@@ -392,15 +392,7 @@ __global__ __launch_bounds__(64 * NW) void tile_kernel(TileArgs A, SsqParams sp)
                     {
                         int fr[TILE_W], fi[TILE_W];
                         const int ur = __float_as_int(xu[b][r].x), ui = __float_as_int(xu[b][r].y);
-                        SSQ_BPERMUTE_OFF(fr[0], baddr, ur, 0);  SSQ_BPERMUTE_OFF(fi[0], baddr, ui, 0);
-                        SSQ_BPERMUTE_OFF(fr[1], baddr, ur, 4);  SSQ_BPERMUTE_OFF(fi[1], baddr, ui, 4);
-                        SSQ_BPERMUTE_OFF(fr[2], baddr, ur, 8);  SSQ_BPERMUTE_OFF(fi[2], baddr, ui, 8);
-                        SSQ_BPERMUTE_OFF(fr[3], baddr, ur, 12); SSQ_BPERMUTE_OFF(fi[3], baddr, ui, 12);
-                        SSQ_BPERMUTE_OFF(fr[4], baddr, ur, 16); SSQ_BPERMUTE_OFF(fi[4], baddr, ui, 16);
-                        SSQ_BPERMUTE_OFF(fr[5], baddr, ur, 20); SSQ_BPERMUTE_OFF(fi[5], baddr, ui, 20);
-                        SSQ_BPERMUTE_OFF(fr[6], baddr, ur, 24); SSQ_BPERMUTE_OFF(fi[6], baddr, ui, 24);
-                        SSQ_BPERMUTE_OFF(fr[7], baddr, ur, 28); SSQ_BPERMUTE_OFF(fi[7], baddr, ui, 28);
-                        SSQ_LDS_WAIT();
+                        TILE_BPERMUTE8(fr, fi, baddr, ur, ui);
 #pragma unroll
                         for (int t = 0; t < TILE_W; ++t) {
                             ssq_f2 sv; sv.x = __int_as_float(fr[t]); sv.y = __int_as_float(fi[t]);
@@ -436,13 +428,7 @@ __global__ __launch_bounds__(64 * NW) void tile_kernel(TileArgs A, SsqParams sp)
                     *reinterpret_cast<float2*>(Wx8 + rowoff + colc8) = Wv;
                     if (STORE_D) *reinterpret_cast<float2*>(dWx8 + rowoff + colc8) = Dv;
                     // phase transform and bin: as emit_point<LEAN> of the block kernels
-                    const float cc = Wv.x, dd = Wv.y, aa = Dv.x, bb = Dv.y;
-                    const float m2 = cc * cc + dd * dd, num = bb * cc - aa * dd;
-                    const bool above = m2 > m2hi, below = m2 < m2lo;
-                    const float w32 = fabsf(num * __builtin_amdgcn_rcpf(m2 * 6.2831855f));
-                    bool ok;
-                    const int kb = bin_screen_cwt<GRID>(w32, sp, omax, ok);
-                    const int kf = (kb ^ fx) + fa;
+                    TILE_BIN_SCREEN(GRID, Wv, Dv);
                     const bool live = colok && !pad;
                     int kout = (above && live) ? kf : -1;
                     // undecided by the float32 screens (~0.05 % of the points, one row in 30): the exact
@@ -484,42 +470,10 @@ __global__ __launch_bounds__(64 * NW) void tile_kernel(TileArgs A, SsqParams sp)
 
 
 // ---------------------------------------------------------------------------- host side
-// wavefronts per workgroup: 12 = 3 per SIMD (168 VGPRs: the step pipeline needs ~160; at 16 wavefronts / 128
-// registers it spills and measured slower)
-template <int GRID, bool STORE_D, int NW, int CSTK>
-static int launch_tile_c(const TilePlan& P, const TileArgs& A, const SsqParams& sp, int nsig, hipStream_t stream) {
-    auto kern = tile_kernel<GRID, STORE_D, NW, CSTK>;
-    const size_t lds = tile_lds_bytes(P.na);
-    // (set at every launch: the attribute belongs to the function ON THE CURRENT DEVICE, a flag per instantiation
-    // would leave a second device of the process without it; the call costs well under a microsecond)
-    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    // persistent workgroups, one per CU (the tile fills the LDS)
-    const int64_t ntot = ((P.N + TILE_COLS - 1) / TILE_COLS) * nsig;
-    const dim3 grid((unsigned)std::min<int64_t>(ntot, P.ncu));
-    TileArgs B = A; B.nsig = nsig;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, stream, B, sp);
-    SSQ_LAUNCH_CHECK();
-    return 0;
-}
-template <int GRID, bool STORE_D, int NW>
-static int launch_tile_nw(const TilePlan& P, const TileArgs& A, const SsqParams& sp, int nsig, hipStream_t stream) {
-    const int cstk = sp.cst_f64 ? 2 : (sp.cst_uniform ? 0 : 1);
-    if (cstk == 0) return launch_tile_c<GRID, STORE_D, NW, 0>(P, A, sp, nsig, stream);
-    if (cstk == 1) return launch_tile_c<GRID, STORE_D, NW, 1>(P, A, sp, nsig, stream);
-    return launch_tile_c<GRID, STORE_D, NW, 2>(P, A, sp, nsig, stream);
-}
-template <int GRID, bool STORE_D>
-static int launch_tile(const TilePlan& P, const TileArgs& A, const SsqParams& sp, int nsig, hipStream_t stream) {
-    return launch_tile_nw<GRID, STORE_D, 12>(P, A, sp, nsig, stream);
-}
-
-
 int TilePlan::run_ordered(int sig, int nsig, float* Wx, float* dWx, float* Tx, const unsigned short* kidx,
                           const void* cst, float cst0, const SsqParams& sp, hipStream_t stream) {
-    SSQ_REQUIRE(tile_lds_bytes(na) <= 160 * 1024, "na = %lld: the ordered tile kernel's Tx tile exceeds the LDS", (long long)na);
     TileArgs A;
-    A.pstep = reinterpret_cast<const int4*>(steps); A.prow = reinterpret_cast<const int2*>(rows);
+    A.pstep = steps; A.prow = rows;
     A.wtab = (const float4*)wtab; A.U = (const float2*)U; A.cst = cst;
     A.Wx = (float2*)Wx; A.dWx = (float2*)dWx; A.Tx = (float2*)Tx; A.kidx = kidx;
     A.N = N; A.na = na; A.nsteps = nsteps; A.n1 = (int)n1; A.mmask = (int)(M - 1);
@@ -527,12 +481,13 @@ int TilePlan::run_ordered(int sig, int nsig, float* Wx, float* dWx, float* Tx, c
     A.theta_scale = (float)(6.283185307179586 / ((double)M * dt)); A.cst0 = cst0;
     A.counters = counters;
     A.gamma = sp.gamma;
-#define TILE_LAUNCH(G)                                                                      \
-    return dWx ? launch_tile<G, true>(*this, A, sp, nsig, stream) : launch_tile<G, false>(*this, A, sp, nsig, stream);
-    if (sp.grid == SSQ_GRID_LOG) { TILE_LAUNCH(SSQ_GRID_LOG) }
-    if (sp.grid == SSQ_GRID_LOG_PIECEWISE) { TILE_LAUNCH(SSQ_GRID_LOG_PIECEWISE) }
-    TILE_LAUNCH(SSQ_GRID_LIN)
-#undef TILE_LAUNCH
+    // persistent workgroups, one per CU (the tile fills the LDS); 12 wavefronts = 3 per SIMD (168 VGPRs: the step
+    // pipeline needs ~160; at 16 wavefronts / 128 registers it spills and measured slower)
+    constexpr int NW = 12;
+    const int64_t G = std::min<int64_t>(((N + TILE_COLS - 1) / TILE_COLS) * nsig, ncu);
+    return tile_dispatch<false>(sp, dWx != nullptr, false, [&](auto grid, auto d, auto cstk, auto) {
+        return tile_launch(ssq::tile_kernel<grid(), d(), NW, cstk()>, G, NW, tile_lds_bytes(na), A, sp, stream);
+    });
 }
 
 }  // namespace ssq

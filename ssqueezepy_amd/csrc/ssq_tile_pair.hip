@@ -50,44 +50,10 @@ typedef unsigned ssq_u32u __attribute__((aligned(2)));                      // t
 // (not a template: deduction would drop the pointer type's 8-byte alignment and let the compiler assume 16)
 __device__ __forceinline__ void t3_store(ssq_f4u* p, const ssq_f4u v) { __builtin_nontemporal_store(v, p); }
 
-struct Tile3Args {
-    const int* items;        // [n_items][8]: row0 | npad << 9 | kind << 12 | lgR << 13 | weights' offset << 18, samples'
-                             // offset of sub-row 0 (class + row), row0 * N * 8, entries between two signals' rows of
-                             // the class (these four: scalar loads), kc of the four sub-rows (read per lane)
-    const int4* waves;       // [NW]: first item, end, first item of the wavefront's second class (= end: none), 0
-    const float4* wtab; const float2* U;
-    const void* cst;
-    float2* Wx; float2* dWx; float2* Tx; const unsigned short* kidx;
-    unsigned short* kdump;   // STORE_K builds: the bin of every point as it is consumed, (signal, row, column); else null
-    int64_t N, na;
-    int n_items, n1, mmask, lgM, sig0, nsig, group;
-    int carry;               // the walk b, b + G, ... runs through the signals' boundaries
-    int xcd;                 // first tiles permuted per XCD
-    float inv_m, theta_scale, cst0;
-    unsigned long long* counters;
-    double gamma;
-};
-
-// the bin of one point from (Wx, dWx) = (W, V): the float32 screen of the block kernels' lean epilogue; `pend`: the
-// screens could not decide (exact double sequence, rare)
-template <int GRID>
-__device__ __forceinline__ int pair_bin(const ssq_f2 W, const ssq_f2 V, bool live, float m2hi, float m2lo,
-                                        const SsqParams& sp, int omax, int fx, int fa, bool& pend) {
-    const float cc = W.x, dd = W.y, aa = V.x, bb = V.y;
-    const float m2 = cc * cc + dd * dd, num = bb * cc - aa * dd;
-    const bool above = m2 > m2hi, below = m2 < m2lo;
-    const float w32 = fabsf(num * __builtin_amdgcn_rcpf(m2 * 6.2831855f));
-    bool ok;
-    const int kb = bin_screen_cwt<GRID>(w32, sp, omax, ok);
-    const int kf = (kb ^ fx) + fa;
-    pend = live && !(below | (above & ok));
-    return (above && live) ? kf : -1;
-}
-
 __device__ __forceinline__ ssq_f4u as_f4u(const float4 v) { ssq_f4u r; r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w; return r; }
 
 template <int GRID, bool STORE_D, int CSTK, bool STORE_K = false>
-__global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqParams sp) {
+__global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(TileWalkArgs A, SsqParams sp) {
     constexpr int NW = TILE3_NW;
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr int COLS = T3_COLS, RPI = T3_RPI, LGC = T3_LGC;
@@ -111,13 +77,9 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqPa
     // A pair must start at an even padded index (then n and n + 1 share their decimation interval): when the left
     // padding n1 is odd the tiles start one column early -- tile t = columns 32 t - sh .. 32 t - sh + 31, column -1 dead
     const int sh = A.n1 & 1, n1e = A.n1 - sh;
-    const int ntx = (int)((N + sh + COLS - 1) / COLS);
-    const int G = (int)gridDim.x;
     // (the walk over the tiles, the XCD permutation of the first tiles and the carry through the signals' boundaries:
-    // as tile2_kernel, see there)
-    const int bid = (A.xcd && (G & 7) == 0) ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
-    const int per_sig = bid < ntx ? (ntx - bid + G - 1) / G : 0;
-    const int ntl = A.carry ? (int)(((int64_t)A.nsig * ntx - bid + G - 1) / G) : per_sig * A.nsig;
+    // ssq_tile_dev.h)
+    TILE_WALK_TILES(COLS, sh);
     const auto* waves = SSQ_CONST_PTR(int4, A.waves);
     const int i0 = waves[wv].x, i1 = waves[wv].y, isp = waves[wv].z, ni = i1 - i0;
     // (no issue priorities: tile2_kernel's two levels swapped with every item measured the same here as none -- 173.0
@@ -180,37 +142,18 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqPa
                 if (ok1 && k < na) Tx[(int64_t)k * N + col + 1] = make_float2(v.z, v.w);
             }
         }
-        if (threadIdx.x == 0 && A.counters)
-            __scoped_atomic_fetch_add(A.counters, 1ull, __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE);
+        tile_count(A.counters);
         SSQ_WG_BARRIER();
     };
 
     if (ni <= 0) {                                             // more wavefronts than items: write-outs only
-        int tx = bid, sg = 0;
-        for (int j = 0; j < ntl; ++j) {
-            finish_tile(tx, sg);
-            tx += G;
-            if (tx >= ntx) { tx = A.carry ? tx - ntx : bid; ++sg; }
-        }
+        TILE_WALK_FINISH_ONLY(finish_tile);
         return;
     }
 
     // ---- the wavefront's sequence of (tile, item) positions: two cursors (the loads' two positions ahead of the
-    // arithmetic's), each an item index and the tile as the kernel uses it -- see tile2_kernel
-    struct Pos { int nabs0, sg; int64_t off8; };
-    const int nabs_step = G * COLS, nabs_first = n1e + bid * COLS, nabs_last = n1e + (ntx - 1) * COLS;
-    const int64_t off8_step = (int64_t)G * COLS * 8;
-    const int64_t off8_wrap = A.carry ? ((int64_t)na * N + (int64_t)(G - ntx) * COLS) * 8
-                                      : ((int64_t)na * N - (int64_t)(per_sig - 1) * G * COLS) * 8;
-    const int nabs_back = ntx * COLS;
-    auto next_tile = [&](Pos q) {
-        Pos r = q;
-        r.nabs0 += nabs_step;
-        const bool wrap = r.nabs0 > nabs_last;
-        r.off8 += wrap ? off8_wrap : off8_step;
-        if (wrap) { r.nabs0 = A.carry ? r.nabs0 - nabs_back : nabs_first; ++r.sg; }
-        return (wrap && r.sg >= A.nsig) ? q : r;               // (the tile after the last: the last)
-    };
+    // arithmetic's), see TILE_WALK_CURSORS
+    TILE_WALK_CURSORS(COLS, n1e);
     // a tile with dead columns: a signal's first when the tiles start a column early, its last when it is partial
     auto edge_tile = [&](int nabs0) { return (sh != 0 && nabs0 == n1e) || nabs0 - n1e - sh + COLS > (int)N; };
     const int total = ntl * ni;                                // positions of this wavefront
@@ -293,7 +236,7 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqPa
 
     Data D[3];
     Pos tc, tl;                                                // the tile of the arithmetic's cursor, of the loads'
-    tc.nabs0 = nabs_first; tc.sg = 0; tc.off8 = ((int64_t)bid * COLS - sh) * 8;
+    TILE_WALK_FIRST(tc, COLS, sh);
     tl = tc;
     if (total <= 0) return;
     int it_c = i0, it_l = i0;
@@ -371,21 +314,9 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqPa
             const int baddr = (((nabs >> lgR) - qb3) << 2) + hb4;
             ssq_f2 A0, D0, A1, D1;
             {
-                int fr[TILE_W], fi[TILE_W];
-                int ur = __float_as_int(dc.u.x), ui = __float_as_int(dc.u.y);
-                SSQ_BPERMUTE_OFF(fr[0], baddr, ur, 0);  SSQ_BPERMUTE_OFF(fi[0], baddr, ui, 0);
-                SSQ_BPERMUTE_OFF(fr[1], baddr, ur, 4);  SSQ_BPERMUTE_OFF(fi[1], baddr, ui, 4);
-                SSQ_BPERMUTE_OFF(fr[2], baddr, ur, 8);  SSQ_BPERMUTE_OFF(fi[2], baddr, ui, 8);
-                SSQ_BPERMUTE_OFF(fr[3], baddr, ur, 12); SSQ_BPERMUTE_OFF(fi[3], baddr, ui, 12);
-                SSQ_BPERMUTE_OFF(fr[4], baddr, ur, 16); SSQ_BPERMUTE_OFF(fi[4], baddr, ui, 16);
-                SSQ_BPERMUTE_OFF(fr[5], baddr, ur, 20); SSQ_BPERMUTE_OFF(fi[5], baddr, ui, 20);
-                SSQ_BPERMUTE_OFF(fr[6], baddr, ur, 24); SSQ_BPERMUTE_OFF(fi[6], baddr, ui, 24);
-                SSQ_BPERMUTE_OFF(fr[7], baddr, ur, 28); SSQ_BPERMUTE_OFF(fi[7], baddr, ui, 28);
-                SSQ_LDS_WAIT();
-                // (A = (a_re, a_im), D = (a'_re, a'_im) of the pair's two columns: what the modulation multiplies)
                 ssq_f2 sv[TILE_W];
-#pragma unroll
-                for (int t = 0; t < TILE_W; ++t) { sv[t].x = __int_as_float(fr[t]); sv[t].y = __int_as_float(fi[t]); }
+                gather8(sv, baddr, dc.u.x, dc.u.y);
+                // (A = (a_re, a_im), D = (a'_re, a'_im) of the pair's two columns: what the modulation multiplies)
                 SSQ_TAPS8X2(A0, D0, A1, D1, wa0, wb0, sv[0], sv[1], sv[2], sv[3], sv[4], sv[5], sv[6], sv[7]);
             }
             const int kcs = dc.kq;                             // centre bin of the lane's row
@@ -421,8 +352,8 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqPa
             if (STORE_D) store_pair(reinterpret_cast<char*>(A.dWx), V0, V1);
             // phase transform and bin: as emit_point<LEAN> of the block kernels, per column
             bool pend0, pend1;
-            int ko0 = pair_bin<GRID>(W0, V0, live0, m2hi, m2lo, sp, omax, fx, fa, pend0);
-            int ko1 = pair_bin<GRID>(W1, V1, live1, m2hi, m2lo, sp, omax, fx, fa, pend1);
+            int ko0 = screened_bin<GRID>(W0, V0, live0, m2hi, m2lo, sp, omax, fx, fa, pend0);
+            int ko1 = screened_bin<GRID>(W1, V1, live1, m2hi, m2lo, sp, omax, fx, fa, pend1);
             if (pend0) ko0 = exact_bin(make_float2(W0.x, W0.y), make_float2(V0.x, V0.y), sp, omax, A.gamma);
             if (pend1) ko1 = exact_bin(make_float2(W1.x, W1.y), make_float2(V1.x, V1.y), sp, omax, A.gamma);
             cell0 = ko0 >= 0 ? ko0 * 512 + c8 : scratch8;
@@ -479,58 +410,15 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(Tile3Args A, SsqPa
 }
 
 // ---------------------------------------------------------------------------- host side
-template <int GRID, bool STORE_D, int CSTK, bool STORE_K = false>
-static int launch_tile3_c(const TilePlan& P, const Tile3Args& A, const SsqParams& sp, hipStream_t stream) {
-    auto kern = tile3_kernel<GRID, STORE_D, CSTK, STORE_K>;
-    const size_t lds = tile2_lds_bytes(P.na, T3_COLS);
-    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const int64_t ntx = (P.N + (P.n1 & 1) + T3_COLS - 1) / T3_COLS;     // (the tiles start a column early when n1 is odd)
-    // persistent workgroups, one per CU; G * COLS a multiple of the largest R (the lanes keep their weights' phase)
-    const int64_t cap = (int64_t)P.ncu;
-    const int64_t q = std::max<int64_t>(1, ((int64_t)1 << P.lgr_max2) / T3_COLS);
-    const int64_t G = ntx <= cap ? ntx : std::max<int64_t>(q, cap / q * q);
-    const char* ce = getenv("SSQ_DEBUG_TILE2_CARRY");              // (read per launch: tests switch it)
-    const bool carry_on = !(ce && atoi(ce) == 0);
-    Tile3Args B = A;
-    B.carry = (carry_on && ntx > G && ntx % q == 0) ? 1 : 0;
-    const char* xe = getenv("SSQ_DEBUG_TILE2_XCD");                 // (read per launch)
-    B.xcd = !(xe && atoi(xe) == 0) && G >= 16;
-    hipLaunchKernelGGL(kern, dim3((unsigned)G), dim3(64 * TILE3_NW), lds, stream, B, sp);
-    SSQ_LAUNCH_CHECK();
-    return 0;
-}
-template <int GRID, bool STORE_D>
-static int launch_tile3_k(const TilePlan& P, const Tile3Args& A, const SsqParams& sp, hipStream_t stream) {
-    const int cstk = sp.cst_f64 ? 2 : (sp.cst_uniform ? 0 : 1);
-    if (A.kdump) {
-        SSQ_REQUIRE(cstk == 0, "bin dump: built for uniform reassignment weights ('log' scales)");
-        return launch_tile3_c<GRID, STORE_D, 0, true>(P, A, sp, stream);
-    }
-    if (cstk == 0) return launch_tile3_c<GRID, STORE_D, 0>(P, A, sp, stream);
-    if (cstk == 1) return launch_tile3_c<GRID, STORE_D, 1>(P, A, sp, stream);
-    return launch_tile3_c<GRID, STORE_D, 2>(P, A, sp, stream);
-}
-
 int TilePlan::run_pair(int sig, int nsig, float* Wx, float* dWx, float* Tx, const unsigned short* kidx,
                        const void* cst, float cst0, const SsqParams& sp, hipStream_t stream, unsigned short* kdump) {
-    SSQ_REQUIRE(pair_ok(), "the pair kernel does not take this plan (more than 318 rows, or fewer than 64 columns)");
-    Tile3Args B;
-    B.kdump = kdump;
-    B.items = reinterpret_cast<const int*>(items3);
-    B.waves = reinterpret_cast<const int4*>(wave_first3);
-    B.wtab = (const float4*)wtab; B.U = (const float2*)U; B.cst = cst;
-    B.Wx = (float2*)Wx; B.dWx = (float2*)dWx; B.Tx = (float2*)Tx; B.kidx = kidx;
-    B.N = N; B.na = na; B.n_items = n_items3; B.n1 = (int)n1; B.mmask = (int)(M - 1);
-    B.lgM = 0; while (((int64_t)1 << B.lgM) < M) ++B.lgM;
-    B.sig0 = sig; B.nsig = nsig; B.group = group; B.inv_m = 1.0f / (float)M;
-    B.theta_scale = (float)(6.283185307179586 / ((double)M * dt)); B.cst0 = cst0;
-    B.counters = counters; B.gamma = sp.gamma; B.carry = 0; B.xcd = 0;
-#define TILE3_LAUNCH(G) return dWx ? launch_tile3_k<G, true>(*this, B, sp, stream) : launch_tile3_k<G, false>(*this, B, sp, stream);
-    if (sp.grid == SSQ_GRID_LOG) { TILE3_LAUNCH(SSQ_GRID_LOG) }
-    if (sp.grid == SSQ_GRID_LOG_PIECEWISE) { TILE3_LAUNCH(SSQ_GRID_LOG_PIECEWISE) }
-    TILE3_LAUNCH(SSQ_GRID_LIN)
-#undef TILE3_LAUNCH
+    TileWalkArgs A = walk_args(items3, wave_first3, sig, nsig, Wx, dWx, Tx, kidx, cst, cst0, sp, kdump);
+    // persistent workgroups, one per CU (the tiles start a column early when n1 is odd)
+    const int G = walk_grid((N + (n1 & 1) + T3_COLS - 1) / T3_COLS, T3_COLS, 1, A);
+    const size_t lds = tile2_lds_bytes(na, T3_COLS);
+    return tile_dispatch(sp, dWx != nullptr, kdump != nullptr, [&](auto grid, auto d, auto cstk, auto k) {
+        return tile_launch(tile3_kernel<grid(), d(), cstk(), k()>, G, TILE3_NW, lds, A, sp, stream);
+    });
 }
 
 }  // namespace ssq
