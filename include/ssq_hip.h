@@ -45,7 +45,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 105 (104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 106 (105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -102,6 +102,16 @@ int ssq_ssqueeze(int dtype, const void* Wx, const void* dWx, const void* Sfs,
                  void* Tx, const void* cst, int cst_f64, int64_t batch,
                  int64_t na, int64_t n, double gamma, int grid,
                  const double* params, int flipud, int32_t* kmap, void* stream);
+
+/* Adjoint of ssq_ssqueeze with the bins held fixed (they are integers, piecewise constant in the data):
+ * gWx[a,b] (+)= |Wx[a,b]| > gamma ? cst[a] * gTx[k(a,b), b] : 0,  k as ssq_ssqueeze computes it
+ * (same grid/params/flipud, `Sfs` NULL = CWT form of w, non-NULL = STFT form). `accumulate` != 0
+ * adds to gWx (the direct gradient w.r.t. Wx is already there), 0 overwrites. With `cst_f64` the
+ * product is formed in double and rounded once. */
+int ssq_ssqueeze_adjoint(int dtype, const void* Wx, const void* dWx, const void* Sfs,
+                         const void* gTx, void* gWx, int accumulate, const void* cst, int cst_f64,
+                         int64_t batch, int64_t na, int64_t n, double gamma, int grid,
+                         const double* params, int flipud, void* stream);
 
 /* Same accumulate, bins taken from a precomputed phase transform `w` (inf = skip).
  * replaces indexed_sum_onfly -> _indexed_sum_{log,log_piecewise,lin}[_par] and the
@@ -412,6 +422,16 @@ const char* ssq_stft_plan_algo(const ssq_stft_plan* plan);
 /* x: (batch, n). Sx, dSx, Tx: (batch, rows, n_hops) complex; w: real. */
 int  ssq_stft_execute(ssq_stft_plan* plan, const void* x, int64_t batch, void* Sx,
                       void* dSx, void* Tx, void* w, void* stream);
+/* Adjoint of the plan's STFT (the gradient of a real loss w.r.t. the real input, torch's convention gx = Re(A^H g)):
+ * gx (batch, n) real  <-  gSx, gdSx (batch, rows, n_hops) complex; either may be NULL (not both).
+ * gx = pad^T ( sum_t  win[m - t*hop]  * Re F^-1(gSx[:, t])[m - t*hop]
+ *            +        dwin[m - t*hop] * Re F^-1(gdSx[:, t])[m - t*hop] )
+ * F^-1(g)[n] = sum_{k=0}^{n_fft/2} g[k] e^{+2 pi i k n / n_fft}: one-sided, no 1/n_fft, no doubling (the imaginary
+ * parts of DC and Nyquist do not contribute). Window, diff-window, padtype, modulation, hop and n are the plan's; gx is
+ * overwritten; two calls on the same input give the same bits. "fused" plans (ssq_stft_plan_algo) run one LDS-transform
+ * kernel and a short unpadding pass, the others rocFFT's inverse real transform, an overlap-add and the same pass. */
+int  ssq_stft_adjoint(ssq_stft_plan* plan, const void* gSx, const void* gdSx, void* gx,
+                      int64_t batch, void* stream);
 
 #ifdef __cplusplus
 }

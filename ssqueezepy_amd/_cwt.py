@@ -75,6 +75,7 @@ class CwtPlan():
         self._bank = (vals, off, lo, row_scale)     # host copy: dense rows for `backward`
         self._psih_dev = None
         self._pad_src = None
+        self._pad_seg = None
         self._ssq_key = None
         self.block_rows = 0
         self.extended_rows = 0           # Nyquist-cut rows run as block rows (analytic signal)
@@ -336,6 +337,18 @@ class CwtPlan():
             self._pad_src = torch.from_numpy(np.ascontiguousarray(src, dtype=np.int64)).to(device)
         return self._pad_src
 
+    def pad_segments(self, device):
+        """The padded positions ordered by the input sample they copy (ascending within a
+        sample), and how many positions each sample has: the transpose of the signal extension
+        as one segmented sum, whose order of additions is fixed."""
+        if self._pad_seg is None or self._pad_seg[0].device != device:
+            src = self.pad_sources(device).cpu().numpy()
+            keep = np.nonzero(src >= 0)[0]
+            order = keep[np.argsort(src[keep], kind='stable')]
+            counts = np.bincount(src[keep], minlength=self.N)
+            self._pad_seg = (torch.from_numpy(order).to(device), torch.from_numpy(counts).to(device))
+        return self._pad_seg
+
     def adjoint(self, gW, rpadded=False):
         """Gradient w.r.t. the real input of a real loss whose gradient w.r.t. `Wx` is `gW`
         ((na, N) / (B, na, N), or padded width if `rpadded`): with A = unpad . ifft . diag(psih)
@@ -347,11 +360,10 @@ class CwtPlan():
         g3 = gW if batched else gW[None]
         dev = g3.device
         psih = self.dense_bank(dev)
-        src = self.pad_sources(dev)
+        order, counts = self.pad_segments(dev)
         code = F32 if self.dtype == 'float32' else F64
         out = torch.zeros((g3.shape[0], self.N), dtype=rdt, device=dev)
         v = torch.empty(self.M, dtype=rdt, device=dev)
-        keep = src >= 0
         for b in range(g3.shape[0]):
             if rpadded:
                 Gp = g3[b].to(cdt).contiguous().clone()
@@ -360,7 +372,9 @@ class CwtPlan():
                 Gp[:, self.n1:self.n1 + self.N] = g3[b]
             check(self.lib.ssq_icwt2(code, Gp.data_ptr(), psih.data_ptr(), v.data_ptr(),
                                      self.na, self.M, algos.stream()))
-            out[b].index_add_(0, src[keep], v[keep])
+            # (a segmented sum, not `index_add_`: that one adds with atomics, in arrival order, and a
+            # sample with three padded copies then differs in its last bit from call to call)
+            out[b] = torch.segment_reduce(v[order], 'sum', lengths=counts)
         return out if batched else out[0]
 
 

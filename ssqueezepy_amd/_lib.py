@@ -77,6 +77,9 @@ _PROTOS = {
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
+    'ssq_ssqueeze_adjoint': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_int, c_int64, c_int64, c_int64, c_double, c_int,
+                                     POINTER(c_double), c_int, c_void_p]),
     'ssq_indexed_sum': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int, c_int64, c_int64, c_int64, c_int,
                                 POINTER(c_double), c_int, c_void_p]),
@@ -134,13 +137,14 @@ _PROTOS = {
     'ssq_stft_plan_algo': (c_char_p, [c_void_p]),
     'ssq_stft_execute': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    'ssq_stft_adjoint': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 105     # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 106     # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -19,6 +19,7 @@ from .scales import process_scales, infer_scaletype, _process_fs_and_t
 from .ssqueezing import (_check_ssqueezing_args, _compute_associated_frequencies, GRID_LIN,
                          ssq_grid_params, ssq_const)
 from .wavelets import Wavelet
+from ._stft import wants_grad as _wants_grad
 
 __all__ = ['ssq_cwt', 'phase_cwt']
 
@@ -78,6 +79,33 @@ def _ssq_design(wavelet, scales, nv, N, dt, ssq_freqs, maprange, was_padded):
     return out
 
 
+class _SsqCwtFunction(torch.autograd.Function):
+    """`Tx, Wx, dWx = plan(x)` (`squeezing='sum'`, `order=0`) with a backward through `Tx` and `Wx`:
+    the gradient of `Tx` reaches `Wx` as a gather through the reassignment's bins, held fixed
+    (`algos.ssqueeze_adjoint`, from the saved `Wx`, `dWx`), and `CwtPlan.adjoint` takes the sum
+    back to `x`. `ssq`: the reassignment's arguments as they were at the forward call."""
+
+    @staticmethod
+    def forward(ctx, x, plan, ssq):
+        out = plan.execute(x.detach(), want_dWx=True, want_Tx=True)
+        ctx.plan, ctx.ssq = plan, ssq
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(out['Wx'], out['dWx'])
+        ctx.mark_non_differentiable(out['dWx'])
+        return out['Tx'], out['Wx'], out['dWx']
+
+    @staticmethod
+    def backward(ctx, gTx, gWx, _gdWx=None):
+        if gTx is None and gWx is None:
+            return None, None, None
+        Wx, dWx = ctx.saved_tensors
+        gW = None if gWx is None else gWx.to(Wx.dtype).resolve_conj().contiguous()
+        if gTx is not None:
+            gW = gW.clone() if gW is not None and gW is gWx else gW
+            gW = algos.ssqueeze_adjoint(Wx, dWx, gTx, out=gW, accumulate=gW is not None, **ctx.ssq)
+        return ctx.plan.adjoint(gW), None, None
+
+
 def ssq_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None,
             ssq_freqs=None, padtype='reflect', squeezing='sum', maprange='peak',
             difftype='trig', difforder=None, gamma=None, vectorized=True,
@@ -100,6 +128,13 @@ def ssq_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None,
     `Tx`, `Wx`, `w`, `dWx` are torch GPU tensors (`astensor=True`) or NumPy arrays.
     Supported on the device path: `difftype='trig'` (other values raise, as in the
     reference's GPU mode); every `squeezing` mode; `order` > 0 / tuple (higher-order GMWs).
+
+    Differentiable for `squeezing='sum'`, `order=0`, without `get_w`: when `x` is a tensor that
+    requires grad (and grad mode is on), `Tx` and `Wx` carry a `grad_fn`; `dWx`, `w`, `ssq_freqs`,
+    `scales` do not. The gradient of `Tx` holds the reassignment's bins fixed -- they are
+    integers, piecewise constant in `x`, so it is the exact gradient wherever one exists. The
+    backward keeps `Wx` and `dWx` (one extra complex array) until it has run. Other options
+    return `Tx` without a gradient, silently.
     """
     if x.ndim == 2 and get_w:
         raise NotImplementedError("`get_w=True` unsupported with batched input.")
@@ -167,6 +202,11 @@ def ssq_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None,
         else:
             Tx = algos.ssqueeze_fast(Wq, dWx_h, ssq_freqs, const, logscale, flipud, gamma)
         dWx = dWx_h if get_dWx else None
+    elif squeezing == 'sum' and not get_w and _wants_grad(x):
+        ssq = dict(ssq_freqs=ssq_freqs, const=const, logscale=grid != GRID_LIN, flipud=flipud,
+                   gamma=gamma)
+        Tx, Wx, dWx = _SsqCwtFunction.apply(xd, plan, ssq)
+        w, dWx = None, (dWx if get_dWx else None)
     elif squeezing == 'sum':
         out = plan.execute(xd, want_dWx=get_dWx, want_Tx=True, want_w=get_w)
         Tx, Wx, w, dWx = out['Tx'], out['Wx'], out.get('w'), out.get('dWx')

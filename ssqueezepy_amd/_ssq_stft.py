@@ -11,7 +11,7 @@ import torch
 
 from . import algos
 from .configs import EPS32, EPS64
-from ._stft import _stft_setup
+from ._stft import _stft_setup, wants_grad
 from .scales import infer_scaletype
 from .ssqueezing import _check_ssqueezing_args, ssq_grid_params
 
@@ -34,6 +34,34 @@ def _make_Sfs(n_rows, fs, dtype):
     return Sfs.copy()
 
 
+class _SsqStftFunction(torch.autograd.Function):
+    """`Tx, Sx, dSx = plan(x)` (`squeezing='sum'`) with a backward through `Tx` and `Sx`. The bins
+    are integers, piecewise constant in `x`: they are held fixed, and the gradient of `Tx` reaches
+    `Sx` as a gather through them (`algos.ssqueeze_adjoint`), recomputed from the saved `Sx`, `dSx`;
+    `StftPlan.adjoint` takes the sum back to `x`. `ssq` holds the reassignment's arguments as they
+    were at the forward call (the cached plan may have been given others since)."""
+
+    @staticmethod
+    def forward(ctx, x, plan, ssq):
+        out = plan.execute(x.detach(), want_dSx=True, want_Tx=True)
+        ctx.plan, ctx.ssq = plan, ssq
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(out['Sx'], out['dSx'])
+        ctx.mark_non_differentiable(out['dSx'])
+        return out['Tx'], out['Sx'], out['dSx']
+
+    @staticmethod
+    def backward(ctx, gTx, gSx, _gdSx=None):
+        if gTx is None and gSx is None:
+            return None, None, None
+        Sx, dSx = ctx.saved_tensors
+        gS = None if gSx is None else gSx.to(Sx.dtype).resolve_conj().contiguous()
+        if gTx is not None:
+            gS = gS.clone() if gS is not None and gS is gSx else gS
+            gS = algos.ssqueeze_adjoint(Sx, dSx, gTx, out=gS, accumulate=gS is not None, **ctx.ssq)
+        return ctx.plan.adjoint(gS), None, None
+
+
 def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None,
              modulated=True, ssq_freqs=None, padtype='reflect', squeezing='sum',
              gamma=None, preserve_transform=None, dtype=None, astensor=True,
@@ -41,7 +69,14 @@ def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=Non
     """Synchrosqueezed STFT (Thakur & Wu 2011). Arguments follow
     ``ssqueezepy.ssq_stft`` (ssqueezepy/_ssq_stft.py:17-76). Returns
     ``(Tx, Sx, ssq_freqs, Sfs[, w][, dSx])`` with `Tx`, `Sx` of shape
-    ``(n_fft//2 + 1, n_hops)``; `ssq_freqs`, `Sfs` are NumPy vectors."""
+    ``(n_fft//2 + 1, n_hops)``; `ssq_freqs`, `Sfs` are NumPy vectors.
+
+    Differentiable for `squeezing='sum'` without `get_w`: when `x` is a tensor that requires
+    grad (and grad mode is on), `Tx` and `Sx` carry a `grad_fn`; `dSx`, `w`, `ssq_freqs`, `Sfs`
+    do not. The gradient of `Tx` holds the reassignment's bins fixed -- they are integers,
+    piecewise constant in `x`, so it is the exact gradient wherever one exists. The backward
+    keeps `Sx` and `dSx` (one extra complex array) until it has run. Other options return
+    tensors without a gradient, silently."""
     if x.ndim == 2 and get_w:
         raise NotImplementedError("`get_w=True` unsupported with batched input.")
     _check_ssqueezing_args(squeezing)
@@ -61,7 +96,12 @@ def ssq_stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=Non
     const = (ssq_freqs[1] - ssq_freqs[0])
     grid, params = ssq_grid_params(ssq_freqs, False)
     plan.set_ssq(Sfs, grid, params, const, flipud, gamma)
-    if squeezing == 'sum':
+    if squeezing == 'sum' and not get_w and wants_grad(x):
+        ssq = dict(ssq_freqs=ssq_freqs, const=const, logscale=False, flipud=flipud,
+                   gamma=gamma, Sfs=Sfs)
+        Tx, Sx, dSx = _SsqStftFunction.apply(xd, plan, ssq)
+        w, dSx = None, (dSx if get_dWx else None)
+    elif squeezing == 'sum':
         out = plan.execute(xd, want_dSx=get_dWx, want_Tx=True, want_w=get_w)
         Tx, Sx, w, dSx = out['Tx'], out['Sx'], out.get('w'), out.get('dSx')
     else:                       # see ssq_cwt: the reassignment runs as its own launch

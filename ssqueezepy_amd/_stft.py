@@ -223,6 +223,56 @@ class StftPlan():
                                         p('Tx'), p('w'), algos.stream()))
         return out
 
+    def adjoint(self, gSx=None, gdSx=None):
+        """Gradient w.r.t. the real input of a real loss whose gradients w.r.t. `Sx`, `dSx` are
+        `gSx`, `gdSx` (``(rows, n_hops)`` / ``(B, rows, n_hops)``; either may be None): ``Re(A^H g)``,
+        the plan's `ssq_stft_adjoint` -- per frame the one-sided inverse transform, the window
+        product, the overlap-add, then the transpose of the signal extension. Deterministic."""
+        g0 = gSx if gSx is not None else gdSx
+        if g0 is None:
+            raise ValueError("`gSx` and `gdSx` are both None")
+        batched = g0.ndim == 3
+        B = g0.shape[0] if batched else 1
+        if B > self.max_batch:
+            raise ValueError("batch %d exceeds the plan's max_batch %d" % (B, self.max_batch))
+        cdt, rdt = _CDT[self.dtype], _TDT[self.dtype]
+        shape = (B, self.rows, self.n_hops) if batched else (self.rows, self.n_hops)
+        gs = []
+        for g in (gSx, gdSx):
+            if g is not None:
+                if tuple(g.shape) != shape:
+                    raise ValueError("gradient of shape %s, transform of shape %s"
+                                     % (tuple(g.shape), shape))
+                g = g.to(cdt).resolve_conj().contiguous()
+            gs.append(g)
+        gx = torch.empty((B, self.N) if batched else (self.N,), dtype=rdt, device=g0.device)
+        check(self.lib.ssq_stft_adjoint(self._h, algos._ptr(gs[0]), algos._ptr(gs[1]),
+                                        gx.data_ptr(), B, algos.stream()))
+        return gx
+
+
+def wants_grad(x):
+    """Whether the transforms of `x` are to carry a gradient: a tensor that requires one, with
+    grad mode on."""
+    return isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+
+
+class _StftFunction(torch.autograd.Function):
+    """`Sx[, dSx] = plan(x)` with a backward through both (`StftPlan.adjoint`)."""
+
+    @staticmethod
+    def forward(ctx, x, plan, want_dSx):
+        out = plan.execute(x.detach(), want_dSx=want_dSx)
+        ctx.plan = plan
+        ctx.set_materialize_grads(False)
+        return (out['Sx'], out['dSx']) if want_dSx else out['Sx']
+
+    @staticmethod
+    def backward(ctx, gSx, gdSx=None):
+        if gSx is None and gdSx is None:
+            return None, None, None
+        return ctx.plan.adjoint(gSx, gdSx), None, None
+
 
 _PLAN_CACHE = {}
 
@@ -281,11 +331,19 @@ def stft(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None,
     (ssqueezepy/_stft.py:13-99). Returns `Sx` ``(n_fft//2 + 1, n_hops)`` with
     ``n_hops = (len(x) - 1)//hop_len + 1`` (batched: leading signal dim), plus
     `dSx` if `derivative`. Torch GPU tensors by default (`astensor=True`), NumPy
-    arrays otherwise."""
+    arrays otherwise.
+
+    Differentiable: when `x` is a tensor that requires grad (and grad mode is on), `Sx` and
+    `dSx` carry a `grad_fn`; the backward is the transform's exact adjoint on the device
+    (`StftPlan.adjoint`), bit-reproducible from call to call."""
     plan, xd, fs, dtype = _stft_setup(x, window, n_fft, win_len, hop_len, fs, t,
                                       padtype, modulated, dtype)
-    out = plan.execute(xd, want_dSx=derivative)
-    Sx, dSx = out['Sx'], out.get('dSx')
+    if wants_grad(x):
+        res = _StftFunction.apply(xd, plan, bool(derivative))
+        Sx, dSx = res if derivative else (res, None)
+    else:
+        out = plan.execute(xd, want_dSx=derivative)
+        Sx, dSx = out['Sx'], out.get('dSx')
     if not astensor:
         Sx = Sx.cpu().numpy()
         dSx = dSx.cpu().numpy() if dSx is not None else None

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device']
 
 _CDT = {torch.complex64: F32, torch.complex128: F64,
@@ -131,6 +131,44 @@ def ssqueeze_fast(Wx, dWx, ssq_freqs, const, logscale=False, flipud=False,
                            p, int(bool(flipud)), _ptr(kmap), stream()))
     if get_k:
         return out, kmap.reshape(Wx.shape)
+    return out
+
+
+def ssqueeze_adjoint(Wx, dWx, gTx, ssq_freqs, const, logscale=False, flipud=False,
+                     gamma=None, Sfs=None, out=None, accumulate=False):
+    """Adjoint of `ssqueeze_fast` with the bins held fixed: ``gWx[i, j] = const[i] *
+    gTx[k(i, j), j]`` where ``|Wx[i, j]| > gamma`` and 0 elsewhere, `k` the bin `ssqueeze_fast`
+    puts the point in (same arguments). The bins are integers, piecewise constant in the data,
+    so this is the exact gradient of `Tx` w.r.t. `Wx` wherever it exists. `out` with
+    `accumulate=True` is added to (a gradient that reaches `Wx` directly is already there);
+    otherwise it is overwritten / allocated."""
+    if gamma is None:
+        raise ValueError("`gamma` must not be None")
+    lib = _lib.load()
+    Wx, dWx = to_device(Wx), to_device(dWx)
+    if Wx.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Wx` must be complex64 or complex128 (got %s)" % Wx.dtype)
+    dWx = dWx.to(Wx.dtype)
+    gTx = to_device(gTx, Wx.dtype).resolve_conj().contiguous()
+    if Wx.shape != dWx.shape or Wx.shape != gTx.shape:
+        raise ValueError("`Wx`, `dWx` and `gTx` shapes differ: %s, %s, %s"
+                         % (tuple(Wx.shape), tuple(dWx.shape), tuple(gTx.shape)))
+    B, na, n = _shape3(Wx)
+    if out is None:
+        if accumulate:
+            raise ValueError("`accumulate=True` needs `out`")
+        out = torch.empty_like(Wx)
+    elif (out.shape != Wx.shape or out.dtype != Wx.dtype or not out.is_cuda
+          or not out.is_contiguous()):
+        raise ValueError("`out` must be a contiguous GPU tensor of `Wx`'s shape and dtype")
+    cst, c64 = _const_vector(const, na, Wx.dtype)
+    kind, p = _grid(ssq_freqs, logscale)
+    sfs = None
+    if Sfs is not None:
+        sfs = to_device(Sfs, _real_of(Wx.dtype))
+    check(lib.ssq_ssqueeze_adjoint(_CDT[Wx.dtype], _ptr(Wx), _ptr(dWx), _ptr(sfs), _ptr(gTx),
+                                   _ptr(out), int(bool(accumulate)), _ptr(cst), c64, B, na, n,
+                                   float(gamma), kind, p, int(bool(flipud)), stream()))
     return out
 
 

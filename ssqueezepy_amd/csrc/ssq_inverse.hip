@@ -6,11 +6,14 @@
 //                                                  _ssq_cwt.py:368-408, _ssq_stft.py:190-197
 //   istft                irfft of every column, overlap-add with window^a, divided by
 //                        the overlap-added window^(a+1)        _stft.py:238-256
+//   adjoint of stft      scale + transpose, inverse real transform, overlap-add with the window, no norm
+//                        (stft_adjoint_composed: the route of ssq_stft_adjoint for float64 / any n_fft)
 // Sums run in the reference's order (ascending row, one accumulator per column, in the
 // array's own precision), so the reductions are bit-identical to the NumPy results.
 // Compiled with -ffp-contract=off.
 #include "ssq_common.h"
 #include "ssq_fft.h"
+#include "ssq_stft.h"
 #include <rocfft/rocfft.h>
 #include <algorithm>
 #include <map>
@@ -334,6 +337,98 @@ static int istft_t(int dtype, const void* Sx, const void* win_a, const void* win
     (void)hipFreeAsync(St, stream);
     (void)hipFreeAsync(frames, stream);
     return rc;
+}
+
+// ---- composed adjoint of the STFT (float64, and every n_fft the fused kernel does not take) ----------------
+// St[c][f] = g[f][c], scaled so that rocFFT's inverse real transform -- which sums the Hermitian completion of
+// what it is given -- returns the one-sided sum Re sum_{k <= n_fft/2} g[k] e^{+2 pi i k n / n_fft}: interior bins
+// halved, DC and (even n_fft) Nyquist real
+template <typename T>
+__global__ __launch_bounds__(256) void adjoint_spec_transpose_kernel(const T* __restrict__ g, T* __restrict__ St,
+                                                                     int64_t rows, int64_t n_hops, int even) {
+    const int64_t total = rows * n_hops;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = t % rows, c = t / rows;
+        const bool edge = f == 0 || (even && f == rows - 1);
+        const T re = g[2 * (f * n_hops + c)], im = g[2 * (f * n_hops + c) + 1];
+        St[2 * t] = edge ? re : re * T(0.5);
+        St[2 * t + 1] = edge ? T(0) : im * T(0.5);
+    }
+}
+
+// ypad[p] (+)= sum over the frames i that hold padded position p, ascending, of frames[i][r] * win[r], r the
+// transform's index of the frame's sample p - i hop (the forward's rotation when modulated)
+template <typename T>
+__global__ __launch_bounds__(256) void adjoint_ola_kernel(const T* __restrict__ frames, const T* __restrict__ win,
+                                                          T* __restrict__ ypad, int64_t n_fft, int64_t n_hops,
+                                                          int64_t hop, int64_t padlen, int modulated, int accumulate) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= padlen) return;
+    const int64_t s20 = (n_fft + 1) / 2, s21 = n_fft / 2;
+    const int64_t i0 = p < n_fft ? 0 : (p - n_fft) / hop + 1;
+    const int64_t i1 = p / hop < n_hops - 1 ? p / hop : n_hops - 1;
+    T acc = accumulate ? ypad[p] : T(0);
+    for (int64_t i = i0; i <= i1; ++i) {
+        const int64_t m = p - i * hop;
+        const int64_t r = !modulated ? m : (m >= s21 ? m - s21 : m + s20);
+        acc = acc + frames[i * n_fft + r] * win[r];
+    }
+    ypad[p] = acc;
+}
+
+template <typename T>
+static int stft_adjoint_composed_t(int dtype, const void* gSx, const void* gdSx, const void* window,
+                                   const void* diff_window, void* ypad, int64_t batch, int64_t n_fft, int64_t n_hops,
+                                   int64_t hop, int64_t padlen, int modulated, hipStream_t stream) {
+    const int64_t rows = n_fft / 2 + 1, total = rows * n_hops;
+    T* St = nullptr; T* frames = nullptr;
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&St, (size_t)total * 2 * sizeof(T), stream));
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&frames, (size_t)(n_fft + 2) * n_hops * sizeof(T), stream));
+    const unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+    int rc = 0;
+    for (int64_t b = 0; b < batch && !rc; ++b) {
+        int accumulate = 0;
+        for (int side = 0; side < 2 && !rc; ++side) {
+            const T* src = (const T*)(side ? gdSx : gSx);
+            if (!src) continue;
+            hipLaunchKernelGGL((adjoint_spec_transpose_kernel<T>), dim3(g), dim3(256), 0, stream,
+                               src + (size_t)b * total * 2, St, rows, n_hops, (int)(n_fft % 2 == 0));
+            if (hipGetLastError() != hipSuccess) { set_error("adjoint_spec_transpose launch failed"); rc = -3; break; }
+            {
+                IstftFft* f = nullptr;
+                std::unique_lock<std::mutex> lock(g_istft_mu);
+                rc = istft_plan(dtype, n_fft, n_hops, stream, &f);
+                if (!rc) {
+                    rocfft_execution_info_set_stream(f->info, stream);
+                    void* ins[1] = {St}; void* outs[1] = {frames};
+                    if (rocfft_execute(f->plan, ins, outs, f->info) != rocfft_status_success) {
+                        set_error("rocfft_execute (stft adjoint) failed"); rc = -4;
+                    }
+                }
+            }
+            if (rc) break;
+            hipLaunchKernelGGL((adjoint_ola_kernel<T>), dim3((unsigned)((padlen + 255) / 256)), dim3(256), 0, stream,
+                               (const T*)frames, (const T*)(side ? diff_window : window),
+                               (T*)ypad + (size_t)b * padlen, n_fft, n_hops, hop, padlen, modulated, accumulate);
+            if (hipGetLastError() != hipSuccess) { set_error("adjoint_ola launch failed"); rc = -3; }
+            accumulate = 1;
+        }
+    }
+    (void)hipFreeAsync(St, stream);
+    (void)hipFreeAsync(frames, stream);
+    return rc;
+}
+
+int stft_adjoint_composed(int dtype, const void* gSx, const void* gdSx, const void* window, const void* diff_window,
+                          void* ypad, int64_t batch, int64_t n_fft, int64_t n_hops, int64_t hop, int64_t padlen,
+                          int modulated, hipStream_t stream) {
+    SSQ_REQUIRE(n_fft >= 2, "stft adjoint: n_fft %lld", (long long)n_fft);
+    if (dtype == SSQ_F32)
+        return stft_adjoint_composed_t<float>(dtype, gSx, gdSx, window, diff_window, ypad, batch, n_fft, n_hops, hop,
+                                              padlen, modulated, stream);
+    return stft_adjoint_composed_t<double>(dtype, gSx, gdSx, window, diff_window, ypad, batch, n_fft, n_hops, hop,
+                                           padlen, modulated, stream);
 }
 
 }  // namespace ssq

@@ -646,6 +646,38 @@ int launch_accumulate(int dtype, int binsrc, const void* Wx, const void* src, co
 #undef SSQ_ACC
 }
 
+// ------------------------------------------------- adjoint of the reassignment
+// The bins are integers, piecewise constant in the data: with them held fixed Tx is linear in Wx and its adjoint is a
+// gather, gWx[i][j] (+)= cst[i] * gTx[k(i, j)][j] (0 below gamma), k from the forward's own point math. Reads run along
+// j; the product is the forward's (float32 data with a float64 weight: formed in double, rounded once).
+template <typename T, bool STFT, bool CST64>
+__global__ __launch_bounds__(256) void ssqueeze_adjoint_kernel(
+    const T* __restrict__ Wx, const T* __restrict__ dWx, const T* __restrict__ Sfs, const T* __restrict__ gTx,
+    T* __restrict__ gWx, const void* __restrict__ cst, SsqParams sp, int64_t batch, int64_t na, int64_t n,
+    int accumulate) {
+    const int64_t total = batch * na * n, omax = na - 1;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = q / (na * n), i = (q - b * na * n) / n, j = q - (b * na + i) * n;
+        const T c = Wx[2 * q], d = Wx[2 * q + 1];
+        SideVal<T, BIN_FROM_DWX> sv;
+        sv.load(dWx, q, i, j, na);
+        const int64_t k = point_bin<T, BIN_FROM_DWX, STFT>(c, d, sv, i, Sfs, sp, omax);
+        T gr = T(0), gi = T(0);
+        if (k >= 0) {
+            const T* g = gTx + 2 * ((b * na + k) * n + j);
+            if constexpr (CST64 && sizeof(T) == 4) {
+                const double w = ((const double*)cst)[i];
+                gr = (T)((double)g[0] * w); gi = (T)((double)g[1] * w);
+            } else {
+                const T w = ((const T*)cst)[i];
+                gr = g[0] * w; gi = g[1] * w;
+            }
+        }
+        if (accumulate) { gr = gWx[2 * q] + gr; gi = gWx[2 * q + 1] + gi; }
+        gWx[2 * q] = gr; gWx[2 * q + 1] = gi;
+    }
+}
+
 // ------------------------------------------------------------------ phase
 template <typename T, bool STFT>
 __global__ __launch_bounds__(256) void phase_kernel(const T* __restrict__ Wx,
@@ -747,7 +779,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 105; }   // 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 106; }   // 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -844,6 +876,28 @@ int ssq_ssqueeze(int dtype, const void* Wx, const void* dWx, const void* Sfs, vo
     SsqParams sp;
     if (fill_params(sp, grid, params, flipud, gamma, cst_f64)) return -1;
     return launch_accumulate(dtype, BIN_FROM_DWX, Wx, dWx, Sfs, Tx, cst, sp, batch, na, n, kmap, as_stream(stream));
+}
+
+int ssq_ssqueeze_adjoint(int dtype, const void* Wx, const void* dWx, const void* Sfs, const void* gTx, void* gWx,
+                         int accumulate, const void* cst, int cst_f64, int64_t batch, int64_t na, int64_t n,
+                         double gamma, int grid, const double* params, int flipud, void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(Wx && dWx && gTx && gWx && cst, "ssq_ssqueeze_adjoint: null pointer");
+    SSQ_REQUIRE(na >= 1 && n >= 1 && batch >= 1, "ssqueeze_adjoint: empty shape (%lld, %lld, %lld)",
+                (long long)batch, (long long)na, (long long)n);
+    SsqParams sp;
+    if (fill_params(sp, grid, params, flipud, gamma, cst_f64)) return -1;
+    const dim3 g(stream_grid(batch * na * n));
+    hipStream_t s = as_stream(stream);
+#define SSQ_ADJ(T, STFT, C64) hipLaunchKernelGGL((ssqueeze_adjoint_kernel<T, STFT, C64>), g, dim3(256), 0, s, \
+        (const T*)Wx, (const T*)dWx, (const T*)Sfs, (const T*)gTx, (T*)gWx, cst, sp, batch, na, n, accumulate)
+    if (dtype == SSQ_F32) {
+        if (cst_f64) { if (Sfs) SSQ_ADJ(float, true, true); else SSQ_ADJ(float, false, true); }
+        else { if (Sfs) SSQ_ADJ(float, true, false); else SSQ_ADJ(float, false, false); }
+    } else { if (Sfs) SSQ_ADJ(double, true, false); else SSQ_ADJ(double, false, false); }
+#undef SSQ_ADJ
+    SSQ_LAUNCH_CHECK();
+    return 0;
 }
 
 int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const void* cst, int cst_f64,

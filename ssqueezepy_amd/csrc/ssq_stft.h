@@ -58,4 +58,10 @@ bool stft_generic_plan(int64_t n, int* radix, int* npass, int* G);
 int launch_stft_generic(const StftFusedArgs& A, const SsqParams& sp, const c32* tw, int n, const int* radix,
                         int npass, int G, int64_t batch, hipStream_t stream);
 
+// composed adjoint (ssq_inverse.hip): ypad (batch, padlen) <- the overlap-added, windowed, unnormalised one-sided inverse
+// transforms of gSx (window) and gdSx (diff_window), either of which may be null; rocFFT, a signal at a time
+int stft_adjoint_composed(int dtype, const void* gSx, const void* gdSx, const void* window, const void* diff_window,
+                          void* ypad, int64_t batch, int64_t n_fft, int64_t n_hops, int64_t hop, int64_t padlen,
+                          int modulated, hipStream_t stream);
+
 }  // namespace ssq

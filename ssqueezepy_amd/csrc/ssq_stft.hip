@@ -12,6 +12,8 @@
 // framing, both windows and both transforms in ONE launch for the whole batch -- the
 // two real frames a = frame*window, b = frame*diff_window ride one complex LDS FFT as
 // a + ib and are separated by Hermitian symmetry (stft_fused_kernel below).
+// The backward pass (ssq_stft_adjoint: gSx, gdSx -> gx) is at the end: stft_adjoint_fused_kernel for the fused plans,
+// the composed route of ssq_inverse.hip for the others, one unpadding pass for both.
 // Compiled with -ffp-contract=off (see ssq_kernels.hip).
 #include "ssq_common.h"
 #include "ssq_fft.h"
@@ -285,6 +287,138 @@ static int launch_stft_fused(const StftFusedArgs& A, const SsqParams& sp, int64_
 }
 
 
+// ---- fused adjoint of the STFT (float32, n_fft = L a power of two): gSx, gdSx -> overlap-added frames ------
+// One item = `nf` consecutive frames of one signal. Their overlap-added, windowed inverse transforms -- a strip of
+// (nf - 1) hop + L padded samples -- are summed in LDS and leave the workgroup once; no frame is ever in HBM, no frame
+// is computed twice, and no sum depends on the order workgroups or wavefronts run in (each strip sample belongs to
+// one work-item, which adds its frames in ascending order). The strips of neighbouring items overlap by L - hop
+// samples: stft_adjoint_unpad_kernel adds them, items ascending, while it folds the padding back onto the signal.
+// The real-output transforms ride the complex LDS inverse two at a time, as the forward's two windows do: with A, B
+// the Hermitian completions of two half-spectra (interior bins halved, the imaginary parts of DC and Nyquist dropped:
+// they do not reach a real output), ifft(A + iB) = a + ib. The pair is (gSx, gdSx) of one frame when both gradients
+// are there (G frames a pass), frames j and j + G of the one that is otherwise (2 G frames a pass).
+constexpr int ADJ_SPAN = 5120;                       // strip samples: 20 KB beside the transform's 32.5 KB (the LDS would hold three
+                                                     // workgroups per CU; from n_fft = 512 on the 186 .. 241 registers allow two)
+constexpr int ADJ_RAW = 2 * D_POINTS + 128;          // floats: the FFT buffer, then 2 G windowed frames of pitch L + 64 / G
+
+struct StftAdjArgs {
+    const float2* gA; const float2* gB;              // (batch, rows, n_hops); gB null: gA's frames pair up
+    const float* winA; const float* winB;            // the windows that go with gA, gB
+    const c32* ftw; float* ws;                       // ws (batch, n_items, span)
+    int64_t n_hops, rows, n_items;
+    int hop, modulated, nf, span, batch;
+};
+
+template <int L, int G, int R1, int R2, int R3>
+__global__ __launch_bounds__(NT) void stft_adjoint_fused_kernel(StftAdjArgs A) {
+    __shared__ float raw[ADJ_RAW];
+    __shared__ float strip[ADJ_SPAN];
+    constexpr int PITCH = L + 64 / G;                // (the G columns of a butterfly's output land in G different banks)
+    static_assert(2 * G * PITCH <= ADJ_RAW, "stft_adjoint_fused_kernel: the windowed frames outgrow the FFT buffer");
+    static_assert(sizeof(float) * (ADJ_RAW + ADJ_SPAN) <= 53 * 1024, "stft_adjoint_fused_kernel: static LDS beyond a third of a CU's 160 KB");
+    constexpr int RL = (R3 > 1) ? R3 : R2;
+    c32* const buf = reinterpret_cast<c32*>(raw);
+    const int tid = threadIdx.x;
+    const int64_t item = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (item >= A.n_items * A.batch) return;
+    const int b = (int)(item / A.n_items), it0 = (int)(item % A.n_items);
+    const int64_t c_first = (int64_t)it0 * A.nf;
+    const int nfv = A.n_hops - c_first < A.nf ? (int)(A.n_hops - c_first) : A.nf;          // the item's frames
+    const bool both = A.gB != nullptr;
+    const int FP = both ? G : 2 * G;                                       // frames per pass
+    const float2* const gB = both ? A.gB : A.gA;
+    const int rot = A.modulated ? L / 2 : 0;
+    const int64_t base = (int64_t)b * A.rows * A.n_hops + c_first;
+    const int span = (nfv - 1) * A.hop + L;                                // <= A.span <= ADJ_SPAN
+    for (int p = tid; p < span; p += NT) strip[p] = 0.f;                  // (strip[p] is work-item p % NT's alone)
+    for (int j0 = 0; j0 < nfv; j0 += FP) {
+        const int fpv = min(FP, nfv - j0);
+        c32 z[PPT];
+        {
+            constexpr int NB = PPT / R1, STR = L / R1;
+#pragma unroll
+            for (int it = 0; it < NB; ++it) {
+                const int idx = tid + it * NT, g = idx % G, u = idx / G;
+                const int jA = j0 + g, jB = both ? jA : jA + G;
+#pragma unroll
+                for (int k = 0; k < R1; ++k) {
+                    const int q = u + k * STR, f = q <= L / 2 ? q : L - q;
+                    const bool edge = f == 0 || f == L / 2;
+                    const int64_t row = base + (int64_t)f * A.n_hops;
+                    float2 a = make_float2(0.f, 0.f), d = make_float2(0.f, 0.f);
+                    if (jA < nfv) a = A.gA[row + jA];
+                    if (jB < nfv) d = gB[row + jB];
+                    const float s = edge ? 1.f : 0.5f, si = edge ? 0.f : (q > L / 2 ? -0.5f : 0.5f);
+                    const float ar = a.x * s, ai = a.y * si, br = d.x * s, bi = d.y * si;
+                    z[it * R1 + k] = {ar - bi, ai + br};
+                }
+            }
+        }
+        lds_ifft<L, G, R1, R2, R3, false, false>(z, buf, A.ftw, tid);     // (its first barrier: the last pass' frames are read)
+        __syncthreads();                                                   // the transform's LDS reads are done
+        {
+            constexpr int NB = PPT / RL, STR = L / RL;
+#pragma unroll
+            for (int it = 0; it < NB; ++it) {
+                const int idx = tid + it * NT, g = idx % G, u = idx / G;
+#pragma unroll
+                for (int k = 0; k < RL; ++k) {
+                    const int n = u + k * STR;
+                    const c32 v = z[it * RL + k];
+                    if (both) raw[g * PITCH + n] = v.x * A.winA[n] + v.y * A.winB[n];
+                    else {
+                        raw[g * PITCH + n] = v.x * A.winA[n];
+                        raw[(G + g) * PITCH + n] = v.y * A.winA[n];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // the pass' frames j0 .. j0 + fpv - 1 into the strip: sample p takes frame j's sample p - j hop
+        const int p_lo = j0 * A.hop, p_hi = (j0 + fpv - 1) * A.hop + L;
+        for (int p = p_lo + ((tid - p_lo) & (NT - 1)); p < p_hi; p += NT) {
+            const int j_hi = min(j0 + fpv - 1, p / A.hop);
+            const int j_lo = max(j0, p < L ? 0 : (p - L) / A.hop + 1);
+            float acc = strip[p];
+            for (int j = j_lo; j <= j_hi; ++j) acc = acc + raw[(j - j0) * PITCH + ((p - j * A.hop) ^ rot)];
+            strip[p] = acc;
+        }
+    }
+    float* const o = A.ws + ((int64_t)b * A.n_items + it0) * A.span;
+    for (int p = tid; p < span; p += NT) o[p] = strip[p];
+}
+
+// gx[j] = the sum of the overlap-added samples whose source under the padding rule is j: `off`, `idx` list those
+// padded positions per signal sample, ascending. A position is summed over the strips that hold it -- item i holds the
+// positions [i step, i step + span) -- items ascending; positions from `pmax` on lie behind the last frame.
+template <typename T>
+__global__ __launch_bounds__(256) void stft_adjoint_unpad_kernel(
+    const T* __restrict__ ws, T* __restrict__ gx, const int32_t* __restrict__ off, const int32_t* __restrict__ idx,
+    int64_t n, int64_t n_items, int64_t step, int64_t span, int64_t pmax) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const T* w = ws + (int64_t)blockIdx.y * n_items * span;
+    T acc = T(0);
+    for (int32_t e = off[j]; e < off[j + 1]; ++e) {
+        const int64_t p = idx[e];
+        if (p >= pmax) continue;
+        const int64_t i_hi = p / step < n_items - 1 ? p / step : n_items - 1, i_lo = p < span ? 0 : (p - span) / step + 1;
+        for (int64_t i = i_lo; i <= i_hi; ++i) acc = acc + w[i * span + (p - i * step)];
+    }
+    gx[(int64_t)blockIdx.y * n + j] = acc;
+}
+
+template <int L, int G, int R1, int R2, int R3>
+static int launch_stft_adjoint_fused(const StftAdjArgs& A, hipStream_t stream) {
+    const int64_t total = A.n_items * A.batch;
+    const int64_t gx = std::min<int64_t>(total, (int64_t)1 << 20), gy = (total + gx - 1) / gx;
+    SSQ_REQUIRE(gy <= 65535, "stft_adjoint_fused_kernel: %lld items", (long long)total);
+    hipLaunchKernelGGL((stft_adjoint_fused_kernel<L, G, R1, R2, R3>), dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0,
+                       stream, A);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
 // R2C with transposed (strided) output: transform c writes bin f at out[f*n_hops + c]
 struct StridedR2C {
     rocfft_plan plan = nullptr; rocfft_execution_info info = nullptr;
@@ -346,6 +480,7 @@ struct ssq_stft_plan {
     WeightVersions weights, freqs;                                                      // these
     PlanOrder order;
     bool executed = false;
+    int32_t* adj_off = nullptr; int32_t* adj_idx = nullptr;   // the adjoint's inverse pad map (built at its first call)
 };
 
 extern "C" {
@@ -430,7 +565,7 @@ void ssq_stft_plan_destroy(ssq_stft_plan* pl) {
     pl->fft.destroy();
     pl->weights.destroy(); pl->freqs.destroy(); pl->order.destroy();
     void* ptrs[] = {pl->window, pl->diff_window, pl->xp, pl->frames, pl->dframes, pl->dSx_ws,
-                    pl->ftw, pl->kidx, pl->wd};
+                    pl->ftw, pl->kidx, pl->wd, pl->adj_off, pl->adj_idx};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete pl;
 }
@@ -601,6 +736,122 @@ extern "C" int ssq_stft_execute(ssq_stft_plan* pl, const void* x, int64_t batch,
     const int rc = pl->d.dtype == SSQ_F32 ? stft_execute_t<float>(pl, x, batch, Sx, dSx, Tx, w, st)
                                           : stft_execute_t<double>(pl, x, batch, Sx, dSx, Tx, w, st);
     pl->executed = true;
+    pl->order.leave(st);
+    return rc;
+}
+
+// the padded positions that copy signal sample j, per j (ascending): the transpose of the plan's signal extension
+static int stft_adjoint_pad_table(ssq_stft_plan* pl) {
+    if (pl->adj_off) return 0;
+    const int64_t n = pl->d.n, m = pl->padlen, n1 = pl->n1;
+    SSQ_REQUIRE(m < ((int64_t)1 << 31), "stft adjoint: padded length %lld", (long long)m);
+    auto source = [&](int64_t t) -> int64_t {              // (the rule of pad_kernel / stft_pad_source)
+        if (t >= 0 && t < n) return t;
+        switch (pl->d.padtype) {
+            case SSQ_PAD_REFLECT: {
+                if (n == 1) return 0;
+                const int64_t period = 2 * (n - 1);
+                int64_t q = t % period; if (q < 0) q += period;
+                return q < n ? q : period - q;
+            }
+            case SSQ_PAD_SYMMETRIC: {
+                const int64_t period = 2 * n;
+                int64_t q = t % period; if (q < 0) q += period;
+                return q < n ? q : period - 1 - q;
+            }
+            case SSQ_PAD_REPLICATE: return t < 0 ? 0 : n - 1;
+            case SSQ_PAD_WRAP: { int64_t q = t % n; if (q < 0) q += n; return q; }
+            default: return -1;
+        }
+    };
+    std::vector<int32_t> off((size_t)n + 1, 0), idx((size_t)m);
+    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) ++off[(size_t)j + 1]; }
+    for (int64_t j = 0; j < n; ++j) off[(size_t)j + 1] += off[(size_t)j];
+    std::vector<int32_t> fill(off.begin(), off.end() - 1);
+    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) idx[(size_t)fill[(size_t)j]++] = (int32_t)p; }
+    SSQ_CHECK_HIP(hipMalloc((void**)&pl->adj_idx, idx.size() * 4));
+    SSQ_CHECK_HIP(hipMemcpy(pl->adj_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    int32_t* o = nullptr;
+    SSQ_CHECK_HIP(hipMalloc((void**)&o, off.size() * 4));
+    SSQ_CHECK_HIP(hipMemcpy(o, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    pl->adj_off = o;
+    return 0;
+}
+
+template <typename T>
+static int stft_adjoint_unpad(ssq_stft_plan* pl, const void* ws, void* gx, int64_t batch, int64_t n_items,
+                              int64_t step, int64_t span, int64_t pmax, hipStream_t stream) {
+    dim3 grid((unsigned)((pl->d.n + 255) / 256), (unsigned)batch);
+    hipLaunchKernelGGL((stft_adjoint_unpad_kernel<T>), grid, dim3(256), 0, stream, (const T*)ws, (T*)gx,
+                       (const int32_t*)pl->adj_off, (const int32_t*)pl->adj_idx, pl->d.n, n_items, step, span, pmax);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+static int stft_adjoint_fused(ssq_stft_plan* pl, const void* gSx, const void* gdSx, void* gx, int64_t batch,
+                              hipStream_t stream) {
+    const ssq_stft_desc& d = pl->d;
+    const int L = (int)d.n_fft, G = D_POINTS / L, hop = (int)d.hop_len;
+    StftAdjArgs A;
+    const bool both = gSx && gdSx;
+    A.gA = (const float2*)(gSx ? gSx : gdSx); A.gB = both ? (const float2*)gdSx : nullptr;
+    A.winA = (const float*)(gSx ? pl->window : pl->diff_window); A.winB = (const float*)pl->diff_window;
+    A.ftw = (const c32*)pl->ftw;
+    A.n_hops = pl->n_hops; A.rows = pl->rows; A.hop = hop; A.modulated = d.modulated; A.batch = (int)batch;
+    // frames per item: what the strip holds, in whole passes -- fewer where that leaves the chip short of workgroups
+    const int FP = both ? G : 2 * G;
+    int64_t nf = (ADJ_SPAN - L) / hop + 1;
+    if (nf >= FP) {
+        nf = nf / FP * FP;
+        const int64_t want = ((pl->n_hops * batch + 1023) / 1024 + FP - 1) / FP * FP;
+        nf = std::max<int64_t>(FP, std::min(nf, want));
+    }
+    nf = std::min(nf, pl->n_hops);
+    A.nf = (int)nf;
+    A.n_items = (pl->n_hops + nf - 1) / nf;
+    A.span = (int)((nf - 1) * hop + L);
+    SSQ_REQUIRE(A.span <= ADJ_SPAN, "stft adjoint: strip of %d samples", A.span);
+    float* ws = nullptr;
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
+    A.ws = ws;
+    int rc;
+    switch (L) {
+        case 128: rc = launch_stft_adjoint_fused<128, 32, 16, 8, 1>(A, stream); break;
+        case 256: rc = launch_stft_adjoint_fused<256, 16, 16, 16, 1>(A, stream); break;
+        case 512: rc = launch_stft_adjoint_fused<512, 8, 8, 8, 8>(A, stream); break;
+        case 1024: rc = launch_stft_adjoint_fused<1024, 4, 16, 8, 8>(A, stream); break;
+        default: rc = launch_stft_adjoint_fused<2048, 2, 16, 16, 8>(A, stream); break;
+    }
+    if (!rc) rc = stft_adjoint_unpad<float>(pl, ws, gx, batch, A.n_items, nf * hop, A.span,
+                                            (pl->n_hops - 1) * (int64_t)hop + L, stream);
+    (void)hipFreeAsync(ws, stream);
+    return rc;
+}
+
+extern "C" int ssq_stft_adjoint(ssq_stft_plan* pl, const void* gSx, const void* gdSx, void* gx, int64_t batch,
+                                void* stream) {
+    SSQ_REQUIRE(pl && gx && (gSx || gdSx), "ssq_stft_adjoint: null pointer");
+    SSQ_REQUIRE(batch >= 1 && batch <= pl->d.max_batch, "batch %lld outside [1, %lld]",
+                (long long)batch, (long long)pl->d.max_batch);
+    SSQ_REQUIRE(batch <= 65535, "ssq_stft_adjoint: batch %lld > 65535", (long long)batch);
+    SSQ_REQUIRE(!gdSx || pl->diff_window, "the gradient of dSx needs a diff_window");
+    hipStream_t st = as_stream(stream);
+    pl->order.enter(st);
+    int rc = stft_adjoint_pad_table(pl);
+    if (!rc) {
+        const ssq_stft_desc& d = pl->d;
+        // (SSQ_DEBUG_STFT_ADJOINT_COMPOSED: the composed route on a fused plan, for comparisons)
+        const bool fused = pl->fused && !getenv("SSQ_DEBUG_STFT_ADJOINT_COMPOSED") && d.hop_len < ((int64_t)1 << 24);
+        if (fused) rc = stft_adjoint_fused(pl, gSx, gdSx, gx, batch, st);
+        else {
+            // composed: the overlap-added frames of the whole batch in the plan's padded-signal workspace, one strip
+            rc = stft_adjoint_composed(d.dtype, gSx, gdSx, pl->window, pl->diff_window, pl->xp, batch, d.n_fft,
+                                       pl->n_hops, d.hop_len, pl->padlen, d.modulated, st);
+            if (!rc) rc = d.dtype == SSQ_F32
+                ? stft_adjoint_unpad<float>(pl, pl->xp, gx, batch, 1, pl->padlen, pl->padlen, pl->padlen, st)
+                : stft_adjoint_unpad<double>(pl, pl->xp, gx, batch, 1, pl->padlen, pl->padlen, pl->padlen, st);
+        }
+    }
     pl->order.leave(st);
     return rc;
 }
