@@ -45,7 +45,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 106 (105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 107 (106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -157,6 +157,27 @@ int ssq_colsum(int dtype, const void* Z, const void* divisor, void* out, int64_t
 int ssq_band_colsum(int dtype, const void* Z, const int32_t* lo, const int32_t* hi,
                     int64_t ncomp, double* out, int64_t na, int64_t n, void* stream);
 
+/* ssq_band_colsum for `batch` signals: Z (batch, na, n), out (batch, ncomp + 1, n). lo/hi are (ncomp, n), shared by
+ * the signals (`bands_per_signal` == 0), or (batch, ncomp, n). Each signal's result has the bits of a single call. */
+int ssq_band_colsum_batch(int dtype, const void* Z, const int32_t* lo, const int32_t* hi,
+                          int bands_per_signal, int64_t ncomp, double* out, int64_t batch,
+                          int64_t na, int64_t n, void* stream);
+
+/* Adjoint of ssq_colsum (the gradient of a real loss w.r.t. the complex Z, gZ = dL/dRe + i dL/dIm):
+ *   gZ[b, i, j] = g[b, j] [/ divisor[i]] + 0i
+ * g (batch, n) real, gZ (batch, na, n) complex, overwritten; the imaginary parts are exact zeros. One streaming pass,
+ * every element written once. */
+int ssq_colsum_adjoint(int dtype, const void* g, const void* divisor, void* gZ, int64_t batch,
+                       int64_t na, int64_t n, void* stream);
+
+/* Adjoint of ssq_band_colsum_batch: g (batch, ncomp + 1, n) float64 -> gZ (batch, na, n) complex of `dtype`,
+ *   gZ[b, i, j] = sum over k < ncomp, ascending, of g[b, k, j] where lo[k, j] <= i <= hi[k, j]
+ *               (g[b, ncomp, j] where no band holds row i) + 0i,
+ * summed in float64 and rounded once. lo/hi as in ssq_band_colsum_batch. */
+int ssq_band_colsum_adjoint(int dtype, const double* g, const int32_t* lo, const int32_t* hi,
+                            int bands_per_signal, int64_t ncomp, void* gZ, int64_t batch,
+                            int64_t na, int64_t n, void* stream);
+
 /* Double-integral inverse CWT core: out (n_up) real <- Re ifft( sum_a fft(Wp[a]) * psih[a] ).
  * `Wp` (na, n_up) complex: the padded transform, overwritten (used as FFT workspace);
  * `psih` (na, n_up) real: wavelet samples already divided by the scale normalisation.
@@ -179,6 +200,34 @@ int ssq_trigdiff(int dtype, void* Ap, const void* xi, double fs, void* out, int6
 int ssq_istft(int dtype, const void* Sx, const void* win_a, const void* win_a1, void* x,
               int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N, int modulated,
               void* stream);
+
+/* ssq_istft for `batch` signals: Sx (batch, n_fft/2 + 1, n_hops), x (batch, N); a single signal is batch 1.
+ *   x[b, s] = ( sum_t win_a[r] * irfft(Sx[b, :, t])[r'] ) / wn[p],   p = s + n_fft/2, r = p - t hop_len in [0, n_fft),
+ *   r' = r rotated by n_fft/2 if `modulated`, wn[p] = sum_t win_a1[p - t hop_len] over t < (N - 1) / hop_len + 1
+ *   (no division where wn <= the dtype's smallest normal number).
+ * The route is the one ssq_istft_algo names: "fused" -- one LDS-transform kernel for the whole batch that overlap-adds
+ * the frames of an item in LDS (no frame reaches memory), then a pass that adds neighbouring strips in ascending order,
+ * divides by wn (computed once per call) and trims -- or "rocfft": ssq_istft's route, a signal at a time. Each
+ * signal's result does not depend on the batch it is in. */
+int ssq_istft_batch(int dtype, const void* Sx, const void* win_a, const void* win_a1, void* x,
+                    int64_t batch, int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N,
+                    int modulated, void* stream);
+
+/* Adjoint of ssq_istft_batch (gSx = dL/dRe(Sx) + i dL/dIm(Sx) of a real loss with gradient g w.r.t. x):
+ * g (batch, N) real -> gSx (batch, n_fft/2 + 1, n_hops) complex, overwritten.
+ *   u[p] = g[p - n_fft/2] / wn[p]  (g[...] itself where the forward did not divide; 0 outside the N samples)
+ *   gSx[k, t] = (c_k / n_fft) * rfft_k( win_a[r] * u[t hop_len + r] ),  the frame rotated as in the forward,
+ *   c_k = 1 for DC and (even n_fft) Nyquist, 2 elsewhere; the imaginary parts of those bins are exact zeros.
+ * "fused" shapes run the forward STFT's LDS-transform kernel on u (zero-extended on the fly) with the weights applied
+ * where a bin is stored; the others frame u, window it, run rocFFT's real forward transform and weight the result.
+ * Two calls on the same input give the same bits. */
+int ssq_istft_adjoint(int dtype, const void* g, const void* win_a, const void* win_a1, void* gSx,
+                      int64_t batch, int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N,
+                      int modulated, void* stream);
+
+/* The route ssq_istft_batch / ssq_istft_adjoint take for a shape: "fused" (float32, n_fft a power of two in
+ * [128, 2048], n_hops == (N - 1) / hop_len + 1) or "rocfft" (everything else). */
+const char* ssq_istft_algo(int dtype, int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N);
 
 /* ------------------------------------------------------------ ridge extraction
  * The loop nests of extract_ridges (ridge_extraction.py:113-232) on arrays that are

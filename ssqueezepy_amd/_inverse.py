@@ -7,6 +7,12 @@ reductions over the scale / frequency axis, the inverse real FFTs and the overla
 runs on the device through the C ABI (`ssq_colsum`, `ssq_band_colsum`, `ssq_istft`,
 include/ssq_hip.h); admissibility constants and windows are host design values.
 A NumPy input gives a NumPy result, a torch GPU tensor gives a torch GPU tensor.
+
+`istft`, `issq_stft`, `issq_cwt` and `icwt(one_int=True)` take a single transform or a batch
+(leading signal dimension) and are differentiable: when the transform is a tensor that requires
+grad (and grad mode is on) the result carries a `grad_fn`, its backward the adjoint kernels
+`ssq_istft_adjoint`, `ssq_colsum_adjoint`, `ssq_band_colsum_adjoint`, bit-reproducible from call
+to call. `icwt(one_int=False)` takes a single transform and carries no gradient.
 """
 import logging
 import numpy as np
@@ -201,20 +207,23 @@ def _process_component_inversion_args(cc, cw):
 
 def _invert_components(Td, cc, cw):
     """Sums of Re(Tx) inside the curve bands ``cc +- cw`` (one per component) and of
-    the remainder (_ssq_cwt.py:381-403): `cc == -1` marks "no curve at this time"."""
-    na = Td.shape[0]
+    the remainder (_ssq_cwt.py:381-403): `cc == -1` marks "no curve at this time". `cc`, `cw`:
+    (N, K), shared by the signals of a batched `Td`, or (B, N, K)."""
+    na = Td.shape[-2]
     upper = np.clip(cc + cw, 0, na)
     lower = np.clip(cc - cw, 0, na)
     upper[cc == -1] = 0
     lower[cc == -1] = 1
     # slice(lower, upper + 1): rows lower .. min(upper, na - 1)
-    return algos.band_colsum(Td, lower.T, np.minimum(upper, na - 1).T)
+    return algos.band_colsum(Td, np.swapaxes(lower, -1, -2),
+                             np.swapaxes(np.minimum(upper, na - 1), -1, -2))
 
 
 def issq_cwt(Tx, wavelet='gmw', cc=None, cw=None):
     """Inverse synchrosqueezed CWT: ``x = (2 / C_ssq) * sum_k Re(Tx[k])`` or, with curve
     centres `cc` and half-widths `cw` (N x K), the K components and the residual
-    ((K + 1) x N, float64)."""
+    ((K + 1) x N, float64). `Tx`: (na, N) or batched (B, na, N), then `cc`, `cw` (N, K) for all
+    signals or (B, N, K), result (B, N) / (B, K + 1, N). Differentiable w.r.t. `Tx`."""
     cc, cw, full_inverse = _process_component_inversion_args(cc, cw)
     Td = algos.to_device(Tx)
     x = algos.colsum_real(Td) if full_inverse else _invert_components(Td, cc, cw)
@@ -229,10 +238,13 @@ def issq_cwt(Tx, wavelet='gmw', cc=None, cw=None):
 def istft(Sx, window=None, n_fft=None, win_len=None, hop_len=1, N=None, modulated=True,
           win_exp=1):
     """Inverse STFT (Griffin & Lim least-squares estimate for `win_exp=1`):
-    ``x[n] = sum_t y_t[n] w^a[n - tH] / sum_t w^(a+1)[n - tH]``, ``y_t = irfft(Sx[:, t])``."""
-    n_fft = n_fft or (Sx.shape[0] - 1) * 2
+    ``x[n] = sum_t y_t[n] w^a[n - tH] / sum_t w^(a+1)[n - tH]``, ``y_t = irfft(Sx[:, t])``.
+    `Sx`: (n_fft//2 + 1, n_hops) or batched (B, n_fft//2 + 1, n_hops); result (N,) / (B, N).
+    float32 with `n_fft` a power of two in [128, 2048] and ``n_hops == (N - 1)//hop_len + 1`` runs
+    one fused kernel for the whole batch (`algos.istft_algo`). Differentiable w.r.t. `Sx`."""
+    n_fft = n_fft or (Sx.shape[-2] - 1) * 2
     win_len = win_len or n_fft
-    N = N or hop_len * Sx.shape[1]          # longest possible signal if not given
+    N = N or hop_len * Sx.shape[-1]         # longest possible signal if not given
     dtype = 'float32' if str(Sx.dtype).endswith('complex64') else 'float64'
     window = _window_and_checks(window, win_len, n_fft, hop_len, dtype)
     if len(window) != n_fft:
@@ -252,13 +264,14 @@ def istft(Sx, window=None, n_fft=None, win_len=None, hop_len=1, N=None, modulate
 def issq_stft(Tx, window=None, cc=None, cw=None, n_fft=None, win_len=None, hop_len=1,
               modulated=True):
     """Inverse synchrosqueezed STFT (hop 1, modulated): ``x = (2 / w[n_fft//2]) *
-    sum_k Re(Tx[k])``, optionally per curve band as in `issq_cwt`."""
+    sum_k Re(Tx[k])``, optionally per curve band as in `issq_cwt`. `Tx` single or batched, and
+    differentiable, as there."""
     if not modulated:
         raise ValueError("inversion with `modulated == False` is unsupported.")
     if hop_len != 1:
         raise ValueError("inversion with `hop_len != 1` is unsupported.")
     cc, cw, full_inverse = _process_component_inversion_args(cc, cw)
-    n_fft = n_fft or (Tx.shape[0] - 1) * 2
+    n_fft = n_fft or (Tx.shape[-2] - 1) * 2
     win_len = win_len or n_fft
     window = _window_and_checks(window, win_len, n_fft, hop_len, None)
     if abs(np.argmax(window) - len(window) // 2) > 1:

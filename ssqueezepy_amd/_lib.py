@@ -98,6 +98,17 @@ _PROTOS = {
                              c_int64, c_int64, c_void_p]),
     'ssq_istft': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                           c_int64, c_int64, c_int64, c_int, c_void_p]),
+    'ssq_istft_batch': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                c_int64, c_int64, c_int64, c_int, c_void_p]),
+    'ssq_istft_adjoint': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                  c_int64, c_int64, c_int64, c_int, c_void_p]),
+    'ssq_istft_algo': (c_char_p, [c_int, c_int64, c_int64, c_int64, c_int64]),
+    'ssq_colsum_adjoint': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                   c_int64, c_void_p]),
+    'ssq_band_colsum_batch': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                      c_void_p, c_int64, c_int64, c_int64, c_void_p]),
+    'ssq_band_colsum_adjoint': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                        c_void_p, c_int64, c_int64, c_int64, c_void_p]),
     'ssq_ridge_energy': (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     'ssq_ridge_neglog': (c_int, [c_int, c_void_p, c_void_p, c_double, c_int64, c_int64, c_void_p]),
     'ssq_ridge_track': (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_double,
@@ -144,7 +155,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 106     # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 107     # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -17,7 +17,8 @@ from . import _lib
 from ._lib import check, params5, F32, F64
 
 __all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu',
-           'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device']
+           'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
+           'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
 _CDT = {torch.complex64: F32, torch.complex128: F64,
         torch.float32: F32, torch.float64: F64}
@@ -267,53 +268,187 @@ def pad_signal_gpu(x, n1, n2, padtype='reflect'):
 
 
 # ------------------------------------------------------------------ inverses
+def wants_grad(x):
+    """Whether a function of `x` is to carry a gradient: a tensor that requires one, with grad
+    mode on."""
+    return isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled()
+
+
+def _divisor(divisor, na, rdt):
+    if divisor is None:
+        return None
+    d = to_device(np.ascontiguousarray(np.asarray(divisor).reshape(-1)), rdt)
+    if d.numel() != na:
+        raise ValueError("`divisor` must have one entry per row (%d != %d)"
+                         % (d.numel(), na))
+    return d
+
+
+def _colsum(Z, d):
+    B, na, n = _shape3(Z)
+    out = torch.empty(Z.shape[:-2] + (n,), dtype=_real_of(Z.dtype), device=Z.device)
+    check(_lib.load().ssq_colsum(_CDT[Z.dtype], _ptr(Z), _ptr(d), _ptr(out), B, na, n,
+                                 stream()))
+    return out
+
+
+def colsum_adjoint(g, na, divisor=None):
+    """Adjoint of `colsum_real`: ``gZ[..., i, j] = g[..., j] [/ divisor[i]] + 0j`` (`ssq_colsum_adjoint`);
+    `g` real (n,) or (B, n), `gZ` complex (na, n) or (B, na, n) of the matching precision."""
+    g = to_device(g).contiguous()
+    if g.dtype not in (torch.float32, torch.float64):
+        raise TypeError("`g` must be float32 or float64 (got %s)" % g.dtype)
+    d = divisor if isinstance(divisor, torch.Tensor) else _divisor(divisor, na, g.dtype)
+    n = g.shape[-1]
+    B = 1 if g.ndim == 1 else g.shape[0]
+    cdt = torch.complex64 if g.dtype == torch.float32 else torch.complex128
+    gZ = torch.empty(g.shape[:-1] + (int(na), n), dtype=cdt, device=g.device)
+    check(_lib.load().ssq_colsum_adjoint(_CDT[g.dtype], _ptr(g), _ptr(d), _ptr(gZ), B, int(na), n,
+                                         stream()))
+    return gZ
+
+
+class _ColsumFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, d):
+        ctx.d, ctx.na = d, Z.shape[-2]
+        return _colsum(Z.detach(), d)
+
+    @staticmethod
+    def backward(ctx, g):
+        return colsum_adjoint(g, ctx.na, ctx.d), None
+
+
 def colsum_real(Z, divisor=None):
     """``sum_i Re(Z[..., i, :]) [/ divisor[i]]`` over the scale / frequency axis, rows in
     ascending order in `Z`'s own precision (bit-identical to NumPy's
-    ``(Z.real / d).sum(axis=-2)``). `Z`: (na, n) or (B, na, n) complex."""
-    lib = _lib.load()
+    ``(Z.real / d).sum(axis=-2)``). `Z`: (na, n) or (B, na, n) complex. Differentiable w.r.t. `Z`
+    (`colsum_adjoint`)."""
+    grad = wants_grad(Z)
     Z = to_device(Z)
     B, na, n = _shape3(Z)
-    rdt = _real_of(Z.dtype)
-    d = None if divisor is None else to_device(np.ascontiguousarray(
-        np.asarray(divisor).reshape(-1)), rdt)
-    if d is not None and d.numel() != na:
-        raise ValueError("`divisor` must have one entry per row (%d != %d)"
-                         % (d.numel(), na))
-    out = torch.empty(Z.shape[:-2] + (n,), dtype=rdt, device=Z.device)
-    check(lib.ssq_colsum(_CDT[Z.dtype], _ptr(Z), _ptr(d) if d is not None else None,
-                         _ptr(out), B, na, n, stream()))
+    d = _divisor(divisor, na, _real_of(Z.dtype))
+    return _ColsumFunction.apply(Z, d) if grad else _colsum(Z.detach(), d)
+
+
+def _bands(lo, hi, Z):
+    """`lo`, `hi` (K, n) or (B, K, n) as int32 device arrays, and whether every signal has its own."""
+    lo = np.ascontiguousarray(lo, dtype=np.int32)
+    hi = np.ascontiguousarray(hi, dtype=np.int32)
+    if lo.shape != hi.shape or lo.ndim not in (2, 3) or lo.shape[-1] != Z.shape[-1]:
+        raise ValueError("`lo`, `hi` must be (K, n) or (B, K, n) (got %s, %s; n = %d)"
+                         % (lo.shape, hi.shape, Z.shape[-1]))
+    if lo.ndim == 3 and (Z.ndim != 3 or lo.shape[0] != Z.shape[0]):
+        raise ValueError("per-signal bands %s do not match a transform of shape %s"
+                         % (lo.shape, tuple(Z.shape)))
+    return (torch.as_tensor(lo, device=Z.device), torch.as_tensor(hi, device=Z.device),
+            lo.ndim == 3)
+
+
+def _band_colsum(Z, lo, hi, own):
+    B, na, n = _shape3(Z)
+    K = lo.shape[-2]
+    out = torch.empty(Z.shape[:-2] + (K + 1, n), dtype=torch.float64, device=Z.device)
+    check(_lib.load().ssq_band_colsum_batch(_CDT[Z.dtype], _ptr(Z), _ptr(lo), _ptr(hi), int(own), K,
+                                            _ptr(out), B, na, n, stream()))
     return out
+
+
+def band_colsum_adjoint(g, lo, hi, na, cdtype):
+    """Adjoint of `band_colsum`: ``gZ[..., i, j]`` = the sum, bands ascending, of ``g[..., k, j]`` over
+    the bands that hold row `i` -- ``g[..., K, j]`` where none does -- in float64, rounded once to
+    `cdtype`; imaginary part zero (`ssq_band_colsum_adjoint`)."""
+    g = to_device(g, torch.float64)
+    gZ = torch.empty(g.shape[:-2] + (int(na), g.shape[-1]), dtype=cdtype, device=g.device)
+    if not isinstance(lo, torch.Tensor):
+        lo, hi, own = _bands(lo, hi, gZ)
+    else:
+        own = lo.ndim == 3
+    B, _, n = _shape3(gZ)
+    check(_lib.load().ssq_band_colsum_adjoint(_CDT[cdtype], _ptr(g), _ptr(lo), _ptr(hi), int(own),
+                                              lo.shape[-2], _ptr(gZ), B, int(na), n, stream()))
+    return gZ
+
+
+class _BandColsumFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, lo, hi, own):
+        ctx.lo, ctx.hi, ctx.na, ctx.cdt = lo, hi, Z.shape[-2], Z.dtype
+        return _band_colsum(Z.detach(), lo, hi, own)
+
+    @staticmethod
+    def backward(ctx, g):
+        return band_colsum_adjoint(g, ctx.lo, ctx.hi, ctx.na, ctx.cdt), None, None, None
 
 
 def band_colsum(Z, lo, hi):
     """Per-component sums of ``Re(Z)`` over the row bands ``lo[k, j] .. hi[k, j]`` of every
     column (float64), plus the sum of the rows no band covers as the last row.
-    `Z`: (na, n) complex; `lo`, `hi`: (K, n) integer arrays, inclusive."""
-    lib = _lib.load()
+    `Z`: (na, n) or (B, na, n) complex; `lo`, `hi`: (K, n) integer arrays, inclusive, shared by
+    the signals, or (B, K, n). Differentiable w.r.t. `Z` (`band_colsum_adjoint`)."""
+    grad = wants_grad(Z)
     Z = to_device(Z)
-    if Z.ndim != 2:
-        raise ValueError("component inversion takes a single (na, n) transform")
-    na, n = Z.shape
-    lo = torch.as_tensor(np.ascontiguousarray(lo, dtype=np.int32), device=Z.device)
-    hi = torch.as_tensor(np.ascontiguousarray(hi, dtype=np.int32), device=Z.device)
-    K = lo.shape[0]
-    out = torch.empty((K + 1, n), dtype=torch.float64, device=Z.device)
-    check(lib.ssq_band_colsum(_CDT[Z.dtype], _ptr(Z), _ptr(lo), _ptr(hi), K, _ptr(out),
-                              na, n, stream()))
-    return out
+    _shape3(Z)
+    lo, hi, own = _bands(lo, hi, Z)
+    if grad:
+        return _BandColsumFunction.apply(Z, lo, hi, own)
+    return _band_colsum(Z.detach(), lo, hi, own)
+
+
+def istft_algo(dtype, n_fft, n_hops, hop_len, N):
+    """The route `istft_gpu` and its backward take for a shape: 'fused' or 'rocfft' (`ssq_istft_algo`)."""
+    code = F32 if str(dtype) in ('float32', 'torch.float32', 'torch.complex64', 'complex64') else F64
+    return _lib.load().ssq_istft_algo(code, int(n_fft), int(n_hops), int(hop_len), int(N)).decode()
+
+
+def _istft(Sx, wa, wa1, n_fft, hop_len, N, modulated):
+    B, rows, n_hops = _shape3(Sx)
+    x = torch.empty(Sx.shape[:-2] + (int(N),), dtype=_real_of(Sx.dtype), device=Sx.device)
+    check(_lib.load().ssq_istft_batch(_CDT[Sx.dtype], _ptr(Sx), _ptr(wa), _ptr(wa1), _ptr(x), B,
+                                      int(n_fft), int(n_hops), int(hop_len), int(N),
+                                      int(bool(modulated)), stream()))
+    return x
+
+
+def istft_adjoint_gpu(g, win_a, win_a1, n_fft, n_hops, hop_len, modulated=True):
+    """Adjoint of `istft_gpu`: `g` real (N,) or (B, N) -> `gSx` complex (n_fft//2 + 1, n_hops) or
+    batched (`ssq_istft_adjoint`, include/ssq_hip.h states the formula)."""
+    g = to_device(g).contiguous()
+    rdt = g.dtype
+    cdt = torch.complex64 if rdt == torch.float32 else torch.complex128
+    wa, wa1 = to_device(win_a, rdt), to_device(win_a1, rdt)
+    B = 1 if g.ndim == 1 else g.shape[0]
+    N = g.shape[-1]
+    gSx = torch.empty(g.shape[:-1] + (int(n_fft) // 2 + 1, int(n_hops)), dtype=cdt, device=g.device)
+    check(_lib.load().ssq_istft_adjoint(_CDT[rdt], _ptr(g), _ptr(wa), _ptr(wa1), _ptr(gSx), B,
+                                        int(n_fft), int(n_hops), int(hop_len), int(N),
+                                        int(bool(modulated)), stream()))
+    return gSx
+
+
+class _IstftFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Sx, wa, wa1, n_fft, hop_len, N, modulated):
+        ctx.args = (wa, wa1, n_fft, Sx.shape[-1], hop_len, modulated)
+        return _istft(Sx.detach(), wa, wa1, n_fft, hop_len, N, modulated)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (istft_adjoint_gpu(g, *ctx.args),) + (None,) * 6
 
 
 def istft_gpu(Sx, win_a, win_a1, n_fft, hop_len, N, modulated=True):
     """irfft of every column of `Sx` + overlap-add with `win_a`, divided by the
-    overlap-added `win_a1`, trimmed to `N` samples (`ssq_istft`, include/ssq_hip.h)."""
-    lib = _lib.load()
+    overlap-added `win_a1`, trimmed to `N` samples (`ssq_istft_batch`, include/ssq_hip.h).
+    `Sx`: (n_fft//2 + 1, n_hops) or (B, n_fft//2 + 1, n_hops). Differentiable w.r.t. `Sx`
+    (`istft_adjoint_gpu`)."""
+    grad = wants_grad(Sx)
     Sx = to_device(Sx)
+    B, rows, n_hops = _shape3(Sx)
+    if rows != int(n_fft) // 2 + 1:
+        raise ValueError("`Sx` has %d rows, n_fft = %d needs %d" % (rows, n_fft, int(n_fft) // 2 + 1))
     rdt = _real_of(Sx.dtype)
-    rows, n_hops = Sx.shape
     wa, wa1 = to_device(win_a, rdt), to_device(win_a1, rdt)
-    x = torch.empty(int(N), dtype=rdt, device=Sx.device)
-    check(lib.ssq_istft(_CDT[Sx.dtype], _ptr(Sx), _ptr(wa), _ptr(wa1), _ptr(x),
-                        int(n_fft), int(n_hops), int(hop_len), int(N),
-                        int(bool(modulated)), stream()))
-    return x
+    if grad:
+        return _IstftFunction.apply(Sx, wa, wa1, int(n_fft), int(hop_len), int(N), bool(modulated))
+    return _istft(Sx.detach(), wa, wa1, n_fft, hop_len, N, modulated)

@@ -1,5 +1,6 @@
-// ssq_inverse.hip -- device side of the inverse transforms (C ABI: ssq_colsum,
-// ssq_band_colsum, ssq_istft). The inverses of the reference are reductions over the
+// ssq_inverse.hip -- device side of the inverse transforms (C ABI: ssq_colsum, ssq_band_colsum[_batch], ssq_istft[_batch]
+// and their adjoints ssq_colsum_adjoint, ssq_band_colsum_adjoint, ssq_istft_adjoint; the fused inverse-STFT kernels
+// they launch are in ssq_stft.hip). The inverses of the reference are reductions over the
 // scale / frequency axis of arrays that already live on the device:
 //   icwt (one integral)  x[j] = sum_i Re(Wx[i,j]) / norm(scale_i)      _cwt.py:472-476
 //   issq_cwt, issq_stft  x[j] = sum_i Re(Tx[i,j])  (optionally inside curve bands)
@@ -60,11 +61,14 @@ __global__ __launch_bounds__(256) void band_colsum_kernel(const T* __restrict__ 
                                                           const int32_t* __restrict__ lo,
                                                           const int32_t* __restrict__ hi, int K,
                                                           double* __restrict__ out, int64_t na,
-                                                          int64_t n) {
+                                                          int64_t n, int64_t band_stride) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const int k = (int)blockIdx.y;
-    const T* z = Z + 2 * j;
+    // blockIdx.z: the signal; its bands are the shared ones (band_stride 0) or its own
+    const T* z = Z + 2 * ((int64_t)blockIdx.z * na * n + j);
+    lo += (int64_t)blockIdx.z * band_stride; hi += (int64_t)blockIdx.z * band_stride;
+    out += (int64_t)blockIdx.z * (K + 1) * n;
     if (k < K) {
         double acc = 0.0;
         const int64_t a = lo[(int64_t)k * n + j], b = hi[(int64_t)k * n + j];
@@ -79,6 +83,63 @@ __global__ __launch_bounds__(256) void band_colsum_kernel(const T* __restrict__ 
             if (!covered) acc = acc + z[2 * i * n];
         }
         out[(int64_t)K * n + j] = (double)acc;
+    }
+}
+
+// gZ[b][i][j] = (g[b][j] (/ div[i]), 0): the adjoint of colsum_kernel. One streaming pass: a work-item holds V columns'
+// gradients and writes them to ROWS rows, 16 bytes a store (V = 2 complex64 / 1 complex128; V = 1 with 8-byte stores for
+// complex64 rows of an odd length, whose starts are not all 16-byte aligned). Every element is written once.
+constexpr int CSA_ROWS = 8;
+template <typename T, bool DIV, int V>
+__global__ __launch_bounds__(256) void colsum_adjoint_kernel(const T* __restrict__ g, const T* __restrict__ div,
+                                                             T* __restrict__ gZ, int64_t na, int64_t n) {
+    typedef T vec_t __attribute__((ext_vector_type(2 * V)));
+    const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (j >= n) return;
+    const int64_t b = blockIdx.z, i0 = (int64_t)blockIdx.y * CSA_ROWS;
+    T gv[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) gv[v] = g[b * n + j + v];              // (V == 2 only where n is even: j + 1 < n)
+    T* o = gZ + 2 * ((b * na + i0) * n + j);
+#pragma unroll
+    for (int r = 0; r < CSA_ROWS; ++r) {
+        if (i0 + r >= na) break;
+        vec_t out;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            T t = gv[v];
+            if (DIV) t = t / div[i0 + r];
+            out[2 * v] = t; out[2 * v + 1] = T(0);
+        }
+        *reinterpret_cast<vec_t*>(o + 2 * r * n) = out;
+    }
+}
+
+// gZ[b][i][j] = (sum over the bands k that hold row i, ascending, of g[b][k][j], or g[b][K][j] where none does; 0):
+// the adjoint of band_colsum_kernel, summed in double and rounded once to T
+template <typename T>
+__global__ __launch_bounds__(256) void band_colsum_adjoint_kernel(const double* __restrict__ g,
+                                                                  const int32_t* __restrict__ lo,
+                                                                  const int32_t* __restrict__ hi, int K,
+                                                                  T* __restrict__ gZ, int64_t na, int64_t n,
+                                                                  int64_t band_stride) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int64_t b = blockIdx.z, i0 = (int64_t)blockIdx.y * CSA_ROWS;
+    lo += b * band_stride + j; hi += b * band_stride + j;
+    g += b * (K + 1) * n + j;
+    T* o = gZ + 2 * ((b * na + i0) * n + j);
+    for (int r = 0; r < CSA_ROWS && i0 + r < na; ++r) {
+        const int64_t i = i0 + r;
+        double acc = 0.0;
+        bool covered = false;
+        for (int k = 0; k < K; ++k) {
+            const bool in = (i >= lo[(int64_t)k * n]) & (i <= hi[(int64_t)k * n]);
+            if (in) acc = acc + g[(int64_t)k * n];
+            covered |= in;
+        }
+        if (!covered) acc = g[(int64_t)K * n];
+        o[2 * r * n] = (T)acc; o[2 * r * n + 1] = T(0);
     }
 }
 
@@ -339,6 +400,108 @@ static int istft_t(int dtype, const void* Sx, const void* win_a, const void* win
     return rc;
 }
 
+// ---- batched inverse STFT and its backward ------------------------------------------------------------------
+// wn[s] = the overlap-added win_a1 at the untrimmed position s + n_fft / 2, over the frames the reference's window
+// norm counts, in double (the sum istft_ola_kernel forms per sample): once per call, not per signal
+template <typename T>
+__global__ __launch_bounds__(256) void istft_norm_kernel(const T* __restrict__ win_a1, double* __restrict__ wn,
+                                                         int64_t n_fft, int64_t hop, int64_t N) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= N) return;
+    const int64_t p = s + n_fft / 2, max_hops = (N - 1) / hop + 1;
+    int64_t i0 = p - n_fft + 1;
+    i0 = i0 <= 0 ? 0 : (i0 + hop - 1) / hop;
+    const int64_t i1 = p / hop;
+    double acc = 0.0;
+    for (int64_t i = i0; i <= i1 && i < max_hops; ++i) acc = acc + (double)win_a1[p - i * hop];
+    wn[s] = acc;
+}
+
+// win_t[r] = win_a[frame position of the transform's index r]: the rotation by n_fft / 2 of a modulated frame
+template <typename T>
+__global__ __launch_bounds__(256) void window_rotate_kernel(const T* __restrict__ win_a, T* __restrict__ win_t,
+                                                            int64_t n_fft, int modulated) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_fft) return;
+    win_t[r] = win_a[modulated ? (r + n_fft / 2) % n_fft : r];
+}
+
+// upad[b][p] = g[b][p - lead] / wn[p - lead] (g itself where the forward did not divide), 0 outside the N samples
+template <typename T>
+__global__ __launch_bounds__(256) void istft_u_kernel(const T* __restrict__ g, const double* __restrict__ wn,
+                                                      T* __restrict__ upad, int64_t N, int64_t lead, int64_t ulen, T tiny) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= ulen) return;
+    const int64_t s = p - lead;
+    T v = T(0);
+    if (s >= 0 && s < N) {
+        v = g[(int64_t)blockIdx.y * N + s];
+        const double d = wn[s];
+        if (d > (double)tiny) v = (T)((double)v / d);
+    }
+    upad[(int64_t)blockIdx.y * ulen + p] = v;
+}
+
+static bool istft_takes_fused(int dtype, int64_t n_fft, int64_t n_hops, int64_t hop, int64_t N) {
+    const bool pow2 = n_fft >= 128 && n_fft <= 2048 && (n_fft & (n_fft - 1)) == 0;
+    // (SSQ_DEBUG_ISTFT_COMPOSED: the composed route on a shape the fused kernels take, for comparisons)
+    return dtype == SSQ_F32 && pow2 && hop >= 1 && N >= 1 && n_hops == (N - 1) / hop + 1 && hop < ((int64_t)1 << 24)
+        && N + n_fft < ((int64_t)1 << 30) && !getenv("SSQ_DEBUG_ISTFT_COMPOSED");
+}
+
+template <typename T>
+static int istft_batch_t(int dtype, const void* Sx, const void* win_a, const void* win_a1, void* x, int64_t batch,
+                         int64_t n_fft, int64_t n_hops, int64_t hop, int64_t N, int modulated, hipStream_t stream) {
+    const int64_t rows = n_fft / 2 + 1;
+    if (!istft_takes_fused(dtype, n_fft, n_hops, hop, N)) {
+        int rc = 0;
+        for (int64_t b = 0; b < batch && !rc; ++b)
+            rc = istft_t<T>(dtype, (const T*)Sx + (size_t)b * rows * n_hops * 2, win_a, win_a1, (T*)x + (size_t)b * N,
+                            n_fft, n_hops, hop, N, modulated, stream);
+        return rc;
+    }
+    double* wn = nullptr; T* win_t = nullptr;
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&wn, (size_t)N * sizeof(double), stream));
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&win_t, (size_t)n_fft * sizeof(T), stream));
+    int rc = 0;
+    hipLaunchKernelGGL((istft_norm_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (const T*)win_a1,
+                       wn, n_fft, hop, N);
+    hipLaunchKernelGGL((window_rotate_kernel<T>), dim3((unsigned)((n_fft + 255) / 256)), dim3(256), 0, stream,
+                       (const T*)win_a, win_t, n_fft, modulated);
+    if (hipGetLastError() != hipSuccess) { set_error("istft norm / window launch failed"); rc = -3; }
+    if (!rc) rc = istft_fused(Sx, win_t, wn, x, batch, n_fft, n_hops, hop, N, modulated, stream);
+    (void)hipFreeAsync(wn, stream);
+    (void)hipFreeAsync(win_t, stream);
+    return rc;
+}
+
+template <typename T>
+static int istft_adjoint_t(int dtype, const void* g, const void* win_a, const void* win_a1, void* gSx, int64_t batch,
+                           int64_t n_fft, int64_t n_hops, int64_t hop, int64_t N, int modulated, hipStream_t stream) {
+    const bool fused = istft_takes_fused(dtype, n_fft, n_hops, hop, N);
+    // fused: u (batch, N), the kernel extends it with zeros; composed: u between n_fft / 2 and the frames' end of zeros
+    const int64_t lead = fused ? 0 : n_fft / 2, ulen = fused ? N : (n_hops - 1) * hop + n_fft;
+    double* wn = nullptr; T* win_t = nullptr; T* u = nullptr;
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&wn, (size_t)N * sizeof(double), stream));
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&win_t, (size_t)n_fft * sizeof(T), stream));
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&u, (size_t)batch * ulen * sizeof(T), stream));
+    const T tiny = sizeof(T) == 4 ? (T)1.17549435e-38f : (T)2.2250738585072014e-308;
+    int rc = 0;
+    hipLaunchKernelGGL((istft_norm_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (const T*)win_a1,
+                       wn, n_fft, hop, N);
+    hipLaunchKernelGGL((window_rotate_kernel<T>), dim3((unsigned)((n_fft + 255) / 256)), dim3(256), 0, stream,
+                       (const T*)win_a, win_t, n_fft, modulated);
+    hipLaunchKernelGGL((istft_u_kernel<T>), dim3((unsigned)((ulen + 255) / 256), (unsigned)batch), dim3(256), 0, stream,
+                       (const T*)g, (const double*)wn, u, N, lead, ulen, tiny);
+    if (hipGetLastError() != hipSuccess) { set_error("istft adjoint: norm / window / u launch failed"); rc = -3; }
+    if (!rc) rc = fused ? istft_adjoint_fused(u, win_t, gSx, batch, n_fft, n_hops, hop, N, modulated, stream)
+                        : istft_adjoint_composed(dtype, u, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated, stream);
+    (void)hipFreeAsync(wn, stream);
+    (void)hipFreeAsync(win_t, stream);
+    (void)hipFreeAsync(u, stream);
+    return rc;
+}
+
 // ---- composed adjoint of the STFT (float64, and every n_fft the fused kernel does not take) ----------------
 // St[c][f] = g[f][c], scaled so that rocFFT's inverse real transform -- which sums the Hermitian completion of
 // what it is given -- returns the one-sided sum Re sum_{k <= n_fft/2} g[k] e^{+2 pi i k n / n_fft}: interior bins
@@ -459,14 +622,64 @@ int ssq_band_colsum(int dtype, const void* Z, const int32_t* lo, const int32_t* 
     SSQ_REQUIRE(Z && lo && hi && out, "ssq_band_colsum: null pointer");
     SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
     SSQ_REQUIRE(ncomp >= 1 && ncomp <= 65534 && na >= 1 && n >= 1, "band_colsum: bad shape");
-    dim3 grid((unsigned)((n + 255) / 256), (unsigned)(ncomp + 1));
+    return ssq_band_colsum_batch(dtype, Z, lo, hi, 0, ncomp, out, 1, na, n, stream);
+}
+
+int ssq_band_colsum_batch(int dtype, const void* Z, const int32_t* lo, const int32_t* hi, int bands_per_signal,
+                          int64_t ncomp, double* out, int64_t batch, int64_t na, int64_t n, void* stream) {
+    SSQ_REQUIRE(Z && lo && hi && out, "ssq_band_colsum_batch: null pointer");
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
+    SSQ_REQUIRE(ncomp >= 1 && ncomp <= 65534 && na >= 1 && n >= 1 && batch >= 1 && batch <= 65535,
+                "band_colsum: bad shape");
+    dim3 grid((unsigned)((n + 255) / 256), (unsigned)(ncomp + 1), (unsigned)batch);
+    const int64_t stride = bands_per_signal ? ncomp * n : 0;
     hipStream_t s = as_stream(stream);
     if (dtype == SSQ_F32)
         hipLaunchKernelGGL((band_colsum_kernel<float>), grid, dim3(256), 0, s, (const float*)Z, lo, hi,
-                           (int)ncomp, out, na, n);
+                           (int)ncomp, out, na, n, stride);
     else
         hipLaunchKernelGGL((band_colsum_kernel<double>), grid, dim3(256), 0, s, (const double*)Z, lo, hi,
-                           (int)ncomp, out, na, n);
+                           (int)ncomp, out, na, n, stride);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssq_band_colsum_adjoint(int dtype, const double* g, const int32_t* lo, const int32_t* hi, int bands_per_signal,
+                            int64_t ncomp, void* gZ, int64_t batch, int64_t na, int64_t n, void* stream) {
+    SSQ_REQUIRE(g && lo && hi && gZ, "ssq_band_colsum_adjoint: null pointer");
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
+    SSQ_REQUIRE(ncomp >= 1 && ncomp <= 65534 && na >= 1 && n >= 1 && batch >= 1 && batch <= 65535
+                && (na + CSA_ROWS - 1) / CSA_ROWS <= 65535, "band_colsum_adjoint: bad shape");
+    dim3 grid((unsigned)((n + 255) / 256), (unsigned)((na + CSA_ROWS - 1) / CSA_ROWS), (unsigned)batch);
+    const int64_t stride = bands_per_signal ? ncomp * n : 0;
+    hipStream_t s = as_stream(stream);
+    if (dtype == SSQ_F32)
+        hipLaunchKernelGGL((band_colsum_adjoint_kernel<float>), grid, dim3(256), 0, s, g, lo, hi, (int)ncomp,
+                           (float*)gZ, na, n, stride);
+    else
+        hipLaunchKernelGGL((band_colsum_adjoint_kernel<double>), grid, dim3(256), 0, s, g, lo, hi, (int)ncomp,
+                           (double*)gZ, na, n, stride);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssq_colsum_adjoint(int dtype, const void* g, const void* divisor, void* gZ, int64_t batch, int64_t na,
+                       int64_t n, void* stream) {
+    SSQ_REQUIRE(g && gZ, "ssq_colsum_adjoint: null pointer");
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
+    SSQ_REQUIRE(batch >= 1 && batch <= 65535 && na >= 1 && n >= 1 && (na + CSA_ROWS - 1) / CSA_ROWS <= 65535,
+                "colsum_adjoint: bad shape (%lld, %lld, %lld)", (long long)batch, (long long)na, (long long)n);
+    hipStream_t s = as_stream(stream);
+    // (16-byte stores need 16-byte aligned rows: complex64 rows of an even length in an aligned array)
+    const bool v2 = dtype == SSQ_F32 && n % 2 == 0 && ((uintptr_t)gZ & 15) == 0;
+    const int64_t cols = v2 ? n / 2 : n;
+    dim3 grid((unsigned)((cols + 255) / 256), (unsigned)((na + CSA_ROWS - 1) / CSA_ROWS), (unsigned)batch);
+#define LAUNCH(T, DIV, V) hipLaunchKernelGGL((colsum_adjoint_kernel<T, DIV, V>), grid, dim3(256), 0, s, (const T*)g, \
+                                             (const T*)divisor, (T*)gZ, na, n)
+    if (dtype == SSQ_F64) { if (divisor) LAUNCH(double, true, 1); else LAUNCH(double, false, 1); }
+    else if (v2) { if (divisor) LAUNCH(float, true, 2); else LAUNCH(float, false, 2); }
+    else { if (divisor) LAUNCH(float, true, 1); else LAUNCH(float, false, 1); }
+#undef LAUNCH
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -498,6 +711,36 @@ int ssq_istft(int dtype, const void* Sx, const void* win_a, const void* win_a1, 
     if (dtype == SSQ_F32)
         return istft_t<float>(dtype, Sx, win_a, win_a1, x, n_fft, n_hops, hop_len, N, modulated, as_stream(stream));
     return istft_t<double>(dtype, Sx, win_a, win_a1, x, n_fft, n_hops, hop_len, N, modulated, as_stream(stream));
+}
+
+int ssq_istft_batch(int dtype, const void* Sx, const void* win_a, const void* win_a1, void* x, int64_t batch,
+                    int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N, int modulated, void* stream) {
+    SSQ_REQUIRE(Sx && win_a && win_a1 && x, "ssq_istft_batch: null pointer");
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
+    SSQ_REQUIRE(n_fft >= 2 && n_hops >= 1 && hop_len >= 1 && N >= 1, "istft: bad sizes");
+    SSQ_REQUIRE(batch >= 1 && batch <= 65535, "istft: batch %lld outside [1, 65535]", (long long)batch);
+    if (dtype == SSQ_F32)
+        return istft_batch_t<float>(dtype, Sx, win_a, win_a1, x, batch, n_fft, n_hops, hop_len, N, modulated,
+                                    as_stream(stream));
+    return istft_batch_t<double>(dtype, Sx, win_a, win_a1, x, batch, n_fft, n_hops, hop_len, N, modulated,
+                                 as_stream(stream));
+}
+
+int ssq_istft_adjoint(int dtype, const void* g, const void* win_a, const void* win_a1, void* gSx, int64_t batch,
+                      int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N, int modulated, void* stream) {
+    SSQ_REQUIRE(g && win_a && win_a1 && gSx, "ssq_istft_adjoint: null pointer");
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
+    SSQ_REQUIRE(n_fft >= 2 && n_hops >= 1 && hop_len >= 1 && N >= 1, "istft adjoint: bad sizes");
+    SSQ_REQUIRE(batch >= 1 && batch <= 65535, "istft adjoint: batch %lld outside [1, 65535]", (long long)batch);
+    if (dtype == SSQ_F32)
+        return istft_adjoint_t<float>(dtype, g, win_a, win_a1, gSx, batch, n_fft, n_hops, hop_len, N, modulated,
+                                      as_stream(stream));
+    return istft_adjoint_t<double>(dtype, g, win_a, win_a1, gSx, batch, n_fft, n_hops, hop_len, N, modulated,
+                                   as_stream(stream));
+}
+
+const char* ssq_istft_algo(int dtype, int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N) {
+    return istft_takes_fused(dtype, n_fft, n_hops, hop_len, N) ? "fused" : "rocfft";
 }
 
 }  // extern "C"

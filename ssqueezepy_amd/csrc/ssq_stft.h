@@ -64,4 +64,17 @@ int stft_adjoint_composed(int dtype, const void* gSx, const void* gdSx, const vo
                           void* ypad, int64_t batch, int64_t n_fft, int64_t n_hops, int64_t hop, int64_t padlen,
                           int modulated, hipStream_t stream);
 
+// ---- inverse STFT: what ssq_istft_batch / ssq_istft_adjoint (ssq_inverse.hip) run in ssq_stft.hip. `win_t` is window^a
+// in the transform's order (rotated by n_fft / 2 when modulated), `wn` the window norm of the N trimmed samples.
+// fused (float32, n_fft a power of two in [128, 2048], n_hops == (N - 1) / hop + 1): stft_adjoint_fused_kernel with the
+// inverse real transform's weights + istft_finish_kernel; its backward: stft_fused_kernel over u (batch, N) = g / wn
+int istft_fused(const void* Sx, const void* win_t, const double* wn, void* x, int64_t batch, int64_t n_fft,
+                int64_t n_hops, int64_t hop, int64_t N, int modulated, hipStream_t stream);
+int istft_adjoint_fused(const void* u, const void* win_t, void* gSx, int64_t batch, int64_t n_fft, int64_t n_hops,
+                        int64_t hop, int64_t N, int modulated, hipStream_t stream);
+// composed backward: framing of upad (batch, ulen), ulen = (n_hops - 1) hop + n_fft -- u zero-extended --, window,
+// rocFFT's real forward transform into gSx's layout, the weights c_k / n_fft; a signal at a time
+int istft_adjoint_composed(int dtype, const void* upad, const void* win_t, void* gSx, int64_t batch, int64_t n_fft,
+                           int64_t n_hops, int64_t hop, int64_t ulen, int modulated, hipStream_t stream);
+
 }  // namespace ssq

@@ -22,6 +22,9 @@
 #include <vector>
 #include <cmath>
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <rocfft/rocfft.h>
 
 namespace ssq {
@@ -64,8 +67,13 @@ __global__ __launch_bounds__(256) void frame_window_kernel(
 // transform's LDS bank conflicts (padded columns: +2 %). The counters put the vector ALU at ~60 % and the LDS pipe at
 // ~58 % busy: what is left is instruction count.
 
-template <int L, int G, int R1, int R2, int R3, bool REASSIGN, bool CST64>
+// IADJ (the backward of the fused inverse STFT, ssq_istft_adjoint): the transform is the adjoint of an inverse real
+// transform -- every bin leaves with its weight c_k / L (c_k = 1 for DC and Nyquist, 2 elsewhere) and the imaginary
+// parts of DC and Nyquist as exact zeros, applied where the bin is stored. `if constexpr`: the other instantiations
+// compile to the code they had.
+template <int L, int G, int R1, int R2, int R3, bool REASSIGN, bool CST64, bool IADJ = false>
 __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqParams sp) {
+    static_assert(!IADJ || !REASSIGN, "stft_fused_kernel: the inverse's backward stores Sx only");
     // the frames' Tx: a real and an imaginary plane of (L/2 + 1) x G float64 cells. The planes take the FFT buffer's
     // place once its last reader is done (the workgroup's LDS stays at 32 KB + 16 G bytes: four workgroups per CU)
     constexpr int CELLS = REASSIGN ? (L / 2 + 1) * G : 1;
@@ -199,7 +207,12 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
                 if (c >= A.n_hops) continue;
                 const c32 P = buf[f * G + g], Q = buf[((L - f) & (L - 1)) * G + g];
                 const int64_t q = base + (int64_t)f * A.n_hops + c;
-                const float sr = 0.5f * (P.x + Q.x), si = 0.5f * (Q.y - P.y);
+                float sr = 0.5f * (P.x + Q.x), si = 0.5f * (Q.y - P.y);
+                if constexpr (IADJ) {
+                    const bool edge = f == 0 || f == L / 2;
+                    const float c = edge ? 1.f / L : 2.f / L;
+                    sr = sr * c; si = edge ? 0.f : si * c;
+                }
                 A.Sx[q] = make_float2(sr, si);
                 if (!deriv) continue;
                 const float dr = -0.5f * (P.y + Q.y), di = 0.5f * (Q.x - P.x);
@@ -264,7 +277,7 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
 }
 
 // one workgroup per item; the grid is two-dimensional only to hold more than 2^31 - 1 of them
-template <int L, int G, int R1, int R2, int R3>
+template <int L, int G, int R1, int R2, int R3, bool IADJ = false>
 static int launch_stft_fused(const StftFusedArgs& A, const SsqParams& sp, int64_t batch, hipStream_t stream) {
     SSQ_REQUIRE(!A.Tx || A.rows == L / 2 + 1, "fused reassignment: %lld rows, transform of %d", (long long)A.rows, L);
     StftFusedArgs B = A;
@@ -276,7 +289,9 @@ static int launch_stft_fused(const StftFusedArgs& A, const SsqParams& sp, int64_
     const int64_t gx = std::min<int64_t>(total, (int64_t)1 << 20), gy = (total + gx - 1) / gx;
     SSQ_REQUIRE(gy <= 65535, "stft_fused_kernel: %lld items", (long long)total);
     dim3 grid((unsigned)gx, (unsigned)gy);
-    if (!A.Tx)
+    if constexpr (IADJ)
+        hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, false, false, true>), grid, dim3(NT), 0, stream, B, sp);
+    else if (!A.Tx)
         hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, false, false>), grid, dim3(NT), 0, stream, B, sp);
     else if (sp.cst_f64)
         hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, true, true>), grid, dim3(NT), 0, stream, B, sp);
@@ -309,7 +324,11 @@ struct StftAdjArgs {
     int hop, modulated, nf, span, batch;
 };
 
-template <int L, int G, int R1, int R2, int R3>
+// INV: the same kernel as the fused inverse STFT (ssq_istft_batch). What differs is the weights of an inverse real
+// transform -- every bin whole and 1 / L (exact: L is a power of two) where the adjoint halves the interior bins --,
+// the window (gA = Sx, winA = window^a in the transform's order, gB null) and the pass that finishes the strips
+// (istft_finish_kernel: the window norm and the trim instead of the padding's transpose).
+template <int L, int G, int R1, int R2, int R3, bool INV>
 __global__ __launch_bounds__(NT) void stft_adjoint_fused_kernel(StftAdjArgs A) {
     __shared__ float raw[ADJ_RAW];
     __shared__ float strip[ADJ_SPAN];
@@ -348,7 +367,8 @@ __global__ __launch_bounds__(NT) void stft_adjoint_fused_kernel(StftAdjArgs A) {
                     float2 a = make_float2(0.f, 0.f), d = make_float2(0.f, 0.f);
                     if (jA < nfv) a = A.gA[row + jA];
                     if (jB < nfv) d = gB[row + jB];
-                    const float s = edge ? 1.f : 0.5f, si = edge ? 0.f : (q > L / 2 ? -0.5f : 0.5f);
+                    constexpr float WI = INV ? 1.f / L : 0.5f, WE = INV ? 1.f / L : 1.f;      // interior, edge bins
+                    const float s = edge ? WE : WI, si = edge ? 0.f : (q > L / 2 ? -WI : WI);
                     const float ar = a.x * s, ai = a.y * si, br = d.x * s, bi = d.y * si;
                     z[it * R1 + k] = {ar - bi, ai + br};
                 }
@@ -408,12 +428,32 @@ __global__ __launch_bounds__(256) void stft_adjoint_unpad_kernel(
     gx[(int64_t)blockIdx.y * n + j] = acc;
 }
 
-template <int L, int G, int R1, int R2, int R3>
+// x[b][s] = the overlap-added sample p = s + half (the trim), summed over the strips that hold it, items ascending, and
+// divided by the window norm wn[s] where that is above `tiny` (the reference's window_norm, in double as istft_ola_kernel)
+__global__ __launch_bounds__(256) void istft_finish_kernel(const float* __restrict__ ws, const double* __restrict__ wn,
+                                                           float* __restrict__ x, int64_t N, int64_t half,
+                                                           int64_t n_items, int64_t step, int64_t span, int64_t pmax,
+                                                           float tiny) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= N) return;
+    const float* w = ws + (int64_t)blockIdx.y * n_items * span;
+    const int64_t p = s + half;
+    float acc = 0.f;
+    if (p < pmax) {
+        const int64_t i_hi = p / step < n_items - 1 ? p / step : n_items - 1, i_lo = p < span ? 0 : (p - span) / step + 1;
+        for (int64_t i = i_lo; i <= i_hi; ++i) acc = acc + w[i * span + (p - i * step)];
+    }
+    const double d = wn[s];
+    if (d > (double)tiny) acc = (float)((double)acc / d);
+    x[(int64_t)blockIdx.y * N + s] = acc;
+}
+
+template <int L, int G, int R1, int R2, int R3, bool INV = false>
 static int launch_stft_adjoint_fused(const StftAdjArgs& A, hipStream_t stream) {
     const int64_t total = A.n_items * A.batch;
     const int64_t gx = std::min<int64_t>(total, (int64_t)1 << 20), gy = (total + gx - 1) / gx;
     SSQ_REQUIRE(gy <= 65535, "stft_adjoint_fused_kernel: %lld items", (long long)total);
-    hipLaunchKernelGGL((stft_adjoint_fused_kernel<L, G, R1, R2, R3>), dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0,
+    hipLaunchKernelGGL((stft_adjoint_fused_kernel<L, G, R1, R2, R3, INV>), dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0,
                        stream, A);
     SSQ_LAUNCH_CHECK();
     return 0;
@@ -788,6 +828,24 @@ static int stft_adjoint_unpad(ssq_stft_plan* pl, const void* ws, void* gx, int64
     return 0;
 }
 
+// the items of stft_adjoint_fused_kernel: frames per item -- what the strip holds, in whole passes of FP frames, fewer
+// where that leaves the chip short of workgroups --, the items of a signal and the strip's length
+static int stft_adjoint_items(StftAdjArgs& A, int L, int FP, int64_t batch) {
+    const int hop = A.hop;
+    int64_t nf = (ADJ_SPAN - L) / hop + 1;
+    if (nf >= FP) {
+        nf = nf / FP * FP;
+        const int64_t want = ((A.n_hops * batch + 1023) / 1024 + FP - 1) / FP * FP;
+        nf = std::max<int64_t>(FP, std::min(nf, want));
+    }
+    nf = std::min(nf, A.n_hops);
+    A.nf = (int)nf;
+    A.n_items = (A.n_hops + nf - 1) / nf;
+    A.span = (int)((nf - 1) * hop + L);
+    SSQ_REQUIRE(A.span <= ADJ_SPAN, "stft adjoint: strip of %d samples", A.span);
+    return 0;
+}
+
 static int stft_adjoint_fused(ssq_stft_plan* pl, const void* gSx, const void* gdSx, void* gx, int64_t batch,
                               hipStream_t stream) {
     const ssq_stft_desc& d = pl->d;
@@ -798,23 +856,12 @@ static int stft_adjoint_fused(ssq_stft_plan* pl, const void* gSx, const void* gd
     A.winA = (const float*)(gSx ? pl->window : pl->diff_window); A.winB = (const float*)pl->diff_window;
     A.ftw = (const c32*)pl->ftw;
     A.n_hops = pl->n_hops; A.rows = pl->rows; A.hop = hop; A.modulated = d.modulated; A.batch = (int)batch;
-    // frames per item: what the strip holds, in whole passes -- fewer where that leaves the chip short of workgroups
-    const int FP = both ? G : 2 * G;
-    int64_t nf = (ADJ_SPAN - L) / hop + 1;
-    if (nf >= FP) {
-        nf = nf / FP * FP;
-        const int64_t want = ((pl->n_hops * batch + 1023) / 1024 + FP - 1) / FP * FP;
-        nf = std::max<int64_t>(FP, std::min(nf, want));
-    }
-    nf = std::min(nf, pl->n_hops);
-    A.nf = (int)nf;
-    A.n_items = (pl->n_hops + nf - 1) / nf;
-    A.span = (int)((nf - 1) * hop + L);
-    SSQ_REQUIRE(A.span <= ADJ_SPAN, "stft adjoint: strip of %d samples", A.span);
+    int rc = stft_adjoint_items(A, L, both ? G : 2 * G, batch);
+    if (rc) return rc;
+    const int64_t nf = A.nf;
     float* ws = nullptr;
     SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
     A.ws = ws;
-    int rc;
     switch (L) {
         case 128: rc = launch_stft_adjoint_fused<128, 32, 16, 8, 1>(A, stream); break;
         case 256: rc = launch_stft_adjoint_fused<256, 16, 16, 16, 1>(A, stream); break;
@@ -855,3 +902,152 @@ extern "C" int ssq_stft_adjoint(ssq_stft_plan* pl, const void* gSx, const void* 
     pl->order.leave(st);
     return rc;
 }
+
+
+// ---- inverse STFT (ssq_istft_batch / ssq_istft_adjoint of ssq_inverse.hip): the fused routes and the composed backward
+namespace ssq {
+
+// e^{2 pi i q / L} for the fused transforms, one table per (device, L), made at first use
+static std::mutex g_tw_mu;
+static std::map<std::pair<int, int>, void*> g_tw;
+static int fused_twiddles(int L, const c32** out) {
+    int dev = 0;
+    SSQ_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_tw_mu);
+    auto it = g_tw.find({dev, L});
+    if (it == g_tw.end()) {
+        std::vector<float> tw((size_t)2 * L);
+        for (int q = 0; q < L; ++q) {
+            const double ang = 2.0 * 3.14159265358979323846 * (double)q / (double)L;
+            tw[2 * q] = (float)cos(ang); tw[2 * q + 1] = (float)sin(ang);
+        }
+        void* d = nullptr;
+        SSQ_CHECK_HIP(hipMalloc(&d, tw.size() * 4));
+        SSQ_CHECK_HIP(hipMemcpy(d, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
+        it = g_tw.emplace(std::make_pair(dev, L), d).first;
+    }
+    *out = (const c32*)it->second;
+    return 0;
+}
+
+int istft_fused(const void* Sx, const void* win_t, const double* wn, void* x, int64_t batch, int64_t n_fft,
+                int64_t n_hops, int64_t hop, int64_t N, int modulated, hipStream_t stream) {
+    const int L = (int)n_fft, G = D_POINTS / L;
+    StftAdjArgs A;
+    A.gA = (const float2*)Sx; A.gB = nullptr; A.winA = (const float*)win_t; A.winB = nullptr;
+    int rc = fused_twiddles(L, &A.ftw);
+    if (rc) return rc;
+    A.n_hops = n_hops; A.rows = L / 2 + 1; A.hop = (int)hop; A.modulated = modulated; A.batch = (int)batch;
+    // (the items are sized as for one signal: a signal's sums then associate the same way in every batch, so that
+    // slice b of a batched result has the bits of the single call)
+    rc = stft_adjoint_items(A, L, 2 * G, 1);
+    if (rc) return rc;
+    float* ws = nullptr;
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
+    A.ws = ws;
+    switch (L) {
+        case 128: rc = launch_stft_adjoint_fused<128, 32, 16, 8, 1, true>(A, stream); break;
+        case 256: rc = launch_stft_adjoint_fused<256, 16, 16, 16, 1, true>(A, stream); break;
+        case 512: rc = launch_stft_adjoint_fused<512, 8, 8, 8, 8, true>(A, stream); break;
+        case 1024: rc = launch_stft_adjoint_fused<1024, 4, 16, 8, 8, true>(A, stream); break;
+        default: rc = launch_stft_adjoint_fused<2048, 2, 16, 16, 8, true>(A, stream); break;
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(istft_finish_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)batch), dim3(256), 0, stream,
+                           (const float*)ws, wn, (float*)x, N, (int64_t)(L / 2), A.n_items, (int64_t)A.nf * hop,
+                           (int64_t)A.span, (n_hops - 1) * hop + L, 1.17549435e-38f);
+        if (hipGetLastError() != hipSuccess) { set_error("istft_finish launch failed"); rc = -3; }
+    }
+    (void)hipFreeAsync(ws, stream);
+    return rc;
+}
+
+int istft_adjoint_fused(const void* u, const void* win_t, void* gSx, int64_t batch, int64_t n_fft, int64_t n_hops,
+                        int64_t hop, int64_t N, int modulated, hipStream_t stream) {
+    const int L = (int)n_fft;
+    StftFusedArgs A{};
+    int rc = fused_twiddles(L, &A.ftw);
+    if (rc) return rc;
+    // the forward kernel over u, zero-extended by L / 2 on the left (the inverse's trim), window^a, no derivative
+    A.window = (const float*)win_t; A.Sx = (float2*)gSx;
+    A.padlen = N + L - 1; A.n_hops = n_hops; A.rows = L / 2 + 1;
+    A.hop = (int)hop; A.s20 = L / 2; A.s21 = L / 2; A.modulated = modulated;
+    A.x = (const float*)u; A.n = (int)N; A.n1 = L / 2; A.padtype = SSQ_PAD_ZERO;
+    SsqParams sp{};
+    switch (L) {
+        case 128: rc = launch_stft_fused<128, 32, 16, 8, 1, true>(A, sp, batch, stream); break;
+        case 256: rc = launch_stft_fused<256, 16, 16, 16, 1, true>(A, sp, batch, stream); break;
+        case 512: rc = launch_stft_fused<512, 8, 8, 8, 8, true>(A, sp, batch, stream); break;
+        case 1024: rc = launch_stft_fused<1024, 4, 16, 8, 8, true>(A, sp, batch, stream); break;
+        default: rc = launch_stft_fused<2048, 2, 16, 16, 8, true>(A, sp, batch, stream); break;
+    }
+    return rc;
+}
+
+// gS[f][c] *= c_f / n_fft; the imaginary parts of DC and (even n_fft) Nyquist are exact zeros
+template <typename T>
+__global__ __launch_bounds__(256) void irfft_adjoint_weights_kernel(T* __restrict__ gS, int64_t rows, int64_t n_hops,
+                                                                    int even, T inv_n) {
+    const int64_t total = rows * n_hops;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t f = t / n_hops;
+        const bool edge = f == 0 || (even && f == rows - 1);
+        const T c = edge ? inv_n : T(2) * inv_n;
+        gS[2 * t] = gS[2 * t] * c;
+        gS[2 * t + 1] = edge ? T(0) : gS[2 * t + 1] * c;
+    }
+}
+
+static std::mutex g_iadj_mu;
+static std::map<std::tuple<int, int64_t, int64_t, hipStream_t>, StridedR2C> g_iadj_plans;      // one work buffer per stream
+
+template <typename T>
+static int istft_adjoint_composed_t(int dtype, const void* upad, const void* win_t, void* gSx, int64_t batch,
+                                    int64_t n_fft, int64_t n_hops, int64_t hop, int64_t ulen, int modulated,
+                                    hipStream_t stream) {
+    const int64_t rows = n_fft / 2 + 1, total = n_fft * n_hops;
+    const int64_t s20 = (n_fft + 1) / 2, s21 = n_fft / 2;
+    T* frames = nullptr;
+    SSQ_CHECK_HIP(hipMallocAsync((void**)&frames, (size_t)total * sizeof(T), stream));
+    const unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+    const unsigned g2 = (unsigned)std::min<int64_t>((rows * n_hops + 255) / 256, 8192);
+    int rc = 0;
+    for (int64_t b = 0; b < batch && !rc; ++b) {
+        hipLaunchKernelGGL((frame_window_kernel<T>), dim3(g), dim3(256), 0, stream, (const T*)upad + (size_t)b * ulen,
+                           (const T*)win_t, (const T*)nullptr, frames, (T*)nullptr, n_fft, n_hops, hop, s20, s21, modulated);
+        if (hipGetLastError() != hipSuccess) { set_error("frame_window launch failed"); rc = -3; break; }
+        T* out = (T*)gSx + (size_t)b * rows * n_hops * 2;
+        {
+            std::lock_guard<std::mutex> lock(g_iadj_mu);          // held until the transform is enqueued
+            auto key = std::make_tuple(dtype, n_fft, n_hops, stream);
+            if (g_iadj_plans.size() >= 16 && !g_iadj_plans.count(key)) {
+                (void)hipDeviceSynchronize();
+                for (auto& kv : g_iadj_plans) kv.second.destroy();
+                g_iadj_plans.clear();
+            }
+            auto it = g_iadj_plans.find(key);
+            if (it == g_iadj_plans.end()) {
+                StridedR2C f;
+                rc = f.create(dtype, (size_t)n_fft, (size_t)n_hops);
+                if (rc) break;
+                it = g_iadj_plans.emplace(key, f).first;
+            }
+            rc = it->second.execute(frames, out, stream);
+        }
+        if (rc) break;
+        hipLaunchKernelGGL((irfft_adjoint_weights_kernel<T>), dim3(g2), dim3(256), 0, stream, out, rows, n_hops,
+                           (int)(n_fft % 2 == 0), (T)(T(1) / (T)n_fft));
+        if (hipGetLastError() != hipSuccess) { set_error("irfft_adjoint_weights launch failed"); rc = -3; }
+    }
+    (void)hipFreeAsync(frames, stream);
+    return rc;
+}
+
+int istft_adjoint_composed(int dtype, const void* upad, const void* win_t, void* gSx, int64_t batch, int64_t n_fft,
+                           int64_t n_hops, int64_t hop, int64_t ulen, int modulated, hipStream_t stream) {
+    if (dtype == SSQ_F32)
+        return istft_adjoint_composed_t<float>(dtype, upad, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated, stream);
+    return istft_adjoint_composed_t<double>(dtype, upad, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated, stream);
+}
+
+}  // namespace ssq
