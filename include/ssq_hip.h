@@ -16,6 +16,20 @@
  *              (re, im) pairs of it (what torch.view_as_real gives, algos.py:61-64).
  *   layouts    2-D arrays are row-major (rows = scales / frequency bins,
  *              cols = time); batched arrays put the signal index first.
+ *   pointers   every array is dense in the stated order: no strides, no padding between
+ *              rows or signals, and the pointer addresses the values themselves (a host
+ *              framework's lazy conjugate / negative / broadcast view must be
+ *              materialised first). A pointer needs only the alignment of its element:
+ *              4 / 8 bytes for real SSQ_F32 / SSQ_F64 data, 8 / 16 bytes for a complex
+ *              (re, im) pair, 4 for int32 -- `buf + 1` of an allocation is as good as
+ *              `buf`. Kernels that move 16 bytes at a time declare the lower alignment
+ *              on the access or test the address and take narrower accesses.
+ *   aliasing   no output may overlap an input or another output of the same call. The
+ *              exceptions are stated at the entry point: ssq_replace_under_abs works in
+ *              place on `w`, ssq_icwt2 uses `Wp` as its workspace and overwrites it,
+ *              and ssq_ssqueeze_adjoint with `accumulate` adds to `gWx`. In particular
+ *              the reassignments scatter: `Tx` must not be `Wx`, `dWx` or `w`, and a
+ *              gradient output must not be the incoming gradient.
  *   ownership  the caller owns every I/O buffer (device memory); plans own their
  *              FFT plans, workspace and the device copy of the filter bank.
  *   threading  one plan per host thread / stream at a time; plans are immutable

@@ -40,7 +40,10 @@ def stream():
 
 
 def to_device(x, dtype=None):
-    """NumPy array / torch tensor -> contiguous torch tensor on the current GPU."""
+    """NumPy array / torch tensor -> contiguous torch tensor on the current GPU whose storage
+    holds the values `x` denotes: a lazy conjugate / negative (`x.conj()`, `x.conj().imag`) is
+    materialised -- `.contiguous()` alone keeps the bit, and `data_ptr()` then addresses the
+    unconjugated values. Differentiable; a plain contiguous device tensor is returned as it is."""
     dev = device()
     if isinstance(x, np.ndarray):
         if not x.flags.c_contiguous:
@@ -50,7 +53,14 @@ def to_device(x, dtype=None):
         raise TypeError("expected numpy array or torch Tensor (got %s)" % type(x))
     if dtype is not None and x.dtype != dtype:
         x = x.to(dtype)
-    return x.to(dev).contiguous()
+    return x.to(dev).resolve_conj().resolve_neg().contiguous()
+
+
+def _check_out(out, like):
+    """An `out=` argument is written through its raw pointer as a dense array of `like`'s shape."""
+    if not (isinstance(out, torch.Tensor) and out.shape == like.shape and out.dtype == like.dtype
+            and out.is_cuda and out.is_contiguous() and not out.is_conj()):
+        raise ValueError("`out` must be a contiguous GPU tensor of `Wx`'s shape and dtype")
 
 
 def ones_like(x):
@@ -118,8 +128,8 @@ def ssqueeze_fast(Wx, dWx, ssq_freqs, const, logscale=False, flipud=False,
     B, na, n = _shape3(Wx)
     if out is None:
         out = torch.empty_like(Wx)
-    elif out.shape != Wx.shape or out.dtype != Wx.dtype or not out.is_cuda:
-        raise ValueError("`out` must be a GPU tensor of `Wx`'s shape and dtype")
+    else:
+        _check_out(out, Wx)
     cst, c64 = _const_vector(const, na, Wx.dtype)
     kind, p = _grid(ssq_freqs, logscale)
     sfs = None
@@ -159,9 +169,8 @@ def ssqueeze_adjoint(Wx, dWx, gTx, ssq_freqs, const, logscale=False, flipud=Fals
         if accumulate:
             raise ValueError("`accumulate=True` needs `out`")
         out = torch.empty_like(Wx)
-    elif (out.shape != Wx.shape or out.dtype != Wx.dtype or not out.is_cuda
-          or not out.is_contiguous()):
-        raise ValueError("`out` must be a contiguous GPU tensor of `Wx`'s shape and dtype")
+    else:
+        _check_out(out, Wx)
     cst, c64 = _const_vector(const, na, Wx.dtype)
     kind, p = _grid(ssq_freqs, logscale)
     sfs = None
@@ -185,6 +194,8 @@ def indexed_sum_onfly(Wx, w, ssq_freqs, const=1, logscale=False, flipud=False,
     B, na, n = _shape3(Wx)
     if out is None:
         out = torch.empty_like(Wx)
+    else:
+        _check_out(out, Wx)
     cst, c64 = _const_vector(const, na, Wx.dtype)
     kind, p = _grid(ssq_freqs, logscale)
     check(lib.ssq_indexed_sum(_CDT[Wx.dtype], _ptr(Wx), _ptr(w), _ptr(out),
