@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 107 (106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 108 (107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -328,6 +328,20 @@ int  ssq_cwt_plan_set_ssq(ssq_cwt_plan* plan, int grid, const double* params,
  * get_w=True in the reference). */
 int  ssq_cwt_execute(ssq_cwt_plan* plan, const void* x, int64_t batch, void* Wx,
                      void* dWx, void* Tx, void* w, int rpadded, void* stream);
+/* Adjoint of the plan's CWT (ABI 108; the gradient of a real loss w.r.t. the real input, torch's convention
+ * gx = Re(A^H g)):
+ * gx (batch, n) real  <-  gWx, gdWx (batch, na, n) complex, (batch, na, m) with `rpadded` != 0; either may be NULL (not
+ * both). With F_a = fft_m(U gWx_a), G_a = fft_m(U gdWx_a) -- U puts the n columns at offset n1 of a zero row of length
+ * m, the identity with `rpadded` --
+ *   gx = pad^T Re ifft_m( sum_a s_a psi_a[k] (F_a[k] - i m_k G_a[k]) )
+ * psi_a: row a of the banded bank (zero outside its band), s_a: row_scale (1 when NULL), m_k: the forward's derivative
+ * multiplier (xi_k / dt in the plan dtype), ifft_m normalised by 1 / m, pad^T: every sample receives the sum of its
+ * padded copies (zero padding contributes nothing). gx is overwritten; the same input gives the same bits, alone or in
+ * any batch. Rows go through the product workspace of the exact forward path in the same chunks (allocated at the
+ * first call that needs it), batched rocFFT row transforms, one kernel that reads the banded bank and skips the rows
+ * whose band does not reach a bin, one inverse transform per signal and an unpadding pass. batch in [1, max_batch]. */
+int  ssq_cwt_adjoint(ssq_cwt_plan* plan, const void* gWx, const void* gdWx, void* gx,
+                     int64_t batch, int rpadded, void* stream);
 
 /* Optional fast path ("overlap-save zoom" iFFT, float32 or float64, power-of-two m,
  * analytic bank): tables planned on the host (ssqueezepy_amd/_blocks.py documents the

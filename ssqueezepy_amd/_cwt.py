@@ -72,7 +72,7 @@ class CwtPlan():
         desc.algo = int(algo)
         self._h = ctypes.c_void_p()
         check(self.lib.ssq_cwt_plan_create(ctypes.byref(self._h), ctypes.byref(desc)))
-        self._bank = (vals, off, lo, row_scale)     # host copy: dense rows for `backward`
+        self._bank = (vals, off, lo, row_scale)     # host copy: `dense_bank`
         self._psih_dev = None
         self._pad_src = None
         self._pad_seg = None
@@ -309,6 +309,8 @@ class CwtPlan():
 
 
     # ---- adjoint (autograd) -------------------------------------------------------------
+    # (`dense_bank`, `pad_sources`, `pad_segments`: the plan's linear map spelled out for tests and tools;
+    # `adjoint` itself needs none of them)
     def dense_bank(self, device):
         """(na, M) real: the rows the plan applies (band-limited, Nyquist-halved, times
         sqrt(scale) when L2-normalised), on `device`."""
@@ -349,52 +351,54 @@ class CwtPlan():
             self._pad_seg = (torch.from_numpy(order).to(device), torch.from_numpy(counts).to(device))
         return self._pad_seg
 
-    def adjoint(self, gW, rpadded=False):
-        """Gradient w.r.t. the real input of a real loss whose gradient w.r.t. `Wx` is `gW`
-        ((na, N) / (B, na, N), or padded width if `rpadded`): with A = unpad . ifft . diag(psih)
-        . fft . pad, ``Re(A^H gW)`` = pad^T Re ifft(sum_a psih_a fft(zero-extended gW_a)) -- the
-        double-integral inverse's kernel (`ssq_icwt2`) followed by the adjoint of the signal
-        extension."""
+    def adjoint(self, gW=None, gdW=None, rpadded=False):
+        """Gradient w.r.t. the real input of a real loss whose gradients w.r.t. `Wx`, `dWx` are
+        `gW`, `gdW` (``(na, N)`` / ``(B, na, N)``, or padded width if `rpadded`; either may be
+        None): ``Re(A^H g)``, the plan's `ssq_cwt_adjoint` in one call for the whole batch --
+        ``pad^T Re ifft(sum_a psih_a (fft(U gW_a) - 1j * xi / dt * fft(U gdW_a)))``, `U` the zero
+        extension to the padded length, `pad^T` the transpose of the signal extension. It reads
+        the plan's banded bank (no dense one is built). Deterministic."""
+        g0 = gW if gW is not None else gdW
+        if g0 is None:
+            raise ValueError("`gW` and `gdW` are both None")
+        batched = g0.ndim == 3
+        B = g0.shape[0] if batched else 1
+        if B > self.max_batch:
+            raise ValueError("batch %d exceeds the plan's max_batch %d" % (B, self.max_batch))
         cdt, rdt = _CDT[self.dtype], _TDT[self.dtype]
-        batched = gW.ndim == 3
-        g3 = gW if batched else gW[None]
-        dev = g3.device
-        psih = self.dense_bank(dev)
-        order, counts = self.pad_segments(dev)
-        code = F32 if self.dtype == 'float32' else F64
-        out = torch.zeros((g3.shape[0], self.N), dtype=rdt, device=dev)
-        v = torch.empty(self.M, dtype=rdt, device=dev)
-        for b in range(g3.shape[0]):
-            if rpadded:
-                Gp = g3[b].to(cdt).contiguous().clone()
-            else:
-                Gp = torch.zeros((self.na, self.M), dtype=cdt, device=dev)
-                Gp[:, self.n1:self.n1 + self.N] = g3[b]
-            check(self.lib.ssq_icwt2(code, Gp.data_ptr(), psih.data_ptr(), v.data_ptr(),
-                                     self.na, self.M, algos.stream()))
-            # (a segmented sum, not `index_add_`: that one adds with atomics, in arrival order, and a
-            # sample with three padded copies then differs in its last bit from call to call)
-            out[b] = torch.segment_reduce(v[order], 'sum', lengths=counts)
-        return out if batched else out[0]
+        cols = self.M if rpadded else self.N
+        shape = (B, self.na, cols) if batched else (self.na, cols)
+        gs = []
+        for g in (gW, gdW):
+            if g is not None:
+                if tuple(g.shape) != shape:
+                    raise ValueError("gradient of shape %s, transform of shape %s"
+                                     % (tuple(g.shape), shape))
+                g = g.to(cdt).resolve_conj().contiguous()
+            gs.append(g)
+        gx = torch.empty((B, self.N) if batched else (self.N,), dtype=rdt, device=g0.device)
+        check(self.lib.ssq_cwt_adjoint(self._h, algos._ptr(gs[0]), algos._ptr(gs[1]),
+                                       gx.data_ptr(), B, int(bool(rpadded)), algos.stream()))
+        return gx
 
 
 class _CwtFunction(torch.autograd.Function):
-    """`Wx = plan(x)` with a backward through `Wx` (`dWx`, when requested, carries no
-    gradient), so that `cwt` of a tensor that requires grad is differentiable as in the
-    reference's GPU mode (examples/reconstruction.py:1-70)."""
+    """`Wx[, dWx] = plan(x)` with a backward through both (`CwtPlan.adjoint`), so that `cwt` of
+    a tensor that requires grad is differentiable as in the reference's GPU mode
+    (examples/reconstruction.py:1-70)."""
 
     @staticmethod
     def forward(ctx, x, plan, want_dWx, rpadded):
         out = plan.execute(x.detach(), want_dWx=want_dWx, rpadded=rpadded)
         ctx.plan, ctx.rpadded = plan, rpadded
-        if want_dWx:
-            ctx.mark_non_differentiable(out['dWx'])
-            return out['Wx'], out['dWx']
-        return out['Wx']
+        ctx.set_materialize_grads(False)
+        return (out['Wx'], out['dWx']) if want_dWx else out['Wx']
 
     @staticmethod
-    def backward(ctx, gW, *unused):
-        return ctx.plan.adjoint(gW, ctx.rpadded), None, None, None
+    def backward(ctx, gW, gdW=None):
+        if gW is None and gdW is None:
+            return None, None, None, None
+        return ctx.plan.adjoint(gW, gdW, ctx.rpadded), None, None, None
 
 
 _PLAN_CACHE = {}
@@ -482,7 +486,8 @@ def cwt(x, wavelet='gmw', scales='log-piecewise', fs=None, t=None, nv=32,
 
     Returns ``(Wx, scales)`` or ``(Wx, scales, dWx)``; `Wx` is ``(na, N)``
     (``(B, na, N)`` for batched input), `scales` a NumPy vector in the wavelet
-    dtype. `vectorized`, `patience` are accepted and ignored (the device path has
+    dtype. For a tensor `x` that requires grad, `Wx` and `dWx` both carry a
+    `grad_fn` (`CwtPlan.adjoint`). `vectorized`, `patience` are accepted and ignored (the device path has
     one execution strategy); `cache_wavelet=False` bypasses the plan cache.
     `order > 0` / a tuple of orders: see `cwt_higher_order`.
     """

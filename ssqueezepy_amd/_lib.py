@@ -127,6 +127,7 @@ _PROTOS = {
                                      c_int, c_int, c_double]),
     'ssq_cwt_execute': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_int, c_void_p]),
+    'ssq_cwt_adjoint': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     'ssq_cwt_plan_set_blocks': (c_int, [c_void_p, POINTER(CwtBlocksDesc)]),
     'ssq_cwt_plan_set_tiles': (c_int, [c_void_p, POINTER(CwtTilesDesc)]),
     'ssq_cwt_plan_timing': (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_int64)]),
@@ -155,7 +156,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 107     # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 108     # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

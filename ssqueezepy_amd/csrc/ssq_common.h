@@ -195,6 +195,38 @@ struct WeightVersions {
     void destroy() { for (void* p : bufs) (void)hipFree(p); bufs.clear(); }
 };
 
+// The transpose of a signal extension, for the adjoints (ssq_stft_adjoint, ssq_cwt_adjoint): the padded positions
+// p in [0, m) that copy signal sample j -- position p reads sample p - n1 through the rule of pad_kernel --, per j,
+// ascending: `idx[off[j] .. off[j + 1])`. Zero padding has no source and is left out. m < 2^31.
+static inline void inverse_pad_table(int64_t n, int64_t m, int64_t n1, int padtype, std::vector<int32_t>& off,
+                                     std::vector<int32_t>& idx) {
+    auto source = [&](int64_t t) -> int64_t {
+        if (t >= 0 && t < n) return t;
+        switch (padtype) {
+            case SSQ_PAD_REFLECT: {
+                if (n == 1) return 0;
+                const int64_t period = 2 * (n - 1);
+                int64_t q = t % period; if (q < 0) q += period;
+                return q < n ? q : period - q;
+            }
+            case SSQ_PAD_SYMMETRIC: {
+                const int64_t period = 2 * n;
+                int64_t q = t % period; if (q < 0) q += period;
+                return q < n ? q : period - 1 - q;
+            }
+            case SSQ_PAD_REPLICATE: return t < 0 ? 0 : n - 1;
+            case SSQ_PAD_WRAP: { int64_t q = t % n; if (q < 0) q += n; return q; }
+            default: return -1;
+        }
+    };
+    off.assign((size_t)n + 1, 0);
+    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) ++off[(size_t)j + 1]; }
+    for (int64_t j = 0; j < n; ++j) off[(size_t)j + 1] += off[(size_t)j];
+    idx.assign((size_t)off[(size_t)n], 0);
+    std::vector<int32_t> fill(off.begin(), off.end() - 1);
+    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) idx[(size_t)fill[(size_t)j]++] = (int32_t)p; }
+}
+
 template <typename T> struct cplx { T re, im; };
 
 // reassignment parameters as the kernels consume them

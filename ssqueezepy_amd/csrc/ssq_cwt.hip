@@ -16,6 +16,7 @@
 //     --rocFFT C2C inverse, batched, scaled 1/M, in place--> padded Wx, dWx
 //     --cwt_epilogue_kernel--> Wx[:, n1:n1+N] (+ dWx / w / bin map)
 //   without the tile path: bin map or w --accumulate kernels (ssq_kernels.hip)--> Tx
+// The backward pass (ssq_cwt_adjoint: gWx, gdWx -> gx) is at the end of the file.
 // Only the returned arrays (Wx, Tx [, dWx, w]) are written at full size; padded intermediates
 // live in plan-owned workspaces reused chunk after chunk.
 //
@@ -164,6 +165,11 @@ struct ssq_cwt_plan {
     TilePlan* tile = nullptr;             // column-tile path of the fused ssq form (ssq_cwt_tiles.hip)
     bool executed = false;
     unsigned short* kdump = nullptr;      // diagnostic (ssq_cwt_plan_set_bin_dump): caller-owned (batch, na, n) bin map
+    // the adjoint (ssq_cwt_adjoint), built at its first call: the spectrum sums (max_batch, m) complex, the inverse
+    // pad map, the rows that reach each segment of ADJ_SEG bins, and the row transforms keyed by their count
+    void* adj_spec = nullptr;
+    int32_t* adj_off = nullptr; int32_t* adj_idx = nullptr; int32_t* adj_seg = nullptr;
+    std::map<int64_t, FftPlan> adj_fwd;
     // optional per-stage HIP-event timing (bench.py reads it): 0 = pad + forward FFT +
     // block spectra, 1 = block rows, 2 = exact / generic rows, 3 = reassignment
     bool timing = false;
@@ -258,13 +264,14 @@ void ssq_cwt_plan_destroy(ssq_cwt_plan* pl) {
     if (!pl) return;
     pl->fwd.destroy();
     for (auto& kv : pl->inv) kv.second.destroy();
+    for (auto& kv : pl->adj_fwd) kv.second.destroy();
     if (pl->blk) { pl->blk->destroy(); delete pl->blk; }
     if (pl->tile) { pl->tile->destroy(); delete pl->tile; }
     for (hipEvent_t e : pl->tev) (void)hipEventDestroy(e);
     pl->weights.destroy();
     pl->order.destroy();
     void* ptrs[] = {pl->bank, pl->band_off, pl->band_lo, pl->row_scale, pl->xp, pl->xh, pl->prod,
-                    pl->kidx, pl->gen_rows, pl->all_rows};
+                    pl->kidx, pl->gen_rows, pl->all_rows, pl->adj_spec, pl->adj_off, pl->adj_idx, pl->adj_seg};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete pl;
 }
@@ -604,3 +611,229 @@ int ssq_cwt_execute(ssq_cwt_plan* pl, const void* x, int64_t batch, void* Wx, vo
 }
 
 }  // extern "C"
+
+// ---- adjoint of the plan's CWT (ssq_cwt_adjoint): gWx, gdWx -> gx --------------------------------------------------
+// With F_a = fft_M(U gWx_a), G_a = fft_M(U gdWx_a) (U: the n columns at offset n1 of a zero row of length M):
+//   gx = pad^T Re ifft_M( sum_a s_a psi_a[k] (F_a[k] - i m_k G_a[k]) )
+// Per signal and pass of rows (the forward's rows_chunk cut to ADJ_PASS_BYTES, in the forward's product workspace):
+//   gWx, gdWx --cwt_adjoint_stage_kernel--> zero-extended rows --rocFFT C2C forward, batched, in place-->
+//   --cwt_adjoint_mac_kernel--> the signal's spectrum sum (adds to what the earlier passes left)
+// then for the whole batch: rocFFT C2C inverse (1/M) of the spectrum sums --cwt_adjoint_unpad_kernel--> gx.
+// Every sum has one order (rows ascending per bin, padded positions ascending per sample): the same input gives the same
+// bits, whatever the batch.
+namespace ssq {
+
+constexpr int ADJ_SEG = 512;       // bins per entry of the row-range table (a multiple of a workgroup's bins)
+constexpr size_t ADJ_PASS_BYTES = (size_t)128 << 20;   // rows staged, transformed and summed per pass
+
+// ws[r][p][k] = g_p[row0 + r][k - col0] for col0 <= k < col0 + cols, else 0: a work-item writes V bins, 16 bytes a store
+// (V = 2 complex64 / 1 complex128; V = 1 with 8-byte stores for complex64 rows of an odd length M)
+template <typename T, int V>
+__global__ __launch_bounds__(256) void cwt_adjoint_stage_kernel(const T* __restrict__ g0, const T* __restrict__ g1,
+                                                                T* __restrict__ ws, int64_t M, int64_t cols, int64_t col0,
+                                                                int64_t row0, int nplanes) {
+    typedef T vec_t __attribute__((ext_vector_type(2 * V)));
+    typedef T cx_t __attribute__((ext_vector_type(2)));
+    const int64_t r = blockIdx.y;
+    const int p = blockIdx.z;
+    const T* g = (p ? g1 : g0) + 2 * (row0 + r) * cols;
+    T* o = ws + 2 * ((r * nplanes + p) * M);
+    for (int64_t k = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V; k < M;
+         k += (int64_t)gridDim.x * blockDim.x * V) {                 // (V == 2 only where M is even: k + 1 < M)
+        vec_t out;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int64_t j = k + v - col0;
+            cx_t c = {T(0), T(0)};
+            if (j >= 0 && j < cols) c = *reinterpret_cast<const cx_t*>(g + 2 * j);
+            out[2 * v] = c[0]; out[2 * v + 1] = c[1];
+        }
+        *reinterpret_cast<vec_t*>(o + 2 * k) = out;
+    }
+}
+
+// S[k] += sum over the rows a of the chunk whose band holds k, ascending, of s_a psi_a[k] (F_a[k] - i m_k G_a[k]).
+// A work-item owns V neighbouring bins; `seg` holds, per ADJ_SEG bins, the first row and one past the last row whose
+// band reaches the segment: a workgroup walks only those, and one whose segment no row of the chunk reaches -- every
+// bin above M/2 of an analytic bank -- returns without reading anything. F, G: planes of the workspace
+// [rows][planes][M], 16 bytes a load where V == 2; the bank is the plan's banded one.
+template <typename T, int V, bool HAS_F, bool HAS_G>
+__global__ __launch_bounds__(256) void cwt_adjoint_mac_kernel(
+    const T* __restrict__ ws, const T* __restrict__ bank, const int64_t* __restrict__ band_off,
+    const int32_t* __restrict__ band_lo, const T* __restrict__ row_scale, const int32_t* __restrict__ seg,
+    T* __restrict__ S, int64_t M, int64_t row0, int64_t rows, double h, T inv_dt) {
+    typedef T vec_t __attribute__((ext_vector_type(2 * V)));
+    constexpr int NP = (HAS_F ? 1 : 0) + (HAS_G ? 1 : 0);
+    const int64_t kb = (int64_t)blockIdx.x * blockDim.x * V;        // first bin of the workgroup
+    const int64_t sg = kb / ADJ_SEG;
+    const int64_t s_lo = seg[2 * sg], s_hi = seg[2 * sg + 1];
+    const int64_t a_lo = s_lo > row0 ? s_lo : row0, a_hi = s_hi < row0 + rows ? s_hi : row0 + rows;
+    const int64_t k0 = kb + (int64_t)threadIdx.x * V;
+    if (a_lo >= a_hi || k0 >= M) return;
+    T mk[V], re[V], im[V];
+    vec_t acc = *reinterpret_cast<const vec_t*>(S + 2 * k0);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        // the forward's derivative multiplier, as bank_multiply_kernel forms it
+        const int64_t k = k0 + v, ks = k <= M / 2 ? k : k - M;
+        mk[v] = (T)((double)ks * h) * inv_dt;
+        re[v] = acc[2 * v]; im[v] = acc[2 * v + 1];
+    }
+#pragma unroll 4
+    for (int64_t a = a_lo; a < a_hi; ++a) {
+        const int64_t lo = band_lo[a], off = band_off[a], len = band_off[a + 1] - off;
+        if (len <= 0) continue;
+        const T* P = ws + 2 * ((a - row0) * NP * M + k0);
+        vec_t f, g;
+        if (HAS_F) f = *reinterpret_cast<const vec_t*>(P);
+        if (HAS_G) g = *reinterpret_cast<const vec_t*>(P + (HAS_F ? 2 * M : 0));
+        const T s = row_scale ? row_scale[a] : T(1);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const int64_t t = k0 + v - lo;
+            const bool in = t >= 0 && t < len;
+            T c = bank[off + (t < 0 ? 0 : (t < len ? t : len - 1))];
+            if (row_scale) c = c * s;
+            T tr = T(0), ti = T(0);
+            if (HAS_F) { tr = f[2 * v]; ti = f[2 * v + 1]; }
+            if (HAS_G) {                     // -i m (gr + i gi) = m gi - i m gr
+                const T dr = mk[v] * g[2 * v + 1], di = -(mk[v] * g[2 * v]);
+                tr = HAS_F ? tr + dr : dr; ti = HAS_F ? ti + di : di;
+            }
+            if (in) { re[v] = re[v] + c * tr; im[v] = im[v] + c * ti; }
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) { acc[2 * v] = re[v]; acc[2 * v + 1] = im[v]; }
+    *reinterpret_cast<vec_t*>(S + 2 * k0) = acc;
+}
+
+// gx[b][j] = sum over the padded positions p that copy sample j, ascending, of Re S[b][p]
+template <typename T>
+__global__ __launch_bounds__(256) void cwt_adjoint_unpad_kernel(const T* __restrict__ S, T* __restrict__ gx,
+                                                                const int32_t* __restrict__ off,
+                                                                const int32_t* __restrict__ idx, int64_t n, int64_t M) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const T* s = S + 2 * (int64_t)blockIdx.y * M;
+    T acc = T(0);
+    for (int32_t e = off[j]; e < off[j + 1]; ++e) acc = acc + s[2 * (int64_t)idx[e]];
+    gx[(int64_t)blockIdx.y * n + j] = acc;
+}
+
+}  // namespace ssq
+
+// the adjoint's tables and its spectrum buffer, at the first call
+static int cwt_adjoint_setup(ssq_cwt_plan* pl) {
+    if (pl->adj_spec) return 0;
+    const ssq_cwt_desc& d = pl->d;
+    SSQ_REQUIRE(d.m < ((int64_t)1 << 31), "cwt adjoint: padded length %lld", (long long)d.m);
+    std::vector<int32_t> off, idx;
+    inverse_pad_table(d.n, d.m, d.n1, d.padtype, off, idx);
+    const int64_t nseg = (d.m + ADJ_SEG - 1) / ADJ_SEG;
+    std::vector<int32_t> seg((size_t)(2 * nseg), 0);
+    for (int64_t a = 0; a < d.na; ++a) {
+        const int64_t lo = pl->h_band_lo[(size_t)a], len = pl->h_band_off[(size_t)a + 1] - pl->h_band_off[(size_t)a];
+        if (len <= 0) continue;
+        for (int64_t s = lo / ADJ_SEG; s <= (lo + len - 1) / ADJ_SEG; ++s) {
+            int32_t* e = &seg[(size_t)(2 * s)];
+            if (e[1] == 0) { e[0] = (int32_t)a; e[1] = (int32_t)a + 1; }
+            else { e[0] = std::min(e[0], (int32_t)a); e[1] = std::max(e[1], (int32_t)a + 1); }
+        }
+    }
+    int rc = dev_alloc((void**)&pl->adj_off, off.size() * 4, pl->bytes);
+    if (!rc) rc = dev_alloc((void**)&pl->adj_idx, idx.size() * 4, pl->bytes);
+    if (!rc) rc = dev_alloc((void**)&pl->adj_seg, seg.size() * 4, pl->bytes);
+    if (!rc) rc = h2d(pl->adj_off, off.data(), off.size() * 4);
+    if (!rc && !idx.empty()) rc = h2d(pl->adj_idx, idx.data(), idx.size() * 4);
+    if (!rc) rc = h2d(pl->adj_seg, seg.data(), seg.size() * 4);
+    if (!rc) rc = dev_alloc(&pl->adj_spec, (size_t)d.max_batch * d.m * pl->csize(), pl->bytes);
+    return rc;
+}
+
+static int cwt_adjoint_fft(ssq_cwt_plan* pl, std::map<int64_t, FftPlan>& plans, int kind, int64_t count, double scale,
+                           void* data, hipStream_t stream) {
+    auto it = plans.find(count);
+    if (it == plans.end()) {
+        FftPlan fp;
+        int rc = fp.create(kind, pl->d.dtype, (size_t)pl->d.m, (size_t)count, scale);
+        if (rc) return rc;
+        pl->bytes += (int64_t)fp.work_bytes;
+        it = plans.emplace(count, fp).first;
+    }
+    return it->second.execute(data, nullptr, stream);
+}
+
+template <typename T, int V>
+static int cwt_adjoint_t(ssq_cwt_plan* pl, const void* gWx, const void* gdWx, void* gx, int64_t batch, int rpadded,
+                         hipStream_t stream) {
+    const ssq_cwt_desc& d = pl->d;
+    const int64_t M = d.m, N = d.n, na = d.na;
+    const int64_t cols = rpadded ? M : N, col0 = rpadded ? 0 : d.n1;
+    const int nplanes = (gWx ? 1 : 0) + (gdWx ? 1 : 0);
+    const double h = (2.0 * 3.141592653589793) / (double)M;
+    const T inv_dt = T(1) / (T)d.dt;
+    if (!pl->prod) {
+        SSQ_CHECK_HIP(hipMalloc(&pl->prod, pl->prod_bytes ? pl->prod_bytes : 1));
+        pl->bytes += (int64_t)pl->prod_bytes;
+    }
+    T* ws = (T*)pl->prod;
+    // rows per pass: the forward's chunk, cut to ADJ_PASS_BYTES of rows (two planes each) -- rocFFT's own work area
+    // is as large as what it transforms in one call, and a pass of this size is still in the Infinity Cache when the
+    // next kernel reads it
+    // (measured at N = 160 000, 300 scales, one signal, gWx alone / with gdWx: 32 MiB 1.80 / 2.78 ms, 128 MiB 1.34 / 2.39,
+    // 512 MiB 1.35 / 2.68, all rows at once 1.34 / 3.07)
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(pl->rows_chunk,
+                                                                 (int64_t)(ADJ_PASS_BYTES / ((size_t)4 * M * sizeof(T)))));
+    SSQ_CHECK_HIP(hipMemsetAsync(pl->adj_spec, 0, (size_t)batch * M * 2 * sizeof(T), stream));
+    const unsigned sx = (unsigned)std::min<int64_t>((M + 256 * V - 1) / (256 * V), 4096);
+    const unsigned mx = (unsigned)((M + 256 * V - 1) / (256 * V));
+    for (int64_t b = 0; b < batch; ++b) {
+        const T* g0 = (const T*)(gWx ? gWx : gdWx) + (size_t)b * na * cols * 2;
+        const T* g1 = (gWx && gdWx) ? (const T*)gdWx + (size_t)b * na * cols * 2 : nullptr;
+        T* S = (T*)pl->adj_spec + (size_t)b * M * 2;
+        // (the workspace holds two planes per row of the chunk: whichever gradients are given fit)
+        for (int64_t row0 = 0; row0 < na; row0 += chunk) {
+            const int64_t rows = std::min(chunk, na - row0);
+            hipLaunchKernelGGL((cwt_adjoint_stage_kernel<T, V>), dim3(sx, (unsigned)rows, (unsigned)nplanes), dim3(256), 0,
+                               stream, g0, g1, ws, M, cols, col0, row0, nplanes);
+            SSQ_LAUNCH_CHECK();
+            int rc = cwt_adjoint_fft(pl, pl->adj_fwd, 2, rows * nplanes, 1.0, ws, stream);
+            if (rc) return rc;
+#define SSQ_MAC(F, G) hipLaunchKernelGGL((cwt_adjoint_mac_kernel<T, V, F, G>), dim3(mx), dim3(256), 0, stream,           \
+                                         (const T*)ws, (const T*)pl->bank, pl->band_off, pl->band_lo,                      \
+                                         (const T*)pl->row_scale, (const int32_t*)pl->adj_seg, S, M, row0, rows, h, inv_dt)
+            if (gWx && gdWx) SSQ_MAC(true, true);
+            else if (gWx) SSQ_MAC(true, false);
+            else SSQ_MAC(false, true);
+#undef SSQ_MAC
+            SSQ_LAUNCH_CHECK();
+        }
+    }
+    int rc = cwt_adjoint_fft(pl, pl->inv, 1, batch, 1.0 / (double)M, pl->adj_spec, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cwt_adjoint_unpad_kernel<T>), dim3((unsigned)((N + 255) / 256), (unsigned)batch), dim3(256), 0,
+                       stream, (const T*)pl->adj_spec, (T*)gx, (const int32_t*)pl->adj_off, (const int32_t*)pl->adj_idx,
+                       N, M);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ssq_cwt_adjoint(ssq_cwt_plan* pl, const void* gWx, const void* gdWx, void* gx, int64_t batch,
+                               int rpadded, void* stream) {
+    SSQ_REQUIRE(pl && gx, "ssq_cwt_adjoint: null pointer");
+    SSQ_REQUIRE(gWx || gdWx, "ssq_cwt_adjoint: gWx and gdWx are both null");
+    SSQ_REQUIRE(batch >= 1 && batch <= pl->d.max_batch, "batch %lld outside [1, %lld]",
+                (long long)batch, (long long)pl->d.max_batch);
+    SSQ_REQUIRE(batch <= 65535, "ssq_cwt_adjoint: batch %lld > 65535", (long long)batch);
+    hipStream_t st = as_stream(stream);
+    pl->order.enter(st);
+    int rc = cwt_adjoint_setup(pl);
+    if (!rc) {
+        if (pl->d.dtype == SSQ_F64) rc = cwt_adjoint_t<double, 1>(pl, gWx, gdWx, gx, batch, rpadded, st);
+        else if (pl->d.m % 2 == 0) rc = cwt_adjoint_t<float, 2>(pl, gWx, gdWx, gx, batch, rpadded, st);
+        else rc = cwt_adjoint_t<float, 1>(pl, gWx, gdWx, gx, batch, rpadded, st);
+    }
+    pl->order.leave(st);
+    return rc;
+}

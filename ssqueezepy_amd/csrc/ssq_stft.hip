@@ -785,31 +785,9 @@ static int stft_adjoint_pad_table(ssq_stft_plan* pl) {
     if (pl->adj_off) return 0;
     const int64_t n = pl->d.n, m = pl->padlen, n1 = pl->n1;
     SSQ_REQUIRE(m < ((int64_t)1 << 31), "stft adjoint: padded length %lld", (long long)m);
-    auto source = [&](int64_t t) -> int64_t {              // (the rule of pad_kernel / stft_pad_source)
-        if (t >= 0 && t < n) return t;
-        switch (pl->d.padtype) {
-            case SSQ_PAD_REFLECT: {
-                if (n == 1) return 0;
-                const int64_t period = 2 * (n - 1);
-                int64_t q = t % period; if (q < 0) q += period;
-                return q < n ? q : period - q;
-            }
-            case SSQ_PAD_SYMMETRIC: {
-                const int64_t period = 2 * n;
-                int64_t q = t % period; if (q < 0) q += period;
-                return q < n ? q : period - 1 - q;
-            }
-            case SSQ_PAD_REPLICATE: return t < 0 ? 0 : n - 1;
-            case SSQ_PAD_WRAP: { int64_t q = t % n; if (q < 0) q += n; return q; }
-            default: return -1;
-        }
-    };
-    std::vector<int32_t> off((size_t)n + 1, 0), idx((size_t)m);
-    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) ++off[(size_t)j + 1]; }
-    for (int64_t j = 0; j < n; ++j) off[(size_t)j + 1] += off[(size_t)j];
-    std::vector<int32_t> fill(off.begin(), off.end() - 1);
-    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) idx[(size_t)fill[(size_t)j]++] = (int32_t)p; }
-    SSQ_CHECK_HIP(hipMalloc((void**)&pl->adj_idx, idx.size() * 4));
+    std::vector<int32_t> off, idx;                         // (the rule of pad_kernel / stft_pad_source)
+    inverse_pad_table(n, m, n1, pl->d.padtype, off, idx);
+    SSQ_CHECK_HIP(hipMalloc((void**)&pl->adj_idx, idx.size() * 4 + 4));
     SSQ_CHECK_HIP(hipMemcpy(pl->adj_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
     int32_t* o = nullptr;
     SSQ_CHECK_HIP(hipMalloc((void**)&o, off.size() * 4));
