@@ -141,6 +141,9 @@ struct BlockArgs {
     float inv_dt;
     double gamma;
     int sig;                           // first signal of the launch (blockIdx.y adds to it)
+    // which instantiation a call takes: the fused ssq_cwt form (Wx + bin map, unscaled), Wx alone (a plain cwt)
+    bool lean() const { return kidx && !dWx && !w && !row_scale; }
+    bool wx_alone() const { return !kidx && !dWx && !w; }
 };
 
 // The body of one workgroup (item `item_idx` of the class's list; blockIdx.y = signal of the launch). Its LDS
@@ -148,12 +151,13 @@ struct BlockArgs {
 // in ONE launch, for transforms too small to fill the GPU per class -- shares one set between the classes.
 // NOD: the call asks for Wx alone (a plain cwt: no dWx, no w, no bin map) -- the derivative's inputs, its transform and
 // its share of the epilogue are compiled out (config 1's block rows 27 -> 17 us).
-template <int L, int G, int R1, int R2, int R3, bool LEAN, bool NOD = false>
+template <int L, bool LEAN, bool NOD = false>
 __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqParams& sp, int item_idx,
                                                c32* __restrict__ buf, c32* __restrict__ spow,
                                                c32* __restrict__ wrapf, c32* __restrict__ bandW,
                                                c32* __restrict__ bandD) {
-    constexpr int RL = (R3 > 1) ? R3 : R2;         // last radix
+    using S = FftShape<L>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;      // (RL: the last radix)
     const int tid = threadIdx.x;
     const int4 item = A.items[item_idx];
     const int row = item.x, blk = item.y, c0 = item.z;
@@ -274,8 +278,8 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     }
     // (twiddles requested ahead of each pass' barrier; nothing has touched `buf` before the first transform:
     // 58.9 -> 56.7 -> 56.2 us at config 2, round 5)
-    lds_ifft<L, G, R1, R2, R3, true, true>(zw, buf, A.ftw, tid);
-    if constexpr (!NOD) lds_ifft<L, G, R1, R2, R3, true>(zd, buf, A.ftw, tid);
+    lds_ifft<L, true, true>(zw, buf, A.ftw, tid);
+    if constexpr (!NOD) lds_ifft<L, true>(zd, buf, A.ftw, tid);
 
     // ---- epilogue: unpad, store, phase transform, bin map
     constexpr int NB = PPT / RL, STR = L / RL;
@@ -325,13 +329,13 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     }
 }
 
-template <int L, int G, int R1, int R2, int R3, bool LEAN, bool NOD = false>
+template <int L, bool LEAN, bool NOD = false>
 __global__ __launch_bounds__(NT) void blockzoom_kernel(BlockArgs A, SsqParams sp) {
     __shared__ c32 buf[D_POINTS];
-    __shared__ c32 spow[R1 * G];
-    __shared__ c32 wrapf[G];
+    __shared__ c32 spow[FftShape<L>::R1 * FftShape<L>::G];
+    __shared__ c32 wrapf[FftShape<L>::G];
     __shared__ c32 bandW[(L <= 512) ? L : 1], bandD[(L <= 512) ? L : 1];
-    blockzoom_body<L, G, R1, R2, R3, LEAN, NOD>(A, sp, (int)blockIdx.x, buf, spow, wrapf, bandW, bandD);
+    blockzoom_body<L, LEAN, NOD>(A, sp, (int)blockIdx.x, buf, spow, wrapf, bandW, bandD);
 }
 
 // every class of a plan in one launch: workgroup b belongs to the class whose item range holds b
@@ -353,12 +357,13 @@ __global__ __launch_bounds__(NT) void blockzoom_multi_kernel(BlockMultiArgs M, S
     BlockArgs A = M.A;
     A.items = M.items[s]; A.ftw = M.ftw[s];
     const int it = b - M.first[s];
+    // (written out: through fft_switch's lambda the compiler lays this kernel out differently from the code that was measured)
     switch (s) {
-        case 0: blockzoom_body<128, 32, 16, 8, 1, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 1: blockzoom_body<256, 16, 16, 16, 1, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 2: blockzoom_body<512, 8, 8, 8, 8, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 3: blockzoom_body<1024, 4, 16, 8, 8, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        default: blockzoom_body<2048, 2, 16, 16, 8, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 0: blockzoom_body<128, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 1: blockzoom_body<256, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 2: blockzoom_body<512, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 3: blockzoom_body<1024, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        default: blockzoom_body<2048, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
     }
 }
 
@@ -375,18 +380,19 @@ struct BlockArgs64 {
     int64_t M, N, na, n_items;
     double inv_dt, gamma;
     int sig;
+    bool wx_alone() const { return !kidx && !dWx && !w; }
 };
 
 // (two wavefronts per SIMD: left alone the compiler takes 276-280 registers -- one wavefront per SIMD -- and config 5's
 // block rows run at 10.5 ms instead of 8.1; at 256 it spills ~90 bytes per lane)
 // NOD: Wx alone (a plain cwt), as for the float32 kernels: the derivative's transform and outputs compiled out.
-template <int L, int G, int R1, int R2, int R3, bool NOD = false>
+template <int L, bool NOD = false>
 __global__ __launch_bounds__(FftGeom<double>::NT) SSQ_WAVES_PER_EU(2, 2) void blockzoom_f64_kernel(BlockArgs64 A, SsqParams sp) {
-    constexpr int NT64 = FftGeom<double>::NT;
+    using S = FftShape<L, double>;
+    constexpr int NT64 = FftGeom<double>::NT, G = S::G, R1 = S::R1, RL = S::RL;
     __shared__ c64 buf[FftGeom<double>::D];
     __shared__ c64 spow[R1 * G];
     __shared__ c64 wrapf[G];
-    constexpr int RL = (R3 > 1) ? R3 : R2;
     const int tid = threadIdx.x;
     const int4 item = A.items[blockIdx.x];
     const int row = item.x, blk = item.y, c0 = item.z;
@@ -459,8 +465,8 @@ __global__ __launch_bounds__(FftGeom<double>::NT) SSQ_WAVES_PER_EU(2, 2) void bl
             }
         }
     }
-    lds_ifft<L, G, R1, R2, R3, false, true>(zw, buf, A.ftw, tid);      // (the buffer is untouched so far: no barrier in front)
-    if constexpr (!NOD) lds_ifft<L, G, R1, R2, R3>(zd, buf, A.ftw, tid);
+    lds_ifft<L, false, true>(zw, buf, A.ftw, tid);      // (the buffer is untouched so far: no barrier in front)
+    if constexpr (!NOD) lds_ifft<L>(zd, buf, A.ftw, tid);
 
     constexpr int NB = PPT / RL, STR = L / RL;
     const int64_t base = ((int64_t)sig * A.na + row) * A.N;
@@ -498,15 +504,14 @@ __global__ __launch_bounds__(FftGeom<double>::NT) SSQ_WAVES_PER_EU(2, 2) void bl
     }
 }
 
-template <int L, int G, int R1, int R2, int R3>
+template <int L>
 static int launch_zoom64(const BlockArgs64& A, const SsqParams& sp, int nsig, hipStream_t stream) {
     if (A.n_items == 0) return 0;
-    if (!A.dWx && !A.w && !A.kidx)                 // Wx alone
-        hipLaunchKernelGGL((blockzoom_f64_kernel<L, G, R1, R2, R3, true>), dim3((unsigned)A.n_items, (unsigned)nsig),
-                           dim3(FftGeom<double>::NT), 0, stream, A, sp);
+    const dim3 grid((unsigned)A.n_items, (unsigned)nsig);
+    if (A.wx_alone())
+        hipLaunchKernelGGL((blockzoom_f64_kernel<L, true>), grid, dim3(FftGeom<double>::NT), 0, stream, A, sp);
     else
-    hipLaunchKernelGGL((blockzoom_f64_kernel<L, G, R1, R2, R3>), dim3((unsigned)A.n_items, (unsigned)nsig),
-                       dim3(FftGeom<double>::NT), 0, stream, A, sp);
+        hipLaunchKernelGGL((blockzoom_f64_kernel<L>), grid, dim3(FftGeom<double>::NT), 0, stream, A, sp);
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -519,17 +524,12 @@ int BlockPlan::run64(int sig, int nsig, double* Wx, double* dWx, double* w, unsi
     A.Wx = Wx; A.dWx = dWx; A.w = w; A.kidx = kidx;
     A.M = M; A.N = N; A.na = na;
     A.inv_dt = 1.0 / dt; A.gamma = sp.gamma; A.sig = sig;
-    int rc = 0;
-#define ZOOM64(slot, L, G, R1, R2, R3)                                                            \
-    A.items = (const int4*)items[slot]; A.n_items = n_items[slot];                                 \
-    A.ftw = (const c64*)ftw + ftw_off[slot];                                                       \
-    if ((rc = launch_zoom64<L, G, R1, R2, R3>(A, sp, nsig, stream))) return rc;
-    ZOOM64(0, 128, 16, 16, 8, 1)
-    ZOOM64(1, 256, 8, 16, 16, 1)
-    ZOOM64(2, 512, 4, 8, 8, 8)
-    ZOOM64(3, 1024, 2, 16, 8, 8)
-    ZOOM64(4, 2048, 1, 16, 16, 8)
-#undef ZOOM64
+    for (int s = 0; s < 5; ++s) {                  // the plan's item lists: L' = 128 << s
+        A.items = (const int4*)items[s]; A.n_items = n_items[s];
+        A.ftw = (const c64*)ftw + ftw_off[s];
+        const int rc = fft_dispatch<128, 2048>(128 << s, [&](auto len) { return launch_zoom64<decltype(len)::value>(A, sp, nsig, stream); });
+        if (rc) return rc;
+    }
     return 0;
 }
 
@@ -554,12 +554,14 @@ struct ExactArgs {
     int64_t M, N, na; int A, B, n1pad, sig, n_rows;   // sig: first signal (blockIdx.z adds)
     int G2;                                           // n2 columns per pass-2 workgroup
     double h; float inv_dt; double gamma;
+    bool lean() const { return kidx && !dWx && !w && !row_scale; }     // (as BlockArgs)
 };
 
-template <int L, int G, int R1, int R2, int R3>
+template <int L>
 __global__ __launch_bounds__(NT) void exact_pass1_kernel(ExactArgs E) {
     __shared__ c32 buf[D_POINTS + 64];
-    constexpr int RL = (R3 > 1) ? R3 : R2;
+    using S = FftShape<L>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;
     const int tid = threadIdx.x, r = blockIdx.y, row = E.rows[r];
     const int c0 = blockIdx.x * G;                          // first k1 of this workgroup
     const int lo = E.band_lo[row];
@@ -604,11 +606,11 @@ __global__ __launch_bounds__(NT) void exact_pass1_kernel(ExactArgs E) {
     }
     constexpr int NBL = PPT / RL, STRL = L / RL;
     const int G2 = E.G2, lg2 = __ffs(G2) - 1;
-    constexpr int LG = (G == 1) ? 0 : (G == 2) ? 1 : (G == 4) ? 2 : (G == 8) ? 3 : (G == 16) ? 4 : 5;
+    constexpr int LG = ilog2(G);
 #pragma unroll
     for (int tr = 0; tr < 2; ++tr) {
         c32 (&v)[PPT] = tr ? zd : zw;
-        lds_ifft<L, G, R1, R2, R3>(v, buf, E.ftw, tid);
+        lds_ifft<L>(v, buf, E.ftw, tid);
         __syncthreads();
 #pragma unroll
         for (int it = 0; it < NBL; ++it) {
@@ -633,10 +635,11 @@ __global__ __launch_bounds__(NT) void exact_pass1_kernel(ExactArgs E) {
     }
 }
 
-template <int L, int G, int R1, int R2, int R3, bool LEAN>
+template <int L, bool LEAN>
 __global__ __launch_bounds__(NT) void exact_pass2_kernel(ExactArgs E, SsqParams sp) {
     __shared__ c32 buf[D_POINTS];
-    constexpr int RL = (R3 > 1) ? R3 : R2;
+    using S = FftShape<L>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;
     const int tid = threadIdx.x, r = blockIdx.y, row = E.rows[r];
     // a workgroup writes G consecutive outputs per n1 (G*8-byte pieces of Wx, G*2 of the bin map):
     // give each XCD (workgroup b -> XCD b % 8) a contiguous range of n2 so the pieces of one
@@ -659,8 +662,8 @@ __global__ __launch_bounds__(NT) void exact_pass2_kernel(ExactArgs E, SsqParams 
             }
         }
     }
-    lds_ifft<L, G, R1, R2, R3>(zw, buf, E.ftw, tid);
-    lds_ifft<L, G, R1, R2, R3>(zd, buf, E.ftw, tid);
+    lds_ifft<L>(zw, buf, E.ftw, tid);
+    lds_ifft<L>(zd, buf, E.ftw, tid);
     constexpr int NB = PPT / RL, STR = L / RL;
     const EmitRow er = make_emit_row(E.Wx, E.dWx, E.w, E.kidx, E.row_scale, E.sig + (int)blockIdx.z, (int)blockIdx.z, row, E.na, E.N, E.gamma, sp.flipud);
     const int N = (int)E.N;
@@ -783,7 +786,7 @@ __global__ __launch_bounds__(NT) void block_spectra4096_kernel(BlockSpecArgs A) 
             z[t] = {A.xp[sig * M + s0], two ? A.xp[sig * M + s1] : 0.f};
         }
     }
-    lds_ifft<P, 1, 16, 16, 16>(z, buf, A.ctw + k.ctw_off, tid);
+    lds_ifft<P>(z, buf, A.ctw + k.ctw_off, tid);
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < PPT; ++t) buf[tid + t * NT] = z[t];    // natural order: Z'[tid + 256 t]
@@ -828,7 +831,7 @@ __device__ __forceinline__ void wide_stage_tw(c32* __restrict__ stw, const c32* 
 }
 template <int CW>
 __device__ __forceinline__ void wide_ifft(c32 (&z)[PPT], c32* __restrict__ buf, const c32* __restrict__ stw, int tid) {
-    lds_ifft<WIDE_L, CW, 16, 8, 8, false, false, 1, 64 * CW>(z, buf, stw, tid);   // (its first barrier: stw is in place)
+    lds_ifft<WIDE_L, false, false, 1, 64 * CW>(z, buf, stw, tid);   // (its first barrier: stw is in place)
 }
 // the last step's twiddles e^{2 pi i r f / P} of a thread's (slot, f) pairs: asked for at the kernel's start
 template <int CW, int C>
@@ -964,16 +967,16 @@ __global__ __launch_bounds__(NT * QMAX) void block_spectra_multi_kernel(BlockSpe
     else if constexpr (QMAX >= 4) block_spectra_wide<4 * QMAX, 16>(A, k, b, buf, stw);
 }
 
-template <int L, int G, int R1, int R2, int R3>
+template <int L>
 static int launch_zoom(const BlockArgs& A, const SsqParams& sp, int nsig, hipStream_t stream) {
     if (A.n_items == 0) return 0;
     const dim3 grid((unsigned)A.n_items, (unsigned)nsig);
-    if (A.kidx && !A.dWx && !A.w && !A.row_scale)
-        hipLaunchKernelGGL((blockzoom_kernel<L, G, R1, R2, R3, true>), grid, dim3(NT), 0, stream, A, sp);
-    else if (!A.kidx && !A.dWx && !A.w)            // Wx alone
-        hipLaunchKernelGGL((blockzoom_kernel<L, G, R1, R2, R3, false, true>), grid, dim3(NT), 0, stream, A, sp);
+    if (A.lean())
+        hipLaunchKernelGGL((blockzoom_kernel<L, true>), grid, dim3(NT), 0, stream, A, sp);
+    else if (A.wx_alone())
+        hipLaunchKernelGGL((blockzoom_kernel<L, false, true>), grid, dim3(NT), 0, stream, A, sp);
     else
-        hipLaunchKernelGGL((blockzoom_kernel<L, G, R1, R2, R3, false>), grid, dim3(NT), 0, stream, A, sp);
+        hipLaunchKernelGGL((blockzoom_kernel<L, false>), grid, dim3(NT), 0, stream, A, sp);
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -1207,7 +1210,6 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
     A.h = (2.0 * 3.141592653589793) / (double)M;
     A.inv_dt = 1.0f / (float)dt;
     A.gamma = sp.gamma; A.sig = sig;
-    int rc = 0;
     {   // A transform too small to fill the GPU class by class (C1: five launches of 10-18 us each): one launch.
         // (SSQ_DEBUG_CWT_BLOCKS_MULTI=0/1 forces; default: when no class has more than two workgroups per CU)
         const char* fe = getenv("SSQ_DEBUG_CWT_BLOCKS_MULTI");                 // (read per call: tests switch it)
@@ -1222,7 +1224,7 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
         // together: block stage 107 -> 89 us, round 5)
         // (... and the fused form's lean kernels always: at config 2, 16 signals per launch, the two large classes in
         // one launch take 58.5 us per transform against 64.0 one after the other -- one tail instead of two -- round 5)
-        const bool lean = A.kidx && !A.dWx && !A.w && !A.row_scale;
+        const bool lean = A.lean();
         const bool multi = force >= 0 ? force != 0
                                       : (used > 1 && (lean || biggest <= 2 * (int64_t)ncu || total * nsig <= 18 * (int64_t)ncu));
         if (multi && total > 0) {
@@ -1237,7 +1239,7 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
             const dim3 grid((unsigned)total, (unsigned)nsig);
             if (lean)
                 hipLaunchKernelGGL((blockzoom_multi_kernel<true>), grid, dim3(NT), 0, stream, Mx, sp);
-            else if (!Mx.A.kidx && !Mx.A.dWx && !Mx.A.w)   // Wx alone
+            else if (A.wx_alone())
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false, true>), grid, dim3(NT), 0, stream, Mx, sp);
             else
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false>), grid, dim3(NT), 0, stream, Mx, sp);
@@ -1245,30 +1247,24 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
             return 0;
         }
     }
-#define ZOOM(slot, L, G, R1, R2, R3)                                                              \
-    A.items = (const int4*)items[slot]; A.n_items = limit ? limit[slot] : n_items[slot];                                 \
-    A.ftw = (const c32*)ftw + ftw_off[slot];                                                       \
-    if ((rc = launch_zoom<L, G, R1, R2, R3>(A, sp, nsig, stream))) return rc;
-    ZOOM(0, 128, 32, 16, 8, 1)
-    ZOOM(1, 256, 16, 16, 16, 1)
-    ZOOM(2, 512, 8, 8, 8, 8)
-    ZOOM(3, 1024, 4, 16, 8, 8)
-    ZOOM(4, 2048, 2, 16, 16, 8)
-#undef ZOOM
+    for (int s = 0; s < 5; ++s) {                  // the plan's item lists: L' = 128 << s
+        A.items = (const int4*)items[s]; A.n_items = limit ? limit[s] : n_items[s];
+        A.ftw = (const c32*)ftw + ftw_off[s];
+        const int rc = fft_dispatch<128, 2048>(128 << s, [&](auto len) { return launch_zoom<decltype(len)::value>(A, sp, nsig, stream); });
+        if (rc) return rc;
+    }
     return 0;
 }
 
 
 // ---- exact rows: host side
-static int log2i(int64_t v) { int l = 0; while ((1ll << l) < v) ++l; return l; }
-
 int BlockPlan::setup_exact(const float* bank_dev, const int64_t* band_off_dev, const int32_t* band_lo_dev,
                            const int32_t* gen_rows_dev, const std::vector<int64_t>& h_off,
                            const std::vector<int32_t>& h_lo, const std::vector<int32_t>& h_gen,
                            int64_t& bytes) {
     exact_ok = false;
     if (h_gen.empty()) return 0;
-    const int lm = log2i(M);
+    const int lm = fft_slot(M, 1);                  // (log2 M when M is a power of two)
     if ((1ll << lm) != M || lm < 14 || lm > 22) return 0;
     for (int32_t i : h_gen) {                       // analytic rows only
         int64_t len = h_off[i + 1] - h_off[i];
@@ -1289,20 +1285,20 @@ int BlockPlan::setup_exact(const float* bank_dev, const int64_t* band_off_dev, c
     return 0;
 }
 
-template <int L, int G, int R1, int R2, int R3>
+template <int L>
 static int launch_exact1(const ExactArgs& E, int n_rows, int nsig, hipStream_t stream) {
-    hipLaunchKernelGGL((exact_pass1_kernel<L, G, R1, R2, R3>), dim3((unsigned)(E.A / G), (unsigned)n_rows, (unsigned)nsig),
+    hipLaunchKernelGGL((exact_pass1_kernel<L>), dim3((unsigned)(E.A / FftShape<L>::G), (unsigned)n_rows, (unsigned)nsig),
                        dim3(NT), 0, stream, E);
     SSQ_LAUNCH_CHECK();
     return 0;
 }
-template <int L, int G, int R1, int R2, int R3>
+template <int L>
 static int launch_exact2(const ExactArgs& E, const SsqParams& sp, int n_rows, int nsig, hipStream_t stream) {
-    const dim3 grid((unsigned)(E.B / G), (unsigned)n_rows, (unsigned)nsig);
-    if (E.kidx && !E.dWx && !E.w && !E.row_scale)
-        hipLaunchKernelGGL((exact_pass2_kernel<L, G, R1, R2, R3, true>), grid, dim3(NT), 0, stream, E, sp);
+    const dim3 grid((unsigned)(E.B / FftShape<L>::G), (unsigned)n_rows, (unsigned)nsig);
+    if (E.lean())
+        hipLaunchKernelGGL((exact_pass2_kernel<L, true>), grid, dim3(NT), 0, stream, E, sp);
     else
-        hipLaunchKernelGGL((exact_pass2_kernel<L, G, R1, R2, R3, false>), grid, dim3(NT), 0, stream, E, sp);
+        hipLaunchKernelGGL((exact_pass2_kernel<L, false>), grid, dim3(NT), 0, stream, E, sp);
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -1317,25 +1313,16 @@ int BlockPlan::run_exact(int sig, int nsig, const void* xh_all, float* Wx, float
     E.M = M; E.N = N; E.na = na; E.A = exA; E.B = exB; E.n1pad = (int)n1; E.sig = sig; E.n_rows = n_exact;
     E.G2 = D_POINTS / exA;
     E.h = (2.0 * 3.141592653589793) / (double)M; E.inv_dt = 1.0f / (float)dt; E.gamma = sp.gamma;
-    auto slot_of = [](int L) { return L == 128 ? 0 : L == 256 ? 1 : L == 512 ? 2 : L == 1024 ? 3 : 4; };
-    int rc = 0;
-    E.ftw = (const c32*)ftw + ftw_off[slot_of(exB)];
-    switch (exB) {
-        case 128: rc = launch_exact1<128, 32, 16, 8, 1>(E, n_exact, nsig, stream); break;
-        case 256: rc = launch_exact1<256, 16, 16, 16, 1>(E, n_exact, nsig, stream); break;
-        case 512: rc = launch_exact1<512, 8, 8, 8, 8>(E, n_exact, nsig, stream); break;
-        case 1024: rc = launch_exact1<1024, 4, 16, 8, 8>(E, n_exact, nsig, stream); break;
-        default: rc = launch_exact1<2048, 2, 16, 16, 8>(E, n_exact, nsig, stream); break;
-    }
+    // (setup_exact keeps both factors inside 128 .. 2048, the lengths of the plan's twiddle tables)
+    const int rc = fft_dispatch<128, 2048>(exB, [&](auto len) {
+        E.ftw = (const c32*)ftw + ftw_off[fft_slot(decltype(len)::value, 128)];
+        return launch_exact1<decltype(len)::value>(E, n_exact, nsig, stream);
+    });
     if (rc) return rc;
-    E.ftw = (const c32*)ftw + ftw_off[slot_of(exA)];
-    switch (exA) {
-        case 128: return launch_exact2<128, 32, 16, 8, 1>(E, sp, n_exact, nsig, stream);
-        case 256: return launch_exact2<256, 16, 16, 16, 1>(E, sp, n_exact, nsig, stream);
-        case 512: return launch_exact2<512, 8, 8, 8, 8>(E, sp, n_exact, nsig, stream);
-        case 1024: return launch_exact2<1024, 4, 16, 8, 8>(E, sp, n_exact, nsig, stream);
-        default: return launch_exact2<2048, 2, 16, 16, 8>(E, sp, n_exact, nsig, stream);
-    }
+    return fft_dispatch<128, 2048>(exA, [&](auto len) {
+        E.ftw = (const c32*)ftw + ftw_off[fft_slot(decltype(len)::value, 128)];
+        return launch_exact2<decltype(len)::value>(E, sp, n_exact, nsig, stream);
+    });
 }
 
 }  // namespace ssq

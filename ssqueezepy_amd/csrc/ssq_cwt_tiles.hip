@@ -10,6 +10,7 @@
 // between them (tile_kernel), the arguments and grid of tile2_kernel / tile3_kernel, what executed (tiles_done).
 #include "ssq_common.h"
 #include "ssq_tiles.h"
+#include "ssq_ldsfft.h"
 #include <algorithm>
 #include <cmath>
 
@@ -351,10 +352,7 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
         for (int s = 0; s < 7; ++s) {
             const int Lp = 64 << s;
             ftw_off[s] = (int64_t)tw.size() / 2;
-            for (int q = 0; q < Lp; ++q) {
-                const double a = 6.283185307179586 * (double)q / (double)Lp;
-                tw.push_back((float)std::cos(a)); tw.push_back((float)std::sin(a));
-            }
+            fft_twiddles(Lp, tw);
         }
         if ((rc = up(&ftw, tw.data(), tw.size() * 4))) return rc;
     }

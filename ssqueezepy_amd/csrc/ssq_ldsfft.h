@@ -2,11 +2,15 @@
 // double: in-register radix-4/8/16 butterflies and `lds_ifft`, a Stockham inverse FFT of G
 // columns of L points through LDS, 16 points per thread (float: 4096 complex points per
 // 256-thread workgroup; double: 2048 points per 128-thread workgroup -- both 32 KiB of LDS).
-// Used by the CWT block / four-step kernels (ssq_cwt_blocks.hip) and the fused STFT
-// kernel (ssq_stft.hip). Device code only; include inside a .hip translation unit.
+// A transform's shape is its length: `FftShape<L, R>` holds the columns per workgroup and the two or
+// three radices that go with L, `fft_switch` / `fft_dispatch` turn a run-time length into that tag.
+// Used by the CWT block / four-step kernels (ssq_cwt_blocks.hip, ssq_tile_fft.hip) and the fused STFT
+// kernels (ssq_stft.hip). Include inside a .hip translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ssq_common.h"
+#include <cmath>
+#include <vector>
 
 namespace ssq {
 
@@ -96,7 +100,67 @@ template <typename R> struct FftGeom {
 constexpr int D_POINTS = FftGeom<float>::D;     // float32 kernels: 4096 points,
 constexpr int NT = FftGeom<float>::NT;          //                  256 threads
 
-// One L-point inverse FFT per column for G columns, Stockham autosort, LDS [q][g].
+// ---- the shapes lds_ifft runs: 64 .. 4096 points, and everything but the length follows from it
+constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
+// G: columns per workgroup; R1, R2, R3: the Stockham radices in pass order (R3 = 1: two passes); RL: the last one.
+// Two passes up to 256 points, three from 512 on; radix 16 for as many passes as the length allows, the first ones.
+template <int L, typename R = float> struct FftShape {
+    static_assert(L >= 64 && L <= 4096 && (L & (L - 1)) == 0, "FftShape: a power of two in [64, 4096]");
+    static constexpr int LOG2L = ilog2(L);
+    static constexpr int G = FftGeom<R>::D / L;
+    static constexpr int NPASS = L <= 256 ? 2 : 3, N16 = LOG2L - 3 * NPASS;
+    static constexpr int R1 = N16 >= 1 ? 16 : 8, R2 = N16 >= 2 ? 16 : 8, R3 = NPASS < 3 ? 1 : N16 >= 3 ? 16 : 8;
+    static constexpr int RL = (R3 > 1) ? R3 : R2;
+    static_assert(R1 * R2 * R3 == L && G >= 1, "FftShape: the radices make up the length");
+};
+// the derivation against the tuples the kernels were written out with
+template <int L, int G, int R1, int R2, int R3, typename R = float, typename S = FftShape<L, R>>
+constexpr bool fft_shape_is() { return S::G == G && S::R1 == R1 && S::R2 == R2 && S::R3 == R3; }
+static_assert(fft_shape_is<64, 64, 8, 8, 1>() && fft_shape_is<128, 32, 16, 8, 1>() && fft_shape_is<256, 16, 16, 16, 1>() &&
+              fft_shape_is<512, 8, 8, 8, 8>() && fft_shape_is<1024, 4, 16, 8, 8>() && fft_shape_is<2048, 2, 16, 16, 8>() &&
+              fft_shape_is<4096, 1, 16, 16, 16>(), "FftShape: float32");
+static_assert(fft_shape_is<128, 16, 16, 8, 1, double>() && fft_shape_is<256, 8, 16, 16, 1, double>() &&
+              fft_shape_is<512, 4, 8, 8, 8, double>() && fft_shape_is<1024, 2, 16, 8, 8, double>() &&
+              fft_shape_is<2048, 1, 16, 16, 8, double>(), "FftShape: float64");
+
+// slot of length L in a table whose first length is LMIN (L = LMIN << slot)
+constexpr int fft_slot(int64_t L, int LMIN) { return L <= LMIN ? 0 : 1 + fft_slot(L >> 1, LMIN); }
+
+// f(FftLen<LMIN << slot>{}): the run-time slot as a compile-time length, in kernels and launchers alike. The last
+// length is the switch's default (a slot is a table index the caller made). A switch, and f by value: a chain of
+// comparisons, or f by reference, and the compiler lays the tile kernels out differently from the code that was measured.
+template <int V> struct FftLen { static constexpr int value = V; };
+template <int LMIN, int LMAX, typename F>
+__host__ __device__ __forceinline__ void fft_switch(int slot, F f) {
+    static_assert((LMIN << 6) >= LMAX, "fft_switch: seven lengths at most");
+    switch (slot) {
+        case 0: if constexpr ((LMIN << 0) < LMAX) { f(FftLen<(LMIN << 0)>{}); break; }
+        case 1: if constexpr ((LMIN << 1) < LMAX) { f(FftLen<(LMIN << 1)>{}); break; }
+        case 2: if constexpr ((LMIN << 2) < LMAX) { f(FftLen<(LMIN << 2)>{}); break; }
+        case 3: if constexpr ((LMIN << 3) < LMAX) { f(FftLen<(LMIN << 3)>{}); break; }
+        case 4: if constexpr ((LMIN << 4) < LMAX) { f(FftLen<(LMIN << 4)>{}); break; }
+        case 5: if constexpr ((LMIN << 5) < LMAX) { f(FftLen<(LMIN << 5)>{}); break; }
+        default: f(FftLen<LMAX>{});
+    }
+}
+// host: rc = f(FftLen<L>{}) for a run-time length; one outside the table is an internal error, not another kernel
+template <int LMIN, int LMAX, typename F>
+int fft_dispatch(int64_t L, F&& f) {
+    SSQ_REQUIRE(L >= LMIN && L <= LMAX && !(L & (L - 1)), "no LDS transform of %lld points (%d .. %d)", (long long)L, LMIN, LMAX);
+    int rc = 0;
+    fft_switch<LMIN, LMAX>(fft_slot(L, LMIN), [&](auto len) { rc = f(len); });
+    return rc;
+}
+
+// e^{2 pi i q / L}, q < L, appended to `tw` as float pairs: the host form of lds_ifft's twiddle table
+inline void fft_twiddles(int L, std::vector<float>& tw) {
+    for (int q = 0; q < L; ++q) {
+        const double a = 6.283185307179586 * (double)q / (double)L;
+        tw.push_back((float)std::cos(a)); tw.push_back((float)std::sin(a));
+    }
+}
+
+// One L-point inverse FFT per column for G = NT * 16 / L columns, Stockham autosort, LDS [q][g]; radices: FftShape<L>.
 // `v` holds the pass-1 inputs on entry (butterfly u = idx / G, column g = idx % G,
 // idx = tid + it*NT, input t at q = u + t*L/R1) and the final-pass outputs on exit
 // (n_hi = u + t*L/RL with RL the last radix, same idx -> (u, g) mapping).
@@ -105,11 +169,12 @@ constexpr int NT = FftGeom<float>::NT;          //                  256 threads
 // change for the intermediates' kernels, which wait on HBM). FRESH: `buf` holds nothing a wavefront may still be
 // reading (a kernel's first transform): no barrier before pass 1. TWS: the twiddle table is e^{2 pi i q / (L TWS)} --
 // a longer transform's table read at every TWS-th entry (the sub-transforms of block_spectra_multi_kernel). NTH: the
-// workgroup's thread count when it is not the geometry's 256 / 128 (16 points per thread all the same).
-template <int L, int G, int R1, int R2, int R3, bool EARLY_TW = false, bool FRESH = false, int TWS = 1, int NTH = 0, typename R>
+// workgroup's thread count when it is not the geometry's 256 / 128 (16 points per thread all the same; G follows).
+template <int L, bool EARLY_TW = false, bool FRESH = false, int TWS = 1, int NTH = 0, typename R>
 __device__ __forceinline__ void lds_ifft(cx<R> (&v)[PPT], cx<R>* __restrict__ buf,
                                          const cx<R>* __restrict__ ftw, int tid) {
-    constexpr int NT = NTH ? NTH : FftGeom<R>::NT;
+    constexpr int NT = NTH ? NTH : FftGeom<R>::NT, G = NT * PPT / L;
+    constexpr int R1 = FftShape<L, R>::R1, R2 = FftShape<L, R>::R2, R3 = FftShape<L, R>::R3;
     static_assert(L * G == NT * PPT, "L * G must fill the workgroup");
     constexpr bool three = (R3 > 1);
     constexpr bool ETW = EARLY_TW && sizeof(R) == 4;

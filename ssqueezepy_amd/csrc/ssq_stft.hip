@@ -71,8 +71,10 @@ __global__ __launch_bounds__(256) void frame_window_kernel(
 // transform -- every bin leaves with its weight c_k / L (c_k = 1 for DC and Nyquist, 2 elsewhere) and the imaginary
 // parts of DC and Nyquist as exact zeros, applied where the bin is stored. `if constexpr`: the other instantiations
 // compile to the code they had.
-template <int L, int G, int R1, int R2, int R3, bool REASSIGN, bool CST64, bool IADJ = false>
+template <int L, bool REASSIGN, bool CST64, bool IADJ = false>
 __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqParams sp) {
+    using S = FftShape<L>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;
     static_assert(!IADJ || !REASSIGN, "stft_fused_kernel: the inverse's backward stores Sx only");
     // the frames' Tx: a real and an imaginary plane of (L/2 + 1) x G float64 cells. The planes take the FFT buffer's
     // place once its last reader is done (the workgroup's LDS stays at 32 KB + 16 G bytes: four workgroups per CU)
@@ -83,7 +85,6 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
     double* const txt = raw;
     float* const sm = reinterpret_cast<float*>(raw);
     static_assert(sizeof(double) * RAW <= 40 * 1024, "stft_fused_kernel: static LDS beyond a quarter of a gfx950 CU's 160 KB");
-    constexpr int RL = (R3 > 1) ? R3 : R2;
     constexpr int NI = ((L / 2 + 1) * G + NT - 1) / NT;       // epilogue points per work-item
     using w_t = typename std::conditional<CST64, double, float>::type;
     const int tid = threadIdx.x;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
             cw0 = ((const w_t*)A.cst)[0];
         }
         // (FRESH: a barrier has just passed; the twiddles asked for ahead of each pass' barrier measured no gain here)
-        lds_ifft<L, G, R1, R2, R3, false, true>(z, buf, A.ftw, tid);
+        lds_ifft<L, false, true>(z, buf, A.ftw, tid);
         __syncthreads();                              // last pass' LDS reads are done
         {
             constexpr int NB = PPT / RL, STR = L / RL;
@@ -277,8 +278,9 @@ __global__ __launch_bounds__(NT) void stft_fused_kernel(StftFusedArgs A, SsqPara
 }
 
 // one workgroup per item; the grid is two-dimensional only to hold more than 2^31 - 1 of them
-template <int L, int G, int R1, int R2, int R3, bool IADJ = false>
+template <int L, bool IADJ = false>
 static int launch_stft_fused(const StftFusedArgs& A, const SsqParams& sp, int64_t batch, hipStream_t stream) {
+    constexpr int G = FftShape<L>::G;
     SSQ_REQUIRE(!A.Tx || A.rows == L / 2 + 1, "fused reassignment: %lld rows, transform of %d", (long long)A.rows, L);
     StftFusedArgs B = A;
     B.batch = (int)batch;
@@ -290,13 +292,13 @@ static int launch_stft_fused(const StftFusedArgs& A, const SsqParams& sp, int64_
     SSQ_REQUIRE(gy <= 65535, "stft_fused_kernel: %lld items", (long long)total);
     dim3 grid((unsigned)gx, (unsigned)gy);
     if constexpr (IADJ)
-        hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, false, false, true>), grid, dim3(NT), 0, stream, B, sp);
+        hipLaunchKernelGGL((stft_fused_kernel<L, false, false, true>), grid, dim3(NT), 0, stream, B, sp);
     else if (!A.Tx)
-        hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, false, false>), grid, dim3(NT), 0, stream, B, sp);
+        hipLaunchKernelGGL((stft_fused_kernel<L, false, false>), grid, dim3(NT), 0, stream, B, sp);
     else if (sp.cst_f64)
-        hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, true, true>), grid, dim3(NT), 0, stream, B, sp);
+        hipLaunchKernelGGL((stft_fused_kernel<L, true, true>), grid, dim3(NT), 0, stream, B, sp);
     else
-        hipLaunchKernelGGL((stft_fused_kernel<L, G, R1, R2, R3, true, false>), grid, dim3(NT), 0, stream, B, sp);
+        hipLaunchKernelGGL((stft_fused_kernel<L, true, false>), grid, dim3(NT), 0, stream, B, sp);
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -328,14 +330,15 @@ struct StftAdjArgs {
 // transform -- every bin whole and 1 / L (exact: L is a power of two) where the adjoint halves the interior bins --,
 // the window (gA = Sx, winA = window^a in the transform's order, gB null) and the pass that finishes the strips
 // (istft_finish_kernel: the window norm and the trim instead of the padding's transpose).
-template <int L, int G, int R1, int R2, int R3, bool INV>
+template <int L, bool INV>
 __global__ __launch_bounds__(NT) void stft_adjoint_fused_kernel(StftAdjArgs A) {
+    using S = FftShape<L>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;
     __shared__ float raw[ADJ_RAW];
     __shared__ float strip[ADJ_SPAN];
     constexpr int PITCH = L + 64 / G;                // (the G columns of a butterfly's output land in G different banks)
     static_assert(2 * G * PITCH <= ADJ_RAW, "stft_adjoint_fused_kernel: the windowed frames outgrow the FFT buffer");
     static_assert(sizeof(float) * (ADJ_RAW + ADJ_SPAN) <= 53 * 1024, "stft_adjoint_fused_kernel: static LDS beyond a third of a CU's 160 KB");
-    constexpr int RL = (R3 > 1) ? R3 : R2;
     c32* const buf = reinterpret_cast<c32*>(raw);
     const int tid = threadIdx.x;
     const int64_t item = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
@@ -374,7 +377,7 @@ __global__ __launch_bounds__(NT) void stft_adjoint_fused_kernel(StftAdjArgs A) {
                 }
             }
         }
-        lds_ifft<L, G, R1, R2, R3, false, false>(z, buf, A.ftw, tid);     // (its first barrier: the last pass' frames are read)
+        lds_ifft<L>(z, buf, A.ftw, tid);     // (its first barrier: the last pass' frames are read)
         __syncthreads();                                                   // the transform's LDS reads are done
         {
             constexpr int NB = PPT / RL, STR = L / RL;
@@ -448,12 +451,12 @@ __global__ __launch_bounds__(256) void istft_finish_kernel(const float* __restri
     x[(int64_t)blockIdx.y * N + s] = acc;
 }
 
-template <int L, int G, int R1, int R2, int R3, bool INV = false>
+template <int L, bool INV = false>
 static int launch_stft_adjoint_fused(const StftAdjArgs& A, hipStream_t stream) {
     const int64_t total = A.n_items * A.batch;
     const int64_t gx = std::min<int64_t>(total, (int64_t)1 << 20), gy = (total + gx - 1) / gx;
     SSQ_REQUIRE(gy <= 65535, "stft_adjoint_fused_kernel: %lld items", (long long)total);
-    hipLaunchKernelGGL((stft_adjoint_fused_kernel<L, G, R1, R2, R3, INV>), dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0,
+    hipLaunchKernelGGL((stft_adjoint_fused_kernel<L, INV>), dim3((unsigned)gx, (unsigned)gy), dim3(NT), 0,
                        stream, A);
     SSQ_LAUNCH_CHECK();
     return 0;
@@ -703,13 +706,7 @@ static int stft_execute_t(ssq_stft_plan* pl, const void* x, int64_t batch, void*
             A.hop = (int)d.hop_len; A.s20 = (int)s20; A.s21 = (int)s21; A.modulated = d.modulated;
             A.x = pad_in_kernel ? (const float*)x : nullptr; A.n = (int)d.n; A.n1 = (int)pl->n1; A.padtype = d.padtype;
             A.wd = (const float2*)pl->wd;
-            switch (n_fft) {
-                case 128: rc = launch_stft_fused<128, 32, 16, 8, 1>(A, pl->sp, batch, stream); break;
-                case 256: rc = launch_stft_fused<256, 16, 16, 16, 1>(A, pl->sp, batch, stream); break;
-                case 512: rc = launch_stft_fused<512, 8, 8, 8, 8>(A, pl->sp, batch, stream); break;
-                case 1024: rc = launch_stft_fused<1024, 4, 16, 8, 8>(A, pl->sp, batch, stream); break;
-                default: rc = launch_stft_fused<2048, 2, 16, 16, 8>(A, pl->sp, batch, stream); break;
-            }
+            rc = fft_dispatch<128, 2048>(n_fft, [&](auto len) { return launch_stft_fused<decltype(len)::value>(A, pl->sp, batch, stream); });
             if (rc) return rc;
         }
     }
@@ -840,13 +837,7 @@ static int stft_adjoint_fused(ssq_stft_plan* pl, const void* gSx, const void* gd
     float* ws = nullptr;
     SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
     A.ws = ws;
-    switch (L) {
-        case 128: rc = launch_stft_adjoint_fused<128, 32, 16, 8, 1>(A, stream); break;
-        case 256: rc = launch_stft_adjoint_fused<256, 16, 16, 16, 1>(A, stream); break;
-        case 512: rc = launch_stft_adjoint_fused<512, 8, 8, 8, 8>(A, stream); break;
-        case 1024: rc = launch_stft_adjoint_fused<1024, 4, 16, 8, 8>(A, stream); break;
-        default: rc = launch_stft_adjoint_fused<2048, 2, 16, 16, 8>(A, stream); break;
-    }
+    rc = fft_dispatch<128, 2048>(L, [&](auto len) { return launch_stft_adjoint_fused<decltype(len)::value>(A, stream); });
     if (!rc) rc = stft_adjoint_unpad<float>(pl, ws, gx, batch, A.n_items, nf * hop, A.span,
                                             (pl->n_hops - 1) * (int64_t)hop + L, stream);
     (void)hipFreeAsync(ws, stream);
@@ -894,11 +885,8 @@ static int fused_twiddles(int L, const c32** out) {
     std::lock_guard<std::mutex> lock(g_tw_mu);
     auto it = g_tw.find({dev, L});
     if (it == g_tw.end()) {
-        std::vector<float> tw((size_t)2 * L);
-        for (int q = 0; q < L; ++q) {
-            const double ang = 2.0 * 3.14159265358979323846 * (double)q / (double)L;
-            tw[2 * q] = (float)cos(ang); tw[2 * q + 1] = (float)sin(ang);
-        }
+        std::vector<float> tw;
+        fft_twiddles(L, tw);
         void* d = nullptr;
         SSQ_CHECK_HIP(hipMalloc(&d, tw.size() * 4));
         SSQ_CHECK_HIP(hipMemcpy(d, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
@@ -923,13 +911,7 @@ int istft_fused(const void* Sx, const void* win_t, const double* wn, void* x, in
     float* ws = nullptr;
     SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
     A.ws = ws;
-    switch (L) {
-        case 128: rc = launch_stft_adjoint_fused<128, 32, 16, 8, 1, true>(A, stream); break;
-        case 256: rc = launch_stft_adjoint_fused<256, 16, 16, 16, 1, true>(A, stream); break;
-        case 512: rc = launch_stft_adjoint_fused<512, 8, 8, 8, 8, true>(A, stream); break;
-        case 1024: rc = launch_stft_adjoint_fused<1024, 4, 16, 8, 8, true>(A, stream); break;
-        default: rc = launch_stft_adjoint_fused<2048, 2, 16, 16, 8, true>(A, stream); break;
-    }
+    rc = fft_dispatch<128, 2048>(L, [&](auto len) { return launch_stft_adjoint_fused<decltype(len)::value, true>(A, stream); });
     if (!rc) {
         hipLaunchKernelGGL(istft_finish_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)batch), dim3(256), 0, stream,
                            (const float*)ws, wn, (float*)x, N, (int64_t)(L / 2), A.n_items, (int64_t)A.nf * hop,
@@ -952,14 +934,7 @@ int istft_adjoint_fused(const void* u, const void* win_t, void* gSx, int64_t bat
     A.hop = (int)hop; A.s20 = L / 2; A.s21 = L / 2; A.modulated = modulated;
     A.x = (const float*)u; A.n = (int)N; A.n1 = L / 2; A.padtype = SSQ_PAD_ZERO;
     SsqParams sp{};
-    switch (L) {
-        case 128: rc = launch_stft_fused<128, 32, 16, 8, 1, true>(A, sp, batch, stream); break;
-        case 256: rc = launch_stft_fused<256, 16, 16, 16, 1, true>(A, sp, batch, stream); break;
-        case 512: rc = launch_stft_fused<512, 8, 8, 8, 8, true>(A, sp, batch, stream); break;
-        case 1024: rc = launch_stft_fused<1024, 4, 16, 8, 8, true>(A, sp, batch, stream); break;
-        default: rc = launch_stft_fused<2048, 2, 16, 16, 8, true>(A, sp, batch, stream); break;
-    }
-    return rc;
+    return fft_dispatch<128, 2048>(L, [&](auto len) { return launch_stft_fused<decltype(len)::value, true>(A, sp, batch, stream); });
 }
 
 // gS[f][c] *= c_f / n_fft; the imaginary parts of DC and (even n_fft) Nyquist are exact zeros

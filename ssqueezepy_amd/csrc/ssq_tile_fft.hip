@@ -65,9 +65,10 @@ struct TileFftArgs {
 };
 
 // (bx, r, z): workgroup inside the class -- k1 group (pass 1) or q2 group (pass 2), row, signal
-template <int LB, int G, int R1, int R2, int R3>
+template <int LB>
 __device__ __forceinline__ void tilefft_pass1_body(const TileFftArgs& E, int bx, int r, int z_sig, c32* buf) {
-    constexpr int RL = (R3 > 1) ? R3 : R2;
+    using S = FftShape<LB>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;
     const int tid = threadIdx.x;
     const TileIRow row = E.irows[r];
     const int c0 = bx * G;                                  // first k1 of this workgroup
@@ -95,7 +96,7 @@ __device__ __forceinline__ void tilefft_pass1_body(const TileFftArgs& E, int bx,
             }
         }
     }
-    lds_ifft<LB, G, R1, R2, R3>(z, buf, E.ftw1, tid);
+    lds_ifft<LB>(z, buf, E.ftw1, tid);
     __syncthreads();
     constexpr int NBL = PPT / RL, STRL = LB / RL;
 #pragma unroll
@@ -112,7 +113,7 @@ __device__ __forceinline__ void tilefft_pass1_body(const TileFftArgs& E, int bx,
     }
     __syncthreads();
     const int G2 = E.G2, lg2 = __ffs(G2) - 1;
-    constexpr int LG = (G == 1) ? 0 : (G == 2) ? 1 : (G == 4) ? 2 : (G == 8) ? 3 : (G == 16) ? 4 : (G == 32) ? 5 : 6;
+    constexpr int LG = ilog2(G);
     c32* Yt = E.Y + ((int64_t)z_sig * E.nrows + r) * E.L;
 #pragma unroll
     for (int it = 0; it < PPT; ++it) {
@@ -123,9 +124,10 @@ __device__ __forceinline__ void tilefft_pass1_body(const TileFftArgs& E, int bx,
     }
 }
 
-template <int LA, int G, int R1, int R2, int R3>
+template <int LA>
 __device__ __forceinline__ void tilefft_pass2_body(const TileFftArgs& E, int bx, int r, int z_sig, c32* buf) {
-    constexpr int RL = (R3 > 1) ? R3 : R2;
+    using S = FftShape<LA>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL;
     const int tid = threadIdx.x;
     const TileIRow row = E.irows[r];
     const c32* Yr = E.Y + ((int64_t)z_sig * E.nrows + r) * E.L;
@@ -140,7 +142,7 @@ __device__ __forceinline__ void tilefft_pass2_body(const TileFftArgs& E, int bx,
                 z[it * R1 + k] = Yr[(int64_t)bx * LA * G + (u + k * STR) * G + g];     // blocked Y
         }
     }
-    lds_ifft<LA, G, R1, R2, R3>(z, buf, E.ftw2, tid);
+    lds_ifft<LA>(z, buf, E.ftw2, tid);
     c32* u_out = E.U + row.ubase + (int64_t)z_sig * row.sig_stride;
     constexpr int NB = PPT / RL, STR = LA / RL;
 #pragma unroll
@@ -169,34 +171,21 @@ __global__ __launch_bounds__(NT) void tilefft_four_kernel(TileFourArgs A) {
     const TileFftArgs& E = A.E[c];
     const int nx = A.nx[c];
     const int bx = b % nx, rz = b / nx, r = rz % E.nrows, z_sig = rz / E.nrows;
-    if (PASS == 1) {
-        switch (A.slot[c]) {
-            case 1: tilefft_pass1_body<128, 32, 16, 8, 1>(E, bx, r, z_sig, buf); break;
-            case 2: tilefft_pass1_body<256, 16, 16, 16, 1>(E, bx, r, z_sig, buf); break;
-            case 3: tilefft_pass1_body<512, 8, 8, 8, 8>(E, bx, r, z_sig, buf); break;
-            case 4: tilefft_pass1_body<1024, 4, 16, 8, 8>(E, bx, r, z_sig, buf); break;
-            default: tilefft_pass1_body<2048, 2, 16, 16, 8>(E, bx, r, z_sig, buf); break;
-        }
-    } else {
-        switch (A.slot[c]) {
-            case 0: tilefft_pass2_body<64, 64, 8, 8, 1>(E, bx, r, z_sig, buf); break;
-            case 1: tilefft_pass2_body<128, 32, 16, 8, 1>(E, bx, r, z_sig, buf); break;
-            case 2: tilefft_pass2_body<256, 16, 16, 16, 1>(E, bx, r, z_sig, buf); break;
-            case 3: tilefft_pass2_body<512, 8, 8, 8, 8>(E, bx, r, z_sig, buf); break;
-            case 4: tilefft_pass2_body<1024, 4, 16, 8, 8>(E, bx, r, z_sig, buf); break;
-            default: tilefft_pass2_body<2048, 2, 16, 16, 8>(E, bx, r, z_sig, buf); break;
-        }
-    }
+    // (slots count from 64 points; a class's pass 1 has at least 128)
+    if (PASS == 1)
+        fft_switch<128, 2048>(A.slot[c] - 1, [&](auto len) { tilefft_pass1_body<decltype(len)::value>(E, bx, r, z_sig, buf); });
+    else
+        fft_switch<64, 2048>(A.slot[c], [&](auto len) { tilefft_pass2_body<decltype(len)::value>(E, bx, r, z_sig, buf); });
 }
 
 // The short classes (64 .. 4096 entries per row) in one kernel: G (row, signal) pairs of a class
 // per workgroup, band -> LDS transform -> samples, transposed through LDS so that every row is
 // written as a run. Replaces the spectra kernel (a write of the zero-padded band) + a rocFFT launch
 // per class.
-template <int L, int G, int R1, int R2, int R3>
+template <int L>
 __device__ __forceinline__ void tilefft_small_body(const TileFftArgs& E, int npairs, int block, c32* buf) {
-    constexpr int RL = (R3 > 1) ? R3 : R2;
-    constexpr int LGL = (L == 64) ? 6 : (L == 128) ? 7 : (L == 256) ? 8 : (L == 512) ? 9 : (L == 1024) ? 10 : (L == 2048) ? 11 : 12;
+    using S = FftShape<L>;
+    constexpr int G = S::G, R1 = S::R1, RL = S::RL, LGL = S::LOG2L;
     const int tid = threadIdx.x;
     const int half = L >> 1;
     c32 z[PPT];
@@ -226,7 +215,7 @@ __device__ __forceinline__ void tilefft_small_body(const TileFftArgs& E, int npa
             }
         }
     }
-    lds_ifft<L, G, R1, R2, R3>(z, buf, E.ftw1, tid);
+    lds_ifft<L>(z, buf, E.ftw1, tid);
     __syncthreads();
     constexpr int NBL = PPT / RL, STRL = L / RL;
 #pragma unroll
@@ -262,15 +251,7 @@ __global__ __launch_bounds__(NT) void tilefft_small_kernel(TileSmallArgs A) {
     int b = (int)blockIdx.x, c = 0;
     while (c + 1 < A.ncls && b >= A.first_block[c + 1]) ++c;
     b -= A.first_block[c];
-    switch (A.slot[c]) {
-        case 0: tilefft_small_body<64, 64, 8, 8, 1>(A.E[c], A.npairs[c], b, buf); break;
-        case 1: tilefft_small_body<128, 32, 16, 8, 1>(A.E[c], A.npairs[c], b, buf); break;
-        case 2: tilefft_small_body<256, 16, 16, 16, 1>(A.E[c], A.npairs[c], b, buf); break;
-        case 3: tilefft_small_body<512, 8, 8, 8, 8>(A.E[c], A.npairs[c], b, buf); break;
-        case 4: tilefft_small_body<1024, 4, 16, 8, 8>(A.E[c], A.npairs[c], b, buf); break;
-        case 5: tilefft_small_body<2048, 2, 16, 16, 8>(A.E[c], A.npairs[c], b, buf); break;
-        default: tilefft_small_body<4096, 1, 16, 16, 16>(A.E[c], A.npairs[c], b, buf); break;
-    }
+    fft_switch<64, 4096>(A.slot[c], [&](auto len) { tilefft_small_body<decltype(len)::value>(A.E[c], A.npairs[c], b, buf); });
 }
 
 // ---------------------------------------------------------------------------- host side
@@ -282,8 +263,7 @@ int TilePlan::spectra(int sig, int nsig, const void* xh_all, hipStream_t stream)
         for (int want = 6; want >= 0; --want)
             for (size_t c = 0; c < cls.size() && S.ncls < 7; ++c) {
                 if (cls[c].A || !cls[c].B) continue;
-                int sl = 0;
-                while ((64 << sl) < cls[c].L) ++sl;
+                const int sl = fft_slot(cls[c].L, 64);
                 if (sl != want) continue;
                 TileFftArgs& E = S.E[S.ncls];
                 E.xh = (const c32*)xh_all; E.xh_stride = M / 2 + 1; E.sig0 = sig;
@@ -317,9 +297,7 @@ int TilePlan::spectra(int sig, int nsig, const void* xh_all, hipStream_t stream)
             E.A = cls[c].A; E.B = cls[c].B; E.L = (int)cls[c].L; E.nrows = (int)cls[c].nrows;
             E.G2 = D_POINTS / E.A;                         // q2 columns per pass-2 workgroup
             E.inv_l = 1.0f / (float)cls[c].L; E.nyq = 0;
-            int sa = 0, sb = 0;                            // table slots: L' = 64 << slot
-            while ((64 << sa) < E.A) ++sa;
-            while ((64 << sb) < E.B) ++sb;
+            const int sa = fft_slot(E.A, 64), sb = fft_slot(E.B, 64);     // table slots: L' = 64 << slot
             E.ftw1 = (const c32*)ftw + ftw_off[sb]; E.ftw2 = (const c32*)ftw + ftw_off[sa];
             F1.E[k] = E; F2.E[k] = E;
             F1.slot[k] = sb; F2.slot[k] = sa;
@@ -375,10 +353,7 @@ int AnalyticFft::create(int64_t M_, int64_t max_batch_, int64_t& bytes) {
     for (int which = 0; which < 2; ++which) {
         const int Lp = which ? B : A;
         (which ? off_b : off_a) = (int64_t)tw.size() / 2;
-        for (int q = 0; q < Lp; ++q) {
-            const double a = 6.283185307179586 * (double)q / (double)Lp;
-            tw.push_back((float)std::cos(a)); tw.push_back((float)std::sin(a));
-        }
+        fft_twiddles(Lp, tw);
     }
     if ((rc = up(&ftw, tw.data(), tw.size() * 4))) return rc;
     // weights: 1 / M on bins [0, M / 2), half of it at the Nyquist bin (both exact: M is a power of two)
@@ -405,9 +380,7 @@ int AnalyticFft::run(const void* xh_all, void* xa, int64_t batch, hipStream_t st
     E.A = A; E.B = B; E.L = (int)M; E.nrows = 1; E.G2 = D_POINTS / A; E.nyq = 1;
     E.inv_l = 1.0f / (float)M;
     E.ftw1 = (const c32*)ftw + off_b; E.ftw2 = (const c32*)ftw + off_a;
-    int sa = 0, sb = 0;
-    while ((64 << sa) < A) ++sa;
-    while ((64 << sb) < B) ++sb;
+    const int sa = fft_slot(A, 64), sb = fft_slot(B, 64);
     TileFourArgs F2 = F;
     F.slot[0] = sb; F.nx[0] = A / (D_POINTS / B);
     F.first_block[1] = F.nx[0] * (int)batch;

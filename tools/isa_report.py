@@ -2,7 +2,9 @@
 """Static report of the compiled kernels (no GPU needed): compiles every translation unit of
 ssqueezepy_amd/csrc for gfx950 to assembly and prints, per kernel, registers, scratch (spills),
 static LDS, code size and the instruction mix.
-    python tools/isa_report.py [substring-filter] > profiles/rNN_isa_report.txt"""
+    python tools/isa_report.py [substring-filter] [--dump DIR] > profiles/rNN_isa_report.txt
+--dump DIR also writes every kernel's normalised body (comments stripped, local labels and mangled symbols
+replaced by fixed tokens) to DIR/<unit>/<demangled name>.s: two checkouts compare with `diff -r`."""
 import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,8 +19,19 @@ def demangle(names):
     return out.split('\n')
 
 
-def main(flt=''):
-    rows = []
+def normalised(body):
+    """A kernel's instructions without what differs between two builds of the same code: comments, the
+    numbering of local labels, the mangled names of kernels and their LDS arrays."""
+    out = []
+    for line in body.split('\n'):
+        line = re.sub(r'\.L\w+', '.L', re.sub(r'\b_Z\w+', 'SYM', line.split(';')[0])).rstrip()
+        if line.strip():
+            out.append(line)
+    return '\n'.join(out) + '\n'
+
+
+def main(flt='', dump=None):
+    rows, bodies = [], {}
     for src, extra in SOURCES:
         with tempfile.TemporaryDirectory() as td:
             asm = os.path.join(td, 'k.s')
@@ -43,6 +56,8 @@ def main(flt=''):
                        lds=sum(i.startswith('ds_') for i in ins),
                        vmem=sum(i.startswith(('global_', 'buffer_', 'flat_', 'scratch_')) for i in ins))
             meta[name].update(mix, n=len(ins))
+            full = re.search(r'^%s:[^\n]*\n(.*?)^\.Lfunc_end' % re.escape(name), text, re.S | re.M)
+            bodies[name] = full.group(1) if full else ''
             rows.append((src, name, meta[name]))
     names = demangle([r[1] for r in rows])
     print('%-22s %5s %5s %7s %7s %7s | %6s %6s %5s %5s  kernel' %
@@ -51,10 +66,17 @@ def main(flt=''):
         short = re.sub(r'\(.*', '', dn).replace('ssq::', '')
         if flt and flt not in short:
             continue
+        if dump:
+            os.makedirs(os.path.join(dump, src), exist_ok=True)
+            with open(os.path.join(dump, src, re.sub(r'[^\w<>,.-]', '_', short)[:200] + '.s'), 'w') as fh:
+                fh.write(normalised(bodies[name]))
         print('%-22s %5d %5d %7d %7d %7d | %6d %6d %5d %5d  %s' %
               (src, d.get('vgpr', 0), d.get('sgpr', 0), d['scratch'], d['ldsb'], d.get('n', 0),
                d.get('valu', 0), d.get('salu', 0), d.get('lds', 0), d.get('vmem', 0), short[:110]))
 
 
 if __name__ == '__main__':
-    main(sys.argv[1] if len(sys.argv) > 1 else '')
+    args = sys.argv[1:]
+    dump = args.pop(args.index('--dump') + 1) if '--dump' in args else None
+    args = [a for a in args if a != '--dump']
+    main(args[0] if args else '', dump)
