@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 108 (107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 109 (108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -97,6 +97,22 @@ int ssq_phase_cwt(int dtype, const void* Wx, const void* dWx, void* w,
 int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs,
                    void* w, int64_t batch, int64_t na, int64_t n, double gamma,
                    void* stream);
+
+/* Second-order phase transform of the STFT (ABI 109; Oberlin, Meignen, Perrier 2015; Behera, Meignen, Oberlin 2018;
+ * DESIGN.md section 4.5.3 states the definition). Five STFTs of one signal, (batch, rows, n) complex each, taken with the
+ * windows g, g' fs, g'' fs^2, tau g and tau g' fs (tau = the window's time axis in seconds, 0 at its centre):
+ *   w1  = Sfs[i] - Im(Vdg / Vg) / 2pi                                   first-order estimate, Hz
+ *   den = Vtg Vdg - Vtdg Vg
+ *   w2  = w1 - Im( (Vddg Vg - Vdg^2) Vtg / (den Vg) ) / 2pi             = Re(w1c - q Vtg / Vg), q the chirp rate
+ *   w   = |Vg| < gamma ? inf : |den| > chirp_tol |Vg|^2 ? |w2| : |w1|
+ * evaluated per point in float64 for both dtypes (float32 planes are promoted) and rounded once to `dtype`; the
+ * fallback |w1| is ssq_phase_stft's value bit for bit (float32 data: its float32 numerator and |Vg|^2).
+ * Sfs: (rows,) real; w: (batch, rows, n) real. One streaming pass: every plane read once, w written once. There is no
+ * counterpart in the reference. rows >= 2, batch, n >= 1, batch rows n < 2^32, chirp_tol >= 0 (+inf: first order
+ * everywhere). */
+int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg,
+                    const void* Vtdg, const void* Sfs, void* w, int64_t batch, int64_t rows, int64_t n,
+                    double gamma, double chirp_tol, void* stream);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` (the second-order map: no counterpart in the reference), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -228,6 +228,36 @@ def phase_stft_gpu(Sx, dSx, Sfs, gamma):
     w = torch.empty(Sx.shape, dtype=_real_of(Sx.dtype), device=Sx.device)
     check(lib.ssq_phase_stft(_CDT[Sx.dtype], _ptr(Sx), _ptr(dSx), _ptr(sfs), _ptr(w),
                              B, na, n, float(gamma), stream()))
+    return w
+
+
+def phase_stft2_gpu(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol=1e-3):
+    """Second-order phase transform of the STFT (`ssq_stft2_phase`, include/ssq_hip.h) from the
+    transforms taken with the windows ``g, g' fs, g'' fs^2, tau g, tau g' fs``, each (rows, n) or (B, rows, n)::
+
+        w1  = Sfs[i] - Im(Vdg / Vg) / 2pi
+        den = Vtg Vdg - Vtdg Vg
+        w2  = w1 - Im((Vddg Vg - Vdg^2) Vtg / (den Vg)) / 2pi
+        w   = inf where |Vg| < gamma else |w2| where |den| > chirp_tol |Vg|^2 else |w1|
+
+    evaluated in float64 per point for both precisions, rounded once to the planes' real dtype; a point that
+    falls back carries `phase_stft_gpu`'s value bit for bit (complex64: its float32 numerator and ``|Vg|^2``)."""
+    lib = _lib.load()
+    Vg = to_device(Vg)
+    if Vg.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Vg` must be complex64 or complex128 (got %s)" % Vg.dtype)
+    planes = [Vg] + [to_device(V, Vg.dtype) for V in (Vdg, Vddg, Vtg, Vtdg)]
+    for V in planes[1:]:
+        if V.shape != Vg.shape:
+            raise ValueError("the five transforms must share one shape (got %s and %s)"
+                             % (tuple(Vg.shape), tuple(V.shape)))
+    B, na, n = _shape3(Vg)
+    sfs = to_device(np.ascontiguousarray(np.asarray(Sfs).reshape(-1)), _real_of(Vg.dtype))
+    if sfs.numel() != na:
+        raise ValueError("`Sfs` must have one entry per row (%d != %d)" % (sfs.numel(), na))
+    w = torch.empty(Vg.shape, dtype=_real_of(Vg.dtype), device=Vg.device)
+    check(lib.ssq_stft2_phase(_CDT[Vg.dtype], *[_ptr(V) for V in planes], _ptr(sfs), _ptr(w), B, na, n,
+                              float(gamma), float(chirp_tol), stream()))
     return w
 
 

@@ -17,6 +17,7 @@
 //       Tx once -- no read-modify-write, no atomics, deterministic.
 //   accumulate_global_kernel fallback for `na` too large for an LDS tile.
 //   phase_kernel             w = |Im(dWx/Wx)|/2pi (CWT) or |Sfs - ...| (STFT).
+//   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
 #include "ssq_common.h"
 #include <cstdlib>
@@ -700,6 +701,85 @@ __global__ __launch_bounds__(256) void phase_kernel(const T* __restrict__ Wx,
     }
 }
 
+// ------------------------------------------------- second-order phase (STFT)
+// One point of ssq_stft2_phase (include/ssq_hip.h states the map): g, d, dd, t, td are the
+// transforms taken with the windows g, g' fs, g'' fs^2, tau g, tau g' fs. The second-order estimate and both thresholds
+// are float64 for both dtypes. A point that falls back carries phase_kernel's w bit for bit: the first-order term through
+// phase_ratio on the stored values -- for float32 data its float32 numerator and |Vg|^2, the reference's arithmetic --
+// so that chirp_tol = inf is phase_stft. Everything is computed and the thresholds select at the end: a point below
+// gamma may carry NaN on the way, never in the result.
+__device__ __forceinline__ double stft2_abs(double x, double y, float) { return sqrt(x * x + y * y); }   // (float32 data: the squares cannot leave float64's range)
+__device__ __forceinline__ double stft2_abs(double x, double y, double) { return hypot(x, y); }
+
+template <typename T>
+__device__ __forceinline__ T stft2_point(T g_re, T g_im, T d_re, T d_im, double ddr, double ddi, double tr, double ti,
+                                         double tdr, double tdi, double sfs, double gamma, double chirp_tol) {
+    const double gr = g_re, gi = g_im, dr = d_re, di = d_im;
+    const double m2 = gr * gr + gi * gi;
+    const double w1 = sfs - phase_ratio(dr, di, gr, gi);
+    const double w1_fallback = sizeof(T) == 4 ? sfs - phase_ratio(d_re, d_im, g_re, g_im) : w1;
+    // num = Vddg Vg - Vdg^2,  den = Vtg Vdg - Vtdg Vg
+    const double nr = (ddr * gr - ddi * gi) - (dr * dr - di * di);
+    const double ni = (ddr * gi + ddi * gr) - (dr * di + di * dr);
+    const double er = (tr * dr - ti * di) - (tdr * gr - tdi * gi);
+    const double ei = (tr * di + ti * dr) - (tdr * gi + tdi * gr);
+    // Im(P / Q), P = num Vtg, Q = den Vg, by Smith's division (no |Q|^2: float64 data may be tiny)
+    const double pr = nr * tr - ni * ti, pi = nr * ti + ni * tr;
+    const double qr = er * gr - ei * gi, qi = er * gi + ei * gr;
+    const bool wide = fabs(qr) >= fabs(qi);
+    const double rat = wide ? qi / qr : qr / qi;
+    const double scl = wide ? qr + qi * rat : qr * rat + qi;
+    const double im = (wide ? pi - pr * rat : pi * rat - pr) / scl;
+    const bool second = stft2_abs(er, ei, T(0)) > chirp_tol * m2;
+    double w = fabs(second ? w1 - im / SSQ_TWO_PI : w1_fallback);
+    if (stft2_abs(gr, gi, T(0)) < gamma) w = (double)INFINITY;
+    return (T)w;
+}
+
+// 16 bytes of a complex plane: two float32 points or one float64 point
+typedef float stft2_f4v __attribute__((ext_vector_type(4)));
+typedef float stft2_f2v __attribute__((ext_vector_type(2)));
+typedef double stft2_d2v __attribute__((ext_vector_type(2)));
+template <typename T> struct Stft2Vec;
+template <> struct Stft2Vec<float> { using load_t = stft2_f4v; using store_t = stft2_f2v; static constexpr int PTS = 2; };
+template <> struct Stft2Vec<double> { using load_t = stft2_d2v; using store_t = double; static constexpr int PTS = 1; };
+
+// Streaming map over the flat (batch, rows, n) index; a thread takes PTS adjacent points per step -- one 16-byte load
+// per plane (VEC; the host checks the alignment) or one point with element loads. The row of a point, for Sfs, comes
+// from one 32-bit division per step; the second point of a pair may begin the next row.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void stft2_phase_kernel(
+    const T* __restrict__ Vg, const T* __restrict__ Vdg, const T* __restrict__ Vddg, const T* __restrict__ Vtg,
+    const T* __restrict__ Vtdg, const T* __restrict__ Sfs, T* __restrict__ w, int64_t rows, int64_t n,
+    int64_t total, double gamma, double chirp_tol) {
+    constexpr int PTS = VEC ? Stft2Vec<T>::PTS : 1;
+    const int64_t steps = (total + PTS - 1) / PTS;
+    for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < steps; s += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t q = s * PTS;
+        const unsigned row = (unsigned)q / (unsigned)n;       // (the host guarantees total < 2^32)
+        const int64_t i = (int64_t)(row % (unsigned)rows), j = (int64_t)((unsigned)q - row * (unsigned)n);
+        if constexpr (PTS == 1) {
+            w[q] = stft2_point<T>(Vg[2 * q], Vg[2 * q + 1], Vdg[2 * q], Vdg[2 * q + 1], Vddg[2 * q], Vddg[2 * q + 1],
+                                  Vtg[2 * q], Vtg[2 * q + 1], Vtdg[2 * q], Vtdg[2 * q + 1], (double)Sfs[i], gamma,
+                                  chirp_tol);
+        } else if (q + PTS <= total) {
+            using load_t = typename Stft2Vec<T>::load_t;
+            const load_t g = reinterpret_cast<const load_t*>(Vg)[s], d = reinterpret_cast<const load_t*>(Vdg)[s],
+                         dd = reinterpret_cast<const load_t*>(Vddg)[s], t = reinterpret_cast<const load_t*>(Vtg)[s],
+                         td = reinterpret_cast<const load_t*>(Vtdg)[s];
+            const int64_t i1 = j + 1 < n ? i : (i + 1 < rows ? i + 1 : 0);
+            typename Stft2Vec<T>::store_t o;
+            o.x = stft2_point<T>(g.x, g.y, d.x, d.y, dd.x, dd.y, t.x, t.y, td.x, td.y, (double)Sfs[i], gamma, chirp_tol);
+            o.y = stft2_point<T>(g.z, g.w, d.z, d.w, dd.z, dd.w, t.z, t.w, td.z, td.w, (double)Sfs[i1], gamma, chirp_tol);
+            reinterpret_cast<typename Stft2Vec<T>::store_t*>(w)[s] = o;
+        } else {                                        // an odd total: the last point on its own
+            w[q] = stft2_point<T>(Vg[2 * q], Vg[2 * q + 1], Vdg[2 * q], Vdg[2 * q + 1], Vddg[2 * q], Vddg[2 * q + 1],
+                                  Vtg[2 * q], Vtg[2 * q + 1], Vtdg[2 * q], Vtdg[2 * q + 1], (double)Sfs[i], gamma,
+                                  chirp_tol);
+        }
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void replace_under_abs_kernel(T* __restrict__ w,
                                                                 const T* __restrict__ ref,
@@ -767,6 +847,23 @@ static inline unsigned stream_grid(int64_t total, int block = 256) {
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
+template <typename T>
+static void launch_stft2_phase(const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg, const void* Vtdg,
+                               const void* Sfs, void* w, int64_t rows, int64_t n, int64_t total, double gamma,
+                               double chirp_tol, hipStream_t stream) {
+    constexpr int PTS = Stft2Vec<T>::PTS;
+    // 16-byte loads need every plane on a 16-byte boundary (a caller's offset pointer need not be), the store of a
+    // step's results its own width
+    bool vec = ((uintptr_t)w % (PTS * sizeof(T))) == 0;
+    for (const void* p : {Vg, Vdg, Vddg, Vtg, Vtdg}) vec = vec && ((uintptr_t)p % 16) == 0;
+#define SSQ_STFT2(V, steps) hipLaunchKernelGGL((stft2_phase_kernel<T, V>), dim3(stream_grid(steps)), dim3(256), 0, stream, \
+        (const T*)Vg, (const T*)Vdg, (const T*)Vddg, (const T*)Vtg, (const T*)Vtdg, (const T*)Sfs, (T*)w, rows, n,          \
+        total, gamma, chirp_tol)
+    if (vec) SSQ_STFT2(true, (total + PTS - 1) / PTS);
+    else SSQ_STFT2(false, total);
+#undef SSQ_STFT2
+}
+
 }  // namespace ssq
 
 using namespace ssq;
@@ -779,7 +876,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 108; }   // 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 109; }   // 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -854,6 +951,26 @@ int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs, 
     else
         hipLaunchKernelGGL((phase_kernel<double, true>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
                            (const double*)Sx, (const double*)dSx, (const double*)Sfs, (double*)w, na, n, total, gamma);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg, const void* Vtdg,
+                    const void* Sfs, void* w, int64_t batch, int64_t rows, int64_t n, double gamma, double chirp_tol,
+                    void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(Vg && Vdg && Vddg && Vtg && Vtdg && Sfs && w, "ssq_stft2_phase: null pointer");
+    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "ssq_stft2_phase: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1",
+                (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(chirp_tol >= 0.0 && gamma >= 0.0, "ssq_stft2_phase: gamma and chirp_tol must be >= 0 (got %g, %g)",
+                gamma, chirp_tol);
+    // (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
+    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
+                "ssq_stft2_phase: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)rows,
+                (long long)n);
+    const int64_t total = batch * rows * n;
+    if (dtype == SSQ_F32) launch_stft2_phase<float>(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
+    else launch_stft2_phase<double>(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
     SSQ_LAUNCH_CHECK();
     return 0;
 }
