@@ -17,7 +17,7 @@ GRIDNAME = {0: 'log', 1: 'log-piecewise', 2: 'linear'}
 
 def oracle_ssq_cwt(orc, x, dtype, wavelet='gmw', scales='log', nv=None, fs=None,
                    padtype='reflect', flipud=True, gamma=None, get_w=False,
-                   typing=0, ssq=True, l1_norm=True, maprange='peak'):
+                   typing=0, ssq=True, l1_norm=True, maprange='peak', workers=None):
     if isinstance(wavelet, str):
         opts = {'dtype': dtype}
         if wavelet == 'gmw':
@@ -33,7 +33,8 @@ def oracle_ssq_cwt(orc, x, dtype, wavelet='gmw', scales='log', nv=None, fs=None,
     M, n1, n2 = pad_geometry(N) if padtype is not None else (N, 0, 0)
     Psih = wavelet(scale=sc, N=M, nohalf=False)
     xi = wavelet.xifn(1., M).reshape(-1)
-    Wx, dWx = orc.cwt(x, Psih, xi, dt, n1, N, derivative=True, padtype=padtype)
+    Wx, dWx = orc.cwt(x, Psih, xi, dt, n1, N, derivative=True, padtype=padtype,
+                      workers=workers)
     if not l1_norm:
         Wx = Wx * np.sqrt(sc).astype(Wx.dtype)
         dWx = dWx * np.sqrt(sc).astype(Wx.dtype)
@@ -57,6 +58,40 @@ def oracle_ssq_cwt(orc, x, dtype, wavelet='gmw', scales='log', nv=None, fs=None,
     out.update(Tx=Tx, ssq_freqs=ssq_freqs[::-1], const=const, grid=grid, params=p,
                gamma=gamma)
     return out
+
+
+def oracle_cwt_rows_float64(orc, x, scales, rows, wavelet='gmw', fs=None, workers=None,
+                            chunk=4):
+    """`Wx`, `dWx` (complex128, ``(len(rows), N)``) of the rows `rows` of a float32 transform,
+    computed in float64 FROM THE FLOAT32 BANK: the float32 wavelet's dense rows cast to float64
+    (the values a float32 plan holds), `xi` of the float64 wavelet, `x` rounded to float32, and
+    `oracle.cwt`, which computes in the bank's dtype. Against it a float32 result shows its
+    kernels' arithmetic and its method's truncation and nothing else -- a reference built from the
+    float64 wavelet differs from the float32 bank by 3e-6 .. 6e-6 of a row and hides both. A dense
+    float64 row of M = 2^22 entries is 32 MiB: rows are evaluated `chunk` at a time."""
+    opts = {'norm': 'bandpass'} if wavelet == 'gmw' else {}
+    wav32 = Wavelet((wavelet, dict(opts, dtype='float32')))
+    wav64 = Wavelet((wavelet, dict(opts, dtype='float64')))
+    N = x.shape[-1]
+    dt, *_ = _process_fs_and_t(fs, None, N)
+    M, n1, _ = pad_geometry(N)
+    sc = np.asarray(scales, dtype='float32').reshape(-1, 1)
+    xi = wav64.xifn(1., M).reshape(-1)
+    x64 = np.asarray(x).astype('float32').astype('float64')
+    rows = list(rows)
+    Wx = np.empty((len(rows), N), dtype='complex128')
+    dWx = np.empty((len(rows), N), dtype='complex128')
+    for c in range(0, len(rows), chunk):
+        Psih = wav32(scale=sc[rows[c:c + chunk]], N=M, nohalf=False).astype('float64')
+        Wx[c:c + chunk], dWx[c:c + chunk] = orc.cwt(x64, Psih, xi, dt, n1, N, derivative=True,
+                                                    workers=workers)
+    return Wx, dWx
+
+
+def row_errors(a, ref):
+    """max |a_i - ref_i| / max |ref_i| per row: the error of every row relative to the row's OWN
+    size (a row at 1e-3 of the array's maximum is invisible to a maximum over the array)."""
+    return np.abs(a - ref).max(axis=-1) / np.abs(ref).max(axis=-1)
 
 
 def oracle_ssq_stft(orc, x, dtype, window=None, n_fft=None, win_len=None, hop_len=1,
