@@ -53,9 +53,10 @@ MIN_CLASS_ROWS = 16   # a shorter run of rows with a decimation of its own joins
 MERGE_MAX_OCTAVES = 3 # ... when that costs it at most 8 times the samples it needs ...
 MERGE_MIN_ROWS = 64   # ... in a plan with at least this many interpolated rows
 COLS = 64             # columns per workgroup of the ordered tile kernel (one per lane)
-NA_MAX = 512          # rows: a packed record holds 9 bits of row; the float64 tile of the default
-                      # kernel (16 B per cell) takes 32 columns up to 318 rows, 16 columns beyond
-                      # (the ordered kernel, SSQ_TILE_ORDER=ordered, stops at 318 rows)
+NA_MAX = 512          # rows: a packed record holds 9 bits of row, so 511 at the most. The float64 tile of the
+                      # default kernels (16 B per cell, na + 1 rows in 160 KiB) takes 32 columns up to 319 rows
+                      # and 16 columns for 320 .. 511; the ordered kernel (SSQ_TILE_ORDER=ordered: 64 columns
+                      # of 8 B and 16 B of ticket words) stops at 318 rows (tests/test_gpu_tile_rows.py)
 RSUB = 4              # rows per step (TILE_G of the kernels)
 STEPS_PER_TICKET = 1  # (steps are handed out one at a time)
 KIND_READBACK, KIND_INTERP = 0, 1

@@ -3,7 +3,7 @@
 // Math and planning: ssqueezepy_amd/_tiles.py. The device code lives in four translation units:
 //   ssq_tile_fft.hip      the intermediates (decimated baseband samples of the interpolated rows; the analytic signal)
 //   ssq_tile_pair.hip     tile3_kernel -- float64 Tx tile in LDS, unordered ds_add_f64, two columns per lane: the default
-//   ssq_tile_f64.hip      tile2_kernel -- the same with one column per lane (16-column tiles for 319 .. 511 rows)
+//   ssq_tile_f64.hip      tile2_kernel -- the same with one column per lane (16-column tiles for 320 .. 511 rows)
 //   ssq_tile_ordered.hip  tile_kernel  -- float32 tile, terms added in the reference's row order by a ticket
 //                         (SSQ_TILE_ORDER=ordered: Tx bit for bit the CPU loop's)
 // (ssq_tile_dev.h: the device pieces they share.) Here: the tables the kernels walk (TilePlan::create), the choice
@@ -392,12 +392,13 @@ void TilePlan::destroy() {
 }
 
 // SSQ_TILE_ORDER = ordered: the ticketed kernel (float32 sums in the reference's order, bit for bit; na <=
-// 318); default: tile3_kernel, or tile2_kernel (float64 tile, unordered adds: the same bins, sums rounded once)
+// 318: tile_lds_bytes); default: tile3_kernel, or tile2_kernel (float64 tile, unordered adds: the same bins, sums
+// rounded once; 32 columns for na <= 319, 16 columns for 320 .. 511: tile2_lds_bytes)
 bool tile_ordered() { return reassign_ordered(); }
 int TilePlan::tile_kernel() const {
     const int ordered = tile_lds_bytes(na) <= 160 * 1024 ? 1 : 0;    // (its 64-column float32 tile fits the LDS)
     if (tile_ordered()) return ordered;
-    // tile3_kernel (two columns per lane): 32-column tiles (up to 318 rows); SSQ_DEBUG_TILE_PAIR=0 keeps tile2_kernel
+    // tile3_kernel (two columns per lane): 32-column tiles (up to 319 rows); SSQ_DEBUG_TILE_PAIR=0 keeps tile2_kernel
     const char* e = getenv("SSQ_DEBUG_TILE_PAIR");
     if (tile3_ok && cols2 == 32 && N >= 64 && !(e && atoi(e) == 0)) return 3;
     return tile2_ok ? 2 : ordered;

@@ -20,7 +20,7 @@
 //
 // So the tile is kept in float64 and every wavefront adds its terms as soon as it has them
 // (ds_add_f64, no return value): 16 bytes per cell, hence COLS = 32 columns per tile (16 when
-// na > 318) and 64 / COLS consecutive rows per wavefront instruction (lane = sub-row h x column).
+// na > 319) and 64 / COLS consecutive rows per wavefront instruction (lane = sub-row h x column).
 // Nothing orders the wavefronts inside a tile, so
 //   * a wavefront owns a CONTIGUOUS block of the tile's rows (cost-balanced by the host), the
 //     same block for every tile: consecutive rows share their decimation class, and the
@@ -55,7 +55,7 @@ namespace ssq {
 //     constant address space: the index is wavefront-uniform): the sub-rows are consecutive rows of
 //     one class, so a lane's addresses are scalar bases + per-lane constants;
 //   * one load of samples (or Wx + bin for rows read back) and one store of Wx per item, one
-//     16-byte-per-lane store of Tx per 4 (8) rows x COLS columns of a finished tile;
+//     8-byte-per-lane store of Tx per 2 (4) rows x COLS columns of a finished tile;
 //   * the interpolation weights stay in registers for the whole launch: a wavefront's block of
 //     rows spans at most two decimation classes (the host cuts the blocks that way), and a lane's
 //     weights depend on its column only through n mod R, the same for every tile of a workgroup
@@ -104,8 +104,9 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(TileWalkArgs A, SsqParam
     const auto* cstv = SSQ_CONST_PTR(w_t, A.cst);
 
     // ---- a tile's end: all terms in (barrier), every wavefront writes its share of the rows to
-    // Tx and clears them, tile free again (barrier). A lane takes two neighbouring columns of a row:
-    // one 16-byte store, a wavefront instruction = 128 / COLS rows (N even; otherwise column by column).
+    // Tx and clears them, tile free again (barrier). A lane takes one cell -- column c of sub-row h -- per round: an
+    // 8-byte store, a wavefront instruction = 64 / COLS rows, a round = NW * RPI rows of the workgroup. N even or
+    // odd alike; a signal's partial last tile goes column by column under a mask.
     auto finish_tile = [&](int tx, int sg) {
         SSQ_WG_BARRIER();
         float2* Tx = A.Tx + (int64_t)(A.sig0 + sg) * na * N;
@@ -390,8 +391,11 @@ int TilePlan::run_f64(int sig, int nsig, float* Wx, float* dWx, float* Tx, const
     const size_t lds = tile2_lds_bytes(na, cols2);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((160 * 1024) / lds, (size_t)(32 / TILE2_NW)));
     const int G = walk_grid((N + cols2 - 1) / cols2, cols2, per_cu, A);
-    return tile_dispatch(sp, dWx != nullptr, kdump != nullptr, [&](auto grid, auto d, auto cstk, auto k) {
-        if (cols2 == 32)
+    return tile_dispatch<2>(sp, dWx != nullptr, kdump != nullptr, [&](auto grid, auto d, auto cstk, auto k) {
+        // (the bin dump beside a double per row: built for the 16-column tile, whose rows pass 256)
+        if constexpr (k() && cstk() == 2) {
+            SSQ_REQUIRE(cols2 == 16, "bin dump with float64 weights per row: built for the 16-column tile (na >= 320)");
+        } else if (cols2 == 32)
             return tile_launch(tile2_kernel<grid(), d(), TILE2_NW, cstk(), 32, k()>, G, TILE2_NW, lds, A, sp, stream);
         return tile_launch(tile2_kernel<grid(), d(), TILE2_NW, cstk(), 16, k()>, G, TILE2_NW, lds, A, sp, stream);
     });

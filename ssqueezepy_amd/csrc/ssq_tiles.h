@@ -110,7 +110,8 @@ struct TilePlan {
     // The tile kernel `run` launches for this plan in the mode selected right now (environment read at every call):
     // 0 none, 1 the ordered one (SSQ_TILE_ORDER=ordered; also the stand-in when !tile2_ok), 2 tile2_kernel (items cut
     // into blocks of at most two classes: tile2_ok), 3 tile3_kernel (tile3_ok, 32-column tiles, N >= 64,
-    // SSQ_DEBUG_TILE_PAIR != 0). The ordered kernel needs its 64-column float32 tile inside the LDS (na <= 318).
+    // SSQ_DEBUG_TILE_PAIR != 0; na <= 319). The ordered kernel needs its 64-column float32 tile inside the LDS (na <= 318);
+    // tile2_kernel runs 32-column tiles up to 319 rows and 16-column tiles for 320 .. 511.
     int tile_kernel() const;
     int tile_cols() const;                  // columns per tile of that kernel (0: none can run)
     // Asked by the executor BEFORE it routes any row: a plan that is not usable takes the block kernels + the
@@ -164,8 +165,9 @@ struct TilePlan {
 // The one dispatch ladder: (sp.grid, dWx given, kind of the reassignment weights, bin dump) as compile-time tags
 // (std::integral_constant) for f(grid, store_d, cstk, store_k). CSTK: 0 one float (cst0), 1 a float per row, 2 a
 // double per row; STORE_K: diagnostic builds (ssq_cwt_plan_set_bin_dump), every point's bin as it is consumed
-// (BIN_DUMP = false: a kernel without them, f is never given store_k = true).
-template <bool BIN_DUMP = true, class F>
+// (BIN_DUMP = 0: a kernel without them, f is never given store_k = true; 1: for one weight per transform; 2: also for
+// a double per row, f(.., K2, true) -- the row-count tests' twin of the build that reads its weight by the row).
+template <int BIN_DUMP = 1, class F>
 int tile_dispatch(const SsqParams& sp, bool store_d, bool store_k, F&& f) {
     using std::integral_constant;
     using K0 = integral_constant<int, 0>; using K1 = integral_constant<int, 1>; using K2 = integral_constant<int, 2>;
@@ -173,9 +175,10 @@ int tile_dispatch(const SsqParams& sp, bool store_d, bool store_k, F&& f) {
         const int cstk = sp.cst_f64 ? 2 : (sp.cst_uniform ? 0 : 1);
         if (BIN_DUMP && store_k) {
             // the diagnostic builds exist for one weight per transform (the bins do not depend on the weights:
-            // 'log' scales, what the full-size index test runs)
+            // 'log' scales, what the full-size index test runs) and, where a kernel asks for them, for a double per row
+            if constexpr (BIN_DUMP >= 2) if (cstk == 2) return f(grid, d, K2{}, std::true_type{});
             SSQ_REQUIRE(cstk == 0, "bin dump: built for uniform reassignment weights ('log' scales)");
-            if constexpr (BIN_DUMP) return f(grid, d, K0{}, std::true_type{});
+            if constexpr (BIN_DUMP >= 1) return f(grid, d, K0{}, std::true_type{});
         }
         if (cstk == 0) return f(grid, d, K0{}, std::false_type{});
         if (cstk == 1) return f(grid, d, K1{}, std::false_type{});

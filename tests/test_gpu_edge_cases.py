@@ -382,8 +382,8 @@ def test_tile_kernel_every_instantiation(S, orc, case, tile_mode):
 
 def test_more_rows_than_the_32_column_tile_holds(S, orc, tile_mode):
     """456 rows -- `process_scales('log', N, nv=32)` without the `[:300]` of the benchmark --
-    exceed the 318 rows a 32-column float64 tile (and the ticketed kernel's 64-column float32 tile)
-    can keep in a CU's LDS: the default tile kernel then runs 16-column tiles, four rows per
+    exceed the 319 rows a 32-column float64 tile (318: the ticketed kernel's 64-column float32 tile)
+    can keep in a CU's LDS (tests/test_gpu_tile_rows.py pins both numbers): the default tile kernel then runs 16-column tiles, four rows per
     wavefront instruction. The ordered kernel has no such form: with `SSQ_TILE_ORDER=ordered` the plan
     reports no usable tile kernel (`tile_cols == 0`) and the call takes the block kernels + the ordered
     reassignment for every row -- decided before any row is routed (round-4 advisor: it used to fail

@@ -90,3 +90,41 @@ def test_interpolation_reproduces_the_full_length_transform():
         worst[1] = max(worst[1], np.abs(Dk - Dr).max() / np.abs(Dr).max())
     # method error only (float32 tables): well under the float32 FFT's own 2.5e-6
     assert worst[0] < 5e-7 and worst[1] < 2e-6, worst
+
+
+def _minimal_bank(na, M, K=4):
+    """`na` rows of K bins each, well below Nyquist: the least `plan_tiles` can plan from."""
+    off = (np.arange(na + 1) * K).astype(np.int64)
+    lo = (16 + np.arange(na)).astype(np.int64)
+    return np.ones(na * K, dtype=np.float32), off, lo
+
+
+def test_planner_refuses_at_the_tile_paths_limits():
+    """`plan_tiles` declines 512 rows and na * N = 2^29 points and plans 511 rows and one point less -- decided
+    before the bank is read, so a minimal one does -- and these are the numbers `TilePlan::create` requires
+    (csrc/ssq_cwt_tiles.hip): the packed records keep the row in 9 bits and byte offsets in 32."""
+    import os
+    import re
+    from ssqueezepy_amd import _tiles
+    assert _tiles.NA_MAX == 512
+
+    def plan(na, N, M):
+        vals, off, lo = _minimal_bank(na, M)
+        return plan_tiles(vals, off, lo, M, N, (M - N) // 2, 1.0, np.ones(na, bool), 1)
+
+    assert plan(512, 4201, 8192) is None
+    tp = plan(511, 4201, 8192)
+    assert tp is not None and tp['interp_rows'].sum() == 511
+    assert int(tp['rows'][:, 0].max()) == 510 and len(tp['rows']) == 512
+    na, M = 256, 1 << 22
+    assert na * (1 << 21) == 1 << 29
+    assert plan(na, 1 << 21, M) is None
+    tp = plan(na, (1 << 21) - 1, M)
+    assert tp is not None and tp['interp_rows'].sum() == na
+    src = open(os.path.join(os.path.dirname(_tiles.__file__), 'csrc', 'ssq_cwt_tiles.hip')).read()
+    m = re.search(r'SSQ_REQUIRE\(na \* N < \(\(int64_t\)1 << (\d+)\) && na < (\d+),', src)
+    assert m, "TilePlan::create no longer states its limits this way"
+    assert (int(m.group(1)), int(m.group(2))) == (29, _tiles.NA_MAX)
+    # ... and what the host checks them with
+    host = open(_tiles.__file__).read()
+    assert 'na >= NA_MAX or na * N >= 2 ** 29' in host
