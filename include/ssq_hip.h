@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 109 (108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 110 (109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -113,6 +113,34 @@ int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs,
 int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg,
                     const void* Vtdg, const void* Sfs, void* w, int64_t batch, int64_t rows, int64_t n,
                     double gamma, double chirp_tol, void* stream);
+
+/* Second-order phase transform of the CWT (ABI 110; Oberlin, Meignen 2017; DESIGN.md section 4.5.4 states the
+ * definition). Five planes, (batch, na, n) complex each, from three CWTs of one signal over real banks -- psih the
+ * wavelet in the frequency domain, w its argument (scale x radians per sample):
+ *   W, dW    Wx, dWx of the bank psih(w)           dW = fs ifft(i xi psih(a xi) xh), the time derivative per second
+ *   Wd, dWd  Wx, dWx of the bank psih'(w) = d psih / dw
+ *   dW3      dWx of the bank w psih(w)
+ * With r = scales[i] / fs (the scale of row i in seconds):
+ *   T   = -1j r Wd     dT = -1j r dWd     ddW = (1j / r) dW3        (T: the CWT taken with t psi(t); ddW: d^2 W / dt^2)
+ *   den = W (W + dT) - T dW
+ *   num = W ddW - dW^2                                               num / den / (2pi j): the chirp rate, Hz/s
+ *   w1  = Im(dW / W) / 2pi                                           first-order estimate, Hz
+ *   w2  = w1 - Im( num T / (den W) ) / 2pi
+ *   w   = |W| < gamma ? inf : |den| > chirp_tol |W|^2 ? |w2| : |w1|
+ * evaluated per point in float64 for both dtypes (float32 planes are promoted) and rounded once to `dtype`; the
+ * gamma test and the fallback |w1| are ssq_phase_cwt's bit for bit (float32 data: gamma and |W| in float32, the
+ * float32 numerator and |W|^2), so chirp_tol = +inf gives ssq_phase_cwt's w. den / W^2 is 1 on a tone and 0 on an
+ * impulse, where no chirp rate exists.
+ * scales: HOST array of na float64, read before the call returns: the entry checks it and keeps scale / fs and its
+ * reciprocal on the device, one small table per (device, fs, scales), the eight most recent. A call whose table exists
+ * only enqueues the kernel -- asynchronous like every other entry, and capturable into a graph; the first call with
+ * new scales uploads the table synchronously (hipMalloc, hipMemcpy) and must not be made under stream capture;
+ * w: (batch, na, n) real. One streaming pass: every plane
+ * read once, w written once. No counterpart in the reference. Refused, with w unwritten: batch, na or n < 1,
+ * batch na n >= 2^32, chirp_tol < 0 or NaN, fs <= 0 or not finite, a scale <= 0 or not finite. */
+int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, const void* dWd, const void* dW3,
+                   const double* scales, void* w, int64_t batch, int64_t na, int64_t n, double fs, double gamma,
+                   double chirp_tol, void* stream);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

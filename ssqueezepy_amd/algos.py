@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` (the second-order map: no counterpart in the reference), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -258,6 +258,40 @@ def phase_stft2_gpu(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol=1e-3):
     w = torch.empty(Vg.shape, dtype=_real_of(Vg.dtype), device=Vg.device)
     check(lib.ssq_stft2_phase(_CDT[Vg.dtype], *[_ptr(V) for V in planes], _ptr(sfs), _ptr(w), B, na, n,
                               float(gamma), float(chirp_tol), stream()))
+    return w
+
+
+def phase_cwt2_gpu(W, dW, Wd, dWd, dW3, scales, fs, gamma, chirp_tol=1e-3):
+    """Second-order phase transform of the CWT (`ssq_cwt2_phase`, include/ssq_hip.h) from the planes
+    ``Wx, dWx`` of the wavelet ``psih(w)``, ``Wx, dWx`` of ``psih'(w)`` and ``dWx`` of ``w psih(w)``
+    (`wavelets.derived_wavelets`), each (na, n) or (B, na, n); `scales` (na,) in samples, ``r = scales / fs``::
+
+        T   = -1j r Wd;  dT = -1j r dWd;  ddW = (1j / r) dW3
+        den = W (W + dT) - T dW
+        w1  = Im(dW / W) / 2pi
+        w2  = w1 - Im((W ddW - dW^2) T / (den W)) / 2pi
+        w   = inf where |W| < gamma else |w2| where |den| > chirp_tol |W|^2 else |w1|
+
+    evaluated in float64 per point for both precisions, rounded once to the planes' real dtype; the infinities and
+    the points that fall back are `phase_cwt_gpu`'s bit for bit (complex64: its float32 numerator and ``|W|^2``)."""
+    lib = _lib.load()
+    W = to_device(W)
+    if W.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`W` must be complex64 or complex128 (got %s)" % W.dtype)
+    planes = [W] + [to_device(V, W.dtype) for V in (dW, Wd, dWd, dW3)]
+    for V in planes[1:]:
+        if V.shape != W.shape:
+            raise ValueError("the five transforms must share one shape (got %s and %s)"
+                             % (tuple(W.shape), tuple(V.shape)))
+    B, na, n = _shape3(W)
+    if hasattr(scales, 'detach'):
+        scales = scales.detach().cpu().numpy()
+    sc = np.ascontiguousarray(np.asarray(scales).reshape(-1), dtype=np.float64)     # a host array: the entry checks it
+    if sc.size != na:
+        raise ValueError("`scales` must have one entry per row (%d != %d)" % (sc.size, na))
+    w = torch.empty(W.shape, dtype=_real_of(W.dtype), device=W.device)
+    check(lib.ssq_cwt2_phase(_CDT[W.dtype], *[_ptr(V) for V in planes], sc.ctypes.data, _ptr(w), B, na, n,
+                             float(fs), float(gamma), float(chirp_tol), stream()))
     return w
 
 

@@ -18,8 +18,10 @@
 //   accumulate_global_kernel fallback for `na` too large for an LDS tile.
 //   phase_kernel             w = |Im(dWx/Wx)|/2pi (CWT) or |Sfs - ...| (STFT).
 //   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
+//   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
 #include "ssq_common.h"
+#include <cfloat>
 #include <cstdlib>
 #include <mutex>
 #include <string>
@@ -711,6 +713,14 @@ __global__ __launch_bounds__(256) void phase_kernel(const T* __restrict__ Wx,
 __device__ __forceinline__ double stft2_abs(double x, double y, float) { return sqrt(x * x + y * y); }   // (float32 data: the squares cannot leave float64's range)
 __device__ __forceinline__ double stft2_abs(double x, double y, double) { return hypot(x, y); }
 
+// Im(P / Q) by Smith's division
+__device__ __forceinline__ double smith_im(double pr, double pi, double qr, double qi) {
+    const bool wide = fabs(qr) >= fabs(qi);
+    const double rat = wide ? qi / qr : qr / qi;
+    const double scl = wide ? qr + qi * rat : qr * rat + qi;
+    return (wide ? pi - pr * rat : pi * rat - pr) / scl;
+}
+
 template <typename T>
 __device__ __forceinline__ T stft2_point(T g_re, T g_im, T d_re, T d_im, double ddr, double ddi, double tr, double ti,
                                          double tdr, double tdi, double sfs, double gamma, double chirp_tol) {
@@ -726,10 +736,7 @@ __device__ __forceinline__ T stft2_point(T g_re, T g_im, T d_re, T d_im, double 
     // Im(P / Q), P = num Vtg, Q = den Vg, by Smith's division (no |Q|^2: float64 data may be tiny)
     const double pr = nr * tr - ni * ti, pi = nr * ti + ni * tr;
     const double qr = er * gr - ei * gi, qi = er * gi + ei * gr;
-    const bool wide = fabs(qr) >= fabs(qi);
-    const double rat = wide ? qi / qr : qr / qi;
-    const double scl = wide ? qr + qi * rat : qr * rat + qi;
-    const double im = (wide ? pi - pr * rat : pi * rat - pr) / scl;
+    const double im = smith_im(pr, pi, qr, qi);
     const bool second = stft2_abs(er, ei, T(0)) > chirp_tol * m2;
     double w = fabs(second ? w1 - im / SSQ_TWO_PI : w1_fallback);
     if (stft2_abs(gr, gi, T(0)) < gamma) w = (double)INFINITY;
@@ -777,6 +784,96 @@ __global__ __launch_bounds__(256) void stft2_phase_kernel(
                                   Vtg[2 * q], Vtg[2 * q + 1], Vtdg[2 * q], Vtdg[2 * q + 1], (double)Sfs[i], gamma,
                                   chirp_tol);
         }
+    }
+}
+
+// -------------------------------------------------- second-order phase (CWT)
+// One point of ssq_cwt2_phase (include/ssq_hip.h states the map): g, d, wd, dwd, d3 are W, dW,
+// Wd, dWd, dW3; r = scale / fs of the point's row and ri = 1 / r. The constants -1j r and 1j / r are a swap, a sign and a
+// real product: T = -1j r Wd, dT = -1j r dWd, ddW = (1j / r) dW3. Types and selects as in stft2_point; the gamma test is
+// phase_kernel's own (mag_lt on the stored values, gamma in the data dtype) and the fallback its phase_ratio, so that
+// chirp_tol = inf is ssq_phase_cwt bit for bit, infinities included.
+template <typename T>
+__device__ __forceinline__ T cwt2_point(T g_re, T g_im, T d_re, T d_im, double wdr, double wdi, double dwdr, double dwdi,
+                                        double d3r, double d3i, double r, double ri, double gamma, double chirp_tol) {
+    const double gr = g_re, gi = g_im, dr = d_re, di = d_im;
+    const double tr = r * wdi, ti = -(r * wdr);
+    const double sr = gr + r * dwdi, si = gi - r * dwdr;              // W + dT
+    const double ddr = -(ri * d3i), ddi = ri * d3r;
+    const double m2 = gr * gr + gi * gi;
+    const double w1 = phase_ratio(dr, di, gr, gi);
+    const double w1_fallback = sizeof(T) == 4 ? phase_ratio(d_re, d_im, g_re, g_im) : w1;
+    // den = W (W + dT) - T dW,  num = W ddW - dW^2
+    const double er = (gr * sr - gi * si) - (tr * dr - ti * di);
+    const double ei = (gr * si + gi * sr) - (tr * di + ti * dr);
+    const double nr = (gr * ddr - gi * ddi) - (dr * dr - di * di);
+    const double ni = (gr * ddi + gi * ddr) - (dr * di + di * dr);
+    // Im(P / Q), P = num T, Q = den W (no |Q|^2: float64 data may be tiny)
+    const double pr = nr * tr - ni * ti, pi = nr * ti + ni * tr;
+    const double qr = er * gr - ei * gi, qi = er * gi + ei * gr;
+    const double im = smith_im(pr, pi, qr, qi);
+    const bool second = stft2_abs(er, ei, T(0)) > chirp_tol * m2;
+    double w = fabs(second ? w1 - im / SSQ_TWO_PI : w1_fallback);
+    if (mag_lt(g_re, g_im, (T)gamma)) w = (double)INFINITY;
+    return (T)w;
+}
+
+// Streaming map over the flat (batch, na, n) index; a thread takes PTS adjacent points per step, as stft2_phase_kernel
+// does -- one 16-byte load per plane (VEC; the host checks the alignment) or one point with element loads. `rtab`:
+// (na, 2) float64, scale / fs of a row and its reciprocal, made by the host entry. The row is per point: with n odd the
+// two complex64 points of one load belong to different rows. A thread divides once, for its first point; from then on
+// its (row, column) advance by the grid's constant stride (no division, and no reciprocal kept in registers, per step).
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) SSQ_WAVES_PER_EU(7, 8) void cwt2_phase_kernel(
+    const T* __restrict__ W, const T* __restrict__ dW, const T* __restrict__ Wd, const T* __restrict__ dWd,
+    const T* __restrict__ dW3, const double* __restrict__ rtab, T* __restrict__ w, int64_t na, int64_t n, int64_t total,
+    double gamma, double chirp_tol) {
+    constexpr int PTS = VEC ? Stft2Vec<T>::PTS : 1;
+    const int64_t steps = (total + PTS - 1) / PTS;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= steps) return;
+    // (the host guarantees total < 2^32; the grid has at most 2^21 threads)
+    const unsigned un = (unsigned)n, una = (unsigned)na, dq = (unsigned)stride * PTS;
+    const unsigned dj = dq % un, di = (dq / un) % una;
+    unsigned i, j;
+    {
+        const unsigned row = (unsigned)(s * PTS) / un;
+        i = row % una; j = (unsigned)(s * PTS) - row * un;
+    }
+    for (; s < steps; s += stride) {
+        const int64_t q = s * PTS;
+        const double r = rtab[2 * i], ri = rtab[2 * i + 1];
+        if constexpr (PTS == 2) {
+            if (q + PTS <= total) {
+                using load_t = typename Stft2Vec<T>::load_t;
+                const load_t g = reinterpret_cast<const load_t*>(W)[s], d = reinterpret_cast<const load_t*>(dW)[s],
+                             wd = reinterpret_cast<const load_t*>(Wd)[s], dwd = reinterpret_cast<const load_t*>(dWd)[s],
+                             d3 = reinterpret_cast<const load_t*>(dW3)[s];
+                const unsigned i1 = j + 1 < un ? i : (i + 1 < una ? i + 1 : 0);
+                const double r1 = rtab[2 * i1], ri1 = rtab[2 * i1 + 1];
+                typename Stft2Vec<T>::store_t o;
+                o.x = cwt2_point<T>(g.x, g.y, d.x, d.y, wd.x, wd.y, dwd.x, dwd.y, d3.x, d3.y, r, ri, gamma, chirp_tol);
+                o.y = cwt2_point<T>(g.z, g.w, d.z, d.w, wd.z, wd.w, dwd.z, dwd.w, d3.z, d3.w, r1, ri1, gamma, chirp_tol);
+                reinterpret_cast<typename Stft2Vec<T>::store_t*>(w)[s] = o;
+            } else {                                    // an odd total: the last point on its own
+                w[q] = cwt2_point<T>(W[2 * q], W[2 * q + 1], dW[2 * q], dW[2 * q + 1], Wd[2 * q], Wd[2 * q + 1],
+                                     dWd[2 * q], dWd[2 * q + 1], dW3[2 * q], dW3[2 * q + 1], r, ri, gamma, chirp_tol);
+            }
+        } else if constexpr (VEC) {                     // float64: a point is 16 bytes
+            using load_t = typename Stft2Vec<T>::load_t;
+            const load_t g = reinterpret_cast<const load_t*>(W)[q], d = reinterpret_cast<const load_t*>(dW)[q],
+                         wd = reinterpret_cast<const load_t*>(Wd)[q], dwd = reinterpret_cast<const load_t*>(dWd)[q],
+                         d3 = reinterpret_cast<const load_t*>(dW3)[q];
+            w[q] = cwt2_point<T>(g.x, g.y, d.x, d.y, wd.x, wd.y, dwd.x, dwd.y, d3.x, d3.y, r, ri, gamma, chirp_tol);
+        } else {
+            w[q] = cwt2_point<T>(W[2 * q], W[2 * q + 1], dW[2 * q], dW[2 * q + 1], Wd[2 * q], Wd[2 * q + 1], dWd[2 * q],
+                                 dWd[2 * q + 1], dW3[2 * q], dW3[2 * q + 1], r, ri, gamma, chirp_tol);
+        }
+        // (j + dj mod n and i + di + carry mod na, written so that nothing passes 2^32: n or na may be near it)
+        const unsigned carry = j >= un - dj, di1 = di + carry;
+        j = carry ? j - (un - dj) : j + dj;
+        i = i >= una - di1 ? i - (una - di1) : i + di1;
     }
 }
 
@@ -864,6 +961,21 @@ static void launch_stft2_phase(const void* Vg, const void* Vdg, const void* Vddg
 #undef SSQ_STFT2
 }
 
+template <typename T>
+static void launch_cwt2_phase(const void* W, const void* dW, const void* Wd, const void* dWd, const void* dW3,
+                              const double* rtab, void* w, int64_t na, int64_t n, int64_t total, double gamma,
+                              double chirp_tol, hipStream_t stream) {
+    constexpr int PTS = Stft2Vec<T>::PTS;
+    // as launch_stft2_phase: 16-byte loads only from 16-byte boundaries, the store of a step at its own width
+    bool vec = ((uintptr_t)w % (PTS * sizeof(T))) == 0;
+    for (const void* p : {W, dW, Wd, dWd, dW3}) vec = vec && ((uintptr_t)p % 16) == 0;
+#define SSQ_CWT2(V, steps) hipLaunchKernelGGL((cwt2_phase_kernel<T, V>), dim3(stream_grid(steps)), dim3(256), 0, stream, \
+        (const T*)W, (const T*)dW, (const T*)Wd, (const T*)dWd, (const T*)dW3, rtab, (T*)w, na, n, total, gamma, chirp_tol)
+    if (vec) SSQ_CWT2(true, (total + PTS - 1) / PTS);
+    else SSQ_CWT2(false, total);
+#undef SSQ_CWT2
+}
+
 }  // namespace ssq
 
 using namespace ssq;
@@ -876,7 +988,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 109; }   // 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 110; }   // 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -971,6 +1083,69 @@ int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg
     const int64_t total = batch * rows * n;
     if (dtype == SSQ_F32) launch_stft2_phase<float>(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
     else launch_stft2_phase<double>(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+// The rows' r = scale / fs and 1 / r in float64, (na, 2), on the current device: checked on the host, uploaded once per
+// (device, fs, scales) and kept -- a call that finds its table enqueues the kernel and nothing else (no allocation, no
+// copy, nothing for the host to wait for), so it can be captured into a graph once its table exists. The eight most
+// recent tables stay; an older one is freed with hipFree, which waits for the kernels that may still read it.
+struct Cwt2Table { int dev; double fs; std::vector<double> scales; double* rtab; };
+static std::mutex g_cwt2_mutex;
+static std::vector<Cwt2Table> g_cwt2_tables;
+
+static int cwt2_row_table(const double* scales, int64_t na, double fs, const double** out) {
+    std::vector<double> rtab((size_t)na * 2);
+    for (int64_t i = 0; i < na; ++i) {
+        const double r = scales[i] / fs;
+        SSQ_REQUIRE(scales[i] > 0.0 && r > 0.0 && r <= DBL_MAX && 1.0 / r > 0.0 && 1.0 / r <= DBL_MAX,
+                    "ssq_cwt2_phase: scales[%lld] = %g: scales must be positive (and scale / fs, fs / scale finite)",
+                    (long long)i, scales[i]);
+        rtab[2 * i] = r; rtab[2 * i + 1] = 1.0 / r;
+    }
+    int dev = 0;
+    SSQ_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_cwt2_mutex);
+    for (size_t k = 0; k < g_cwt2_tables.size(); ++k) {
+        const Cwt2Table& t = g_cwt2_tables[k];
+        if (t.dev == dev && t.fs == fs && (int64_t)t.scales.size() == na &&
+            memcmp(t.scales.data(), scales, (size_t)na * sizeof(double)) == 0) {
+            *out = t.rtab;
+            return 0;
+        }
+    }
+    if (g_cwt2_tables.size() >= 8) {
+        (void)hipFree(g_cwt2_tables.front().rtab);
+        g_cwt2_tables.erase(g_cwt2_tables.begin());
+    }
+    double* d = nullptr;
+    SSQ_CHECK_HIP(hipMalloc((void**)&d, rtab.size() * sizeof(double)));
+    hipError_t e = hipMemcpy(d, rtab.data(), rtab.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); SSQ_CHECK_HIP(e); }
+    g_cwt2_tables.push_back(Cwt2Table{dev, fs, std::vector<double>(scales, scales + na), d});
+    *out = d;
+    return 0;
+}
+
+int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, const void* dWd, const void* dW3,
+                   const double* scales, void* w, int64_t batch, int64_t na, int64_t n, double fs, double gamma,
+                   double chirp_tol, void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(W && dW && Wd && dWd && dW3 && scales && w, "ssq_cwt2_phase: null pointer");
+    SSQ_REQUIRE(batch >= 1 && na >= 1 && n >= 1, "ssq_cwt2_phase: bad shape (%lld, %lld, %lld): batch, na, n >= 1",
+                (long long)batch, (long long)na, (long long)n);
+    SSQ_REQUIRE(chirp_tol >= 0.0, "ssq_cwt2_phase: chirp_tol must be >= 0 (got %g)", chirp_tol);
+    SSQ_REQUIRE(fs > 0.0 && fs <= DBL_MAX, "ssq_cwt2_phase: fs must be positive and finite (got %g)", fs);
+    // (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
+    SSQ_REQUIRE(na <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (na * n),
+                "ssq_cwt2_phase: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)na,
+                (long long)n);
+    const int64_t total = batch * na * n;
+    const double* rdev = nullptr;
+    if (cwt2_row_table(scales, na, fs, &rdev)) return -1;
+    if (dtype == SSQ_F32) launch_cwt2_phase<float>(W, dW, Wd, dWd, dW3, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
+    else launch_cwt2_phase<double>(W, dW, Wd, dWd, dW3, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
     SSQ_LAUNCH_CHECK();
     return 0;
 }

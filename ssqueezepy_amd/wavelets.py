@@ -26,7 +26,7 @@ from .configs import fill_defaults
 pi = np.pi
 
 __all__ = ['Wavelet', 'center_frequency', 'xi_grid', 'find_maximum',
-           'find_first_occurrence', 'morsefreq']
+           'find_first_occurrence', 'morsefreq', 'derived_wavelets']
 
 
 # --------------------------------------------------------------------- grids
@@ -384,6 +384,84 @@ class Wavelet():
         self._Psih_N = N
         self._Psih_scale = np.array(scale, copy=True)
         return self._Psih
+
+
+# --------------------------------------------------- second-order companions
+_DERIVED = {}
+
+
+def _gmw_derivative(cfg, dt):
+    """``d psih / dw`` of the order-0 GMW `_make_gmw` builds from `cfg`: ``psih (beta / w - gamma w^(gamma-1))`` for
+    ``w > 0``, 0 elsewhere (both norms: the normalisation is a constant factor). With `centered_scale` the family
+    evaluates ``psih(wc w)``, whose derivative carries the factor `wc`."""
+    fn, _ = _make_gmw(**dict(cfg, dtype=dt))
+    wc_py = morsefreq(cfg['gamma'], cfg['beta'])
+    centered = bool(cfg['centered_scale'])
+    g, b, wc = _as0d(cfg['gamma'], cfg['beta'], wc_py, dtype=dt)
+
+    def gmw_dw(w):
+        w = np.atleast_1d(np.asarray(w, dtype=dt))
+        psih = np.asarray(fn(w), dtype=dt)
+        u = np.asarray(w * wc if centered else w, dtype=dt)
+        pos = (u > 0) & (psih != 0)
+        u = np.where(pos, u, 1)                 # (no 0 / 0 at w = 0, no 0 * inf where psih has underflowed)
+        with np.errstate(all='ignore'):
+            out = psih * (b / u - g * u**(g - 1))
+            if centered:
+                out = out * wc
+        return np.where(pos, out, 0).astype(dt)
+    return gmw_dw
+
+
+def _morlet_derivative(cfg, dt):
+    """``d psih / dw`` of `_make_morlet`'s ``C (exp(-(w - mu)^2 / 2) - ks exp(-w^2 / 2))``:
+    ``C (-(w - mu) exp(-(w - mu)^2 / 2) + ks w exp(-w^2 / 2))``."""
+    mu = cfg['mu']
+    cs = (1 + np.exp(-mu**2) - 2 * np.exp(-3 / 4 * mu**2)) ** (-.5)
+    ks = np.exp(-.5 * mu**2)
+    mu, cs, ks = _as0d(mu, cs, ks, dtype=dt)
+    C = np.asarray([-.5, np.sqrt(2) * cs * pi**.25], dtype=dt)
+
+    def morlet_dw(w):
+        w = np.atleast_1d(np.asarray(w, dtype=dt))
+        return C[1] * (ks * w * np.exp(C[0] * w**2) - (w - mu) * np.exp(C[0] * (w - mu)**2))
+    return morlet_dw
+
+
+def derived_wavelets(wavelet):
+    """The two companions of a built-in `wavelet` that the second-order synchrosqueezed CWT (`ssq_cwt2`) transforms
+    with: ``(Wavelet(w -> psih'(w)), Wavelet(w -> w psih(w)))``, `psih` being `wavelet.fn` -- the function of
+    ``scale * xi`` the transform samples, `centered_scale` included -- and ``psih' = d psih / dw``, in closed form.
+    Both are real, of `wavelet`'s dtype. Supported: ``'gmw'`` of order 0 (both norms) and ``'morlet'``. The pair is
+    made once per wavelet configuration, so that plans keyed by it are found again."""
+    supported = "supported: 'gmw' with order=0 (norm 'bandpass' or 'energy') and 'morlet'"
+    if not isinstance(wavelet, Wavelet):
+        raise TypeError("`wavelet` must be a Wavelet (got %s)" % type(wavelet))
+    if wavelet.family is None:
+        raise NotImplementedError("no closed-form derivative of a user-supplied wavelet function; " + supported)
+    if wavelet.family not in ('gmw', 'morlet'):
+        raise NotImplementedError("no closed-form derivative for the '%s' wavelet; %s" % (wavelet.family, supported))
+    if wavelet.family == 'gmw' and int(wavelet.config.get('order', 0)) != 0:
+        raise NotImplementedError("no closed-form derivative for a GMW of order %s; %s"
+                                  % (wavelet.config['order'], supported))
+    key = wavelet.key()
+    hit = _DERIVED.get(key)
+    if hit is not None:
+        return hit
+    dt = wavelet.dtype
+    make = _gmw_derivative if wavelet.family == 'gmw' else _morlet_derivative
+    cfg = {k: v for k, v in wavelet.config.items() if k != 'dtype'}
+    psih, dpsih = wavelet.fn, make(cfg, dt)
+
+    def w_psih(w):
+        w = np.atleast_1d(np.asarray(w, dtype=dt))
+        return (w * np.asarray(psih(w), dtype=dt)).astype(dt)
+    w_psih.__name__ = 'w_' + wavelet.family
+    out = (Wavelet(dpsih), Wavelet(w_psih))     # (their dtype: that of the functions' output, `dt`)
+    if len(_DERIVED) >= 16:
+        _DERIVED.pop(next(iter(_DERIVED)))
+    _DERIVED[key] = out
+    return out
 
 
 # ------------------------------------------------------------- 1-D searches
