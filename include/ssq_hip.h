@@ -107,8 +107,9 @@ int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs,
  *   w   = |Vg| < gamma ? inf : |den| > chirp_tol |Vg|^2 ? |w2| : |w1|
  * evaluated per point in float64 for both dtypes (float32 planes are promoted) and rounded once to `dtype`; the
  * fallback |w1| is ssq_phase_stft's value bit for bit (float32 data: its float32 numerator and |Vg|^2).
- * Sfs: (rows,) real; w: (batch, rows, n) real. One streaming pass: every plane read once, w written once. There is no
- * counterpart in the reference. rows >= 2, batch, n >= 1, batch rows n < 2^32, chirp_tol >= 0 (+inf: first order
+ * Sfs: (rows,) real; w: (batch, rows, n) real. One streaming pass: every plane read once, w written once. The gamma
+ * test is on |Vg| in float64 for both dtypes (ssq_cwt2_phase's is ssq_phase_cwt's). There is no counterpart in the
+ * reference. rows >= 2, batch, n >= 1, batch rows n < 2^32, chirp_tol >= 0 (+inf: first order
  * everywhere). */
 int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg,
                     const void* Vtdg, const void* Sfs, void* w, int64_t batch, int64_t rows, int64_t n,

@@ -231,6 +231,20 @@ def phase_stft_gpu(Sx, dSx, Sfs, gamma):
     return w
 
 
+def _five_planes(name, first, *rest):
+    """The five planes of a second-order map on the device in the complex dtype of `first` (`name` in the message),
+    their ``(B, rows, n)`` and the output plane `w`, allocated."""
+    first = to_device(first)
+    if first.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`%s` must be complex64 or complex128 (got %s)" % (name, first.dtype))
+    planes = [first] + [to_device(V, first.dtype) for V in rest]
+    for V in planes[1:]:
+        if V.shape != first.shape:
+            raise ValueError("the five transforms must share one shape (got %s and %s)"
+                             % (tuple(first.shape), tuple(V.shape)))
+    return planes, _shape3(first), torch.empty(first.shape, dtype=_real_of(first.dtype), device=first.device)
+
+
 def phase_stft2_gpu(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol=1e-3):
     """Second-order phase transform of the STFT (`ssq_stft2_phase`, include/ssq_hip.h) from the
     transforms taken with the windows ``g, g' fs, g'' fs^2, tau g, tau g' fs``, each (rows, n) or (B, rows, n)::
@@ -243,20 +257,11 @@ def phase_stft2_gpu(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol=1e-3):
     evaluated in float64 per point for both precisions, rounded once to the planes' real dtype; a point that
     falls back carries `phase_stft_gpu`'s value bit for bit (complex64: its float32 numerator and ``|Vg|^2``)."""
     lib = _lib.load()
-    Vg = to_device(Vg)
-    if Vg.dtype not in (torch.complex64, torch.complex128):
-        raise TypeError("`Vg` must be complex64 or complex128 (got %s)" % Vg.dtype)
-    planes = [Vg] + [to_device(V, Vg.dtype) for V in (Vdg, Vddg, Vtg, Vtdg)]
-    for V in planes[1:]:
-        if V.shape != Vg.shape:
-            raise ValueError("the five transforms must share one shape (got %s and %s)"
-                             % (tuple(Vg.shape), tuple(V.shape)))
-    B, na, n = _shape3(Vg)
-    sfs = to_device(np.ascontiguousarray(np.asarray(Sfs).reshape(-1)), _real_of(Vg.dtype))
+    planes, (B, na, n), w = _five_planes('Vg', Vg, Vdg, Vddg, Vtg, Vtdg)
+    sfs = to_device(np.ascontiguousarray(np.asarray(Sfs).reshape(-1)), w.dtype)
     if sfs.numel() != na:
         raise ValueError("`Sfs` must have one entry per row (%d != %d)" % (sfs.numel(), na))
-    w = torch.empty(Vg.shape, dtype=_real_of(Vg.dtype), device=Vg.device)
-    check(lib.ssq_stft2_phase(_CDT[Vg.dtype], *[_ptr(V) for V in planes], _ptr(sfs), _ptr(w), B, na, n,
+    check(lib.ssq_stft2_phase(_CDT[w.dtype], *[_ptr(V) for V in planes], _ptr(sfs), _ptr(w), B, na, n,
                               float(gamma), float(chirp_tol), stream()))
     return w
 
@@ -275,22 +280,13 @@ def phase_cwt2_gpu(W, dW, Wd, dWd, dW3, scales, fs, gamma, chirp_tol=1e-3):
     evaluated in float64 per point for both precisions, rounded once to the planes' real dtype; the infinities and
     the points that fall back are `phase_cwt_gpu`'s bit for bit (complex64: its float32 numerator and ``|W|^2``)."""
     lib = _lib.load()
-    W = to_device(W)
-    if W.dtype not in (torch.complex64, torch.complex128):
-        raise TypeError("`W` must be complex64 or complex128 (got %s)" % W.dtype)
-    planes = [W] + [to_device(V, W.dtype) for V in (dW, Wd, dWd, dW3)]
-    for V in planes[1:]:
-        if V.shape != W.shape:
-            raise ValueError("the five transforms must share one shape (got %s and %s)"
-                             % (tuple(W.shape), tuple(V.shape)))
-    B, na, n = _shape3(W)
+    planes, (B, na, n), w = _five_planes('W', W, dW, Wd, dWd, dW3)
     if hasattr(scales, 'detach'):
         scales = scales.detach().cpu().numpy()
     sc = np.ascontiguousarray(np.asarray(scales).reshape(-1), dtype=np.float64)     # a host array: the entry checks it
     if sc.size != na:
         raise ValueError("`scales` must have one entry per row (%d != %d)" % (sc.size, na))
-    w = torch.empty(W.shape, dtype=_real_of(W.dtype), device=W.device)
-    check(lib.ssq_cwt2_phase(_CDT[W.dtype], *[_ptr(V) for V in planes], sc.ctypes.data, _ptr(w), B, na, n,
+    check(lib.ssq_cwt2_phase(_CDT[w.dtype], *[_ptr(V) for V in planes], sc.ctypes.data, _ptr(w), B, na, n,
                              float(fs), float(gamma), float(chirp_tol), stream()))
     return w
 

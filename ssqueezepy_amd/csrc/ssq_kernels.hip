@@ -19,6 +19,7 @@
 //   phase_kernel             w = |Im(dWx/Wx)|/2pi (CWT) or |Sfs - ...| (STFT).
 //   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
 //   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
+//       (They share Phase2Vec and launch_phase2; why not more: DESIGN.md section 4.5.3.)
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
 #include "ssq_common.h"
 #include <cfloat>
@@ -710,8 +711,8 @@ __global__ __launch_bounds__(256) void phase_kernel(const T* __restrict__ Wx,
 // phase_ratio on the stored values -- for float32 data its float32 numerator and |Vg|^2, the reference's arithmetic --
 // so that chirp_tol = inf is phase_stft. Everything is computed and the thresholds select at the end: a point below
 // gamma may carry NaN on the way, never in the result.
-__device__ __forceinline__ double stft2_abs(double x, double y, float) { return sqrt(x * x + y * y); }   // (float32 data: the squares cannot leave float64's range)
-__device__ __forceinline__ double stft2_abs(double x, double y, double) { return hypot(x, y); }
+__device__ __forceinline__ double phase2_abs(double x, double y, float) { return sqrt(x * x + y * y); }   // (float32 data: the squares cannot leave float64's range)
+__device__ __forceinline__ double phase2_abs(double x, double y, double) { return hypot(x, y); }
 
 // Im(P / Q) by Smith's division
 __device__ __forceinline__ double smith_im(double pr, double pi, double qr, double qi) {
@@ -737,19 +738,19 @@ __device__ __forceinline__ T stft2_point(T g_re, T g_im, T d_re, T d_im, double 
     const double pr = nr * tr - ni * ti, pi = nr * ti + ni * tr;
     const double qr = er * gr - ei * gi, qi = er * gi + ei * gr;
     const double im = smith_im(pr, pi, qr, qi);
-    const bool second = stft2_abs(er, ei, T(0)) > chirp_tol * m2;
+    const bool second = phase2_abs(er, ei, T(0)) > chirp_tol * m2;
     double w = fabs(second ? w1 - im / SSQ_TWO_PI : w1_fallback);
-    if (stft2_abs(gr, gi, T(0)) < gamma) w = (double)INFINITY;
+    if (phase2_abs(gr, gi, T(0)) < gamma) w = (double)INFINITY;
     return (T)w;
 }
 
 // 16 bytes of a complex plane: two float32 points or one float64 point
-typedef float stft2_f4v __attribute__((ext_vector_type(4)));
-typedef float stft2_f2v __attribute__((ext_vector_type(2)));
-typedef double stft2_d2v __attribute__((ext_vector_type(2)));
-template <typename T> struct Stft2Vec;
-template <> struct Stft2Vec<float> { using load_t = stft2_f4v; using store_t = stft2_f2v; static constexpr int PTS = 2; };
-template <> struct Stft2Vec<double> { using load_t = stft2_d2v; using store_t = double; static constexpr int PTS = 1; };
+typedef float phase2_f4v __attribute__((ext_vector_type(4)));
+typedef float phase2_f2v __attribute__((ext_vector_type(2)));
+typedef double phase2_d2v __attribute__((ext_vector_type(2)));
+template <typename T> struct Phase2Vec;
+template <> struct Phase2Vec<float> { using load_t = phase2_f4v; using store_t = phase2_f2v; static constexpr int PTS = 2; };
+template <> struct Phase2Vec<double> { using load_t = phase2_d2v; using store_t = double; static constexpr int PTS = 1; };
 
 // Streaming map over the flat (batch, rows, n) index; a thread takes PTS adjacent points per step -- one 16-byte load
 // per plane (VEC; the host checks the alignment) or one point with element loads. The row of a point, for Sfs, comes
@@ -759,7 +760,7 @@ __global__ __launch_bounds__(256) void stft2_phase_kernel(
     const T* __restrict__ Vg, const T* __restrict__ Vdg, const T* __restrict__ Vddg, const T* __restrict__ Vtg,
     const T* __restrict__ Vtdg, const T* __restrict__ Sfs, T* __restrict__ w, int64_t rows, int64_t n,
     int64_t total, double gamma, double chirp_tol) {
-    constexpr int PTS = VEC ? Stft2Vec<T>::PTS : 1;
+    constexpr int PTS = VEC ? Phase2Vec<T>::PTS : 1;
     const int64_t steps = (total + PTS - 1) / PTS;
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < steps; s += (int64_t)gridDim.x * blockDim.x) {
         const int64_t q = s * PTS;
@@ -770,15 +771,15 @@ __global__ __launch_bounds__(256) void stft2_phase_kernel(
                                   Vtg[2 * q], Vtg[2 * q + 1], Vtdg[2 * q], Vtdg[2 * q + 1], (double)Sfs[i], gamma,
                                   chirp_tol);
         } else if (q + PTS <= total) {
-            using load_t = typename Stft2Vec<T>::load_t;
+            using load_t = typename Phase2Vec<T>::load_t;
             const load_t g = reinterpret_cast<const load_t*>(Vg)[s], d = reinterpret_cast<const load_t*>(Vdg)[s],
                          dd = reinterpret_cast<const load_t*>(Vddg)[s], t = reinterpret_cast<const load_t*>(Vtg)[s],
                          td = reinterpret_cast<const load_t*>(Vtdg)[s];
             const int64_t i1 = j + 1 < n ? i : (i + 1 < rows ? i + 1 : 0);
-            typename Stft2Vec<T>::store_t o;
+            typename Phase2Vec<T>::store_t o;
             o.x = stft2_point<T>(g.x, g.y, d.x, d.y, dd.x, dd.y, t.x, t.y, td.x, td.y, (double)Sfs[i], gamma, chirp_tol);
             o.y = stft2_point<T>(g.z, g.w, d.z, d.w, dd.z, dd.w, t.z, t.w, td.z, td.w, (double)Sfs[i1], gamma, chirp_tol);
-            reinterpret_cast<typename Stft2Vec<T>::store_t*>(w)[s] = o;
+            reinterpret_cast<typename Phase2Vec<T>::store_t*>(w)[s] = o;
         } else {                                        // an odd total: the last point on its own
             w[q] = stft2_point<T>(Vg[2 * q], Vg[2 * q + 1], Vdg[2 * q], Vdg[2 * q + 1], Vddg[2 * q], Vddg[2 * q + 1],
                                   Vtg[2 * q], Vtg[2 * q + 1], Vtdg[2 * q], Vtdg[2 * q + 1], (double)Sfs[i], gamma,
@@ -812,7 +813,7 @@ __device__ __forceinline__ T cwt2_point(T g_re, T g_im, T d_re, T d_im, double w
     const double pr = nr * tr - ni * ti, pi = nr * ti + ni * tr;
     const double qr = er * gr - ei * gi, qi = er * gi + ei * gr;
     const double im = smith_im(pr, pi, qr, qi);
-    const bool second = stft2_abs(er, ei, T(0)) > chirp_tol * m2;
+    const bool second = phase2_abs(er, ei, T(0)) > chirp_tol * m2;
     double w = fabs(second ? w1 - im / SSQ_TWO_PI : w1_fallback);
     if (mag_lt(g_re, g_im, (T)gamma)) w = (double)INFINITY;
     return (T)w;
@@ -828,7 +829,7 @@ __global__ __launch_bounds__(256) SSQ_WAVES_PER_EU(7, 8) void cwt2_phase_kernel(
     const T* __restrict__ W, const T* __restrict__ dW, const T* __restrict__ Wd, const T* __restrict__ dWd,
     const T* __restrict__ dW3, const double* __restrict__ rtab, T* __restrict__ w, int64_t na, int64_t n, int64_t total,
     double gamma, double chirp_tol) {
-    constexpr int PTS = VEC ? Stft2Vec<T>::PTS : 1;
+    constexpr int PTS = VEC ? Phase2Vec<T>::PTS : 1;
     const int64_t steps = (total + PTS - 1) / PTS;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -846,22 +847,22 @@ __global__ __launch_bounds__(256) SSQ_WAVES_PER_EU(7, 8) void cwt2_phase_kernel(
         const double r = rtab[2 * i], ri = rtab[2 * i + 1];
         if constexpr (PTS == 2) {
             if (q + PTS <= total) {
-                using load_t = typename Stft2Vec<T>::load_t;
+                using load_t = typename Phase2Vec<T>::load_t;
                 const load_t g = reinterpret_cast<const load_t*>(W)[s], d = reinterpret_cast<const load_t*>(dW)[s],
                              wd = reinterpret_cast<const load_t*>(Wd)[s], dwd = reinterpret_cast<const load_t*>(dWd)[s],
                              d3 = reinterpret_cast<const load_t*>(dW3)[s];
                 const unsigned i1 = j + 1 < un ? i : (i + 1 < una ? i + 1 : 0);
                 const double r1 = rtab[2 * i1], ri1 = rtab[2 * i1 + 1];
-                typename Stft2Vec<T>::store_t o;
+                typename Phase2Vec<T>::store_t o;
                 o.x = cwt2_point<T>(g.x, g.y, d.x, d.y, wd.x, wd.y, dwd.x, dwd.y, d3.x, d3.y, r, ri, gamma, chirp_tol);
                 o.y = cwt2_point<T>(g.z, g.w, d.z, d.w, wd.z, wd.w, dwd.z, dwd.w, d3.z, d3.w, r1, ri1, gamma, chirp_tol);
-                reinterpret_cast<typename Stft2Vec<T>::store_t*>(w)[s] = o;
+                reinterpret_cast<typename Phase2Vec<T>::store_t*>(w)[s] = o;
             } else {                                    // an odd total: the last point on its own
                 w[q] = cwt2_point<T>(W[2 * q], W[2 * q + 1], dW[2 * q], dW[2 * q + 1], Wd[2 * q], Wd[2 * q + 1],
                                      dWd[2 * q], dWd[2 * q + 1], dW3[2 * q], dW3[2 * q + 1], r, ri, gamma, chirp_tol);
             }
         } else if constexpr (VEC) {                     // float64: a point is 16 bytes
-            using load_t = typename Stft2Vec<T>::load_t;
+            using load_t = typename Phase2Vec<T>::load_t;
             const load_t g = reinterpret_cast<const load_t*>(W)[q], d = reinterpret_cast<const load_t*>(dW)[q],
                          wd = reinterpret_cast<const load_t*>(Wd)[q], dwd = reinterpret_cast<const load_t*>(dWd)[q],
                          d3 = reinterpret_cast<const load_t*>(dW3)[q];
@@ -944,36 +945,18 @@ static inline unsigned stream_grid(int64_t total, int block = 256) {
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-template <typename T>
-static void launch_stft2_phase(const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg, const void* Vtdg,
-                               const void* Sfs, void* w, int64_t rows, int64_t n, int64_t total, double gamma,
-                               double chirp_tol, hipStream_t stream) {
-    constexpr int PTS = Stft2Vec<T>::PTS;
+// Either second-order map: its kernel's 16-byte and element instances, its planes and its row table
+template <typename T, typename Tab, typename K>
+static void launch_phase2(K vec_kernel, K element_kernel, const void* const (&planes)[5], const Tab* tab, void* w,
+                          int64_t rows, int64_t n, int64_t total, double gamma, double chirp_tol, hipStream_t stream) {
+    constexpr int PTS = Phase2Vec<T>::PTS;
     // 16-byte loads need every plane on a 16-byte boundary (a caller's offset pointer need not be), the store of a
     // step's results its own width
     bool vec = ((uintptr_t)w % (PTS * sizeof(T))) == 0;
-    for (const void* p : {Vg, Vdg, Vddg, Vtg, Vtdg}) vec = vec && ((uintptr_t)p % 16) == 0;
-#define SSQ_STFT2(V, steps) hipLaunchKernelGGL((stft2_phase_kernel<T, V>), dim3(stream_grid(steps)), dim3(256), 0, stream, \
-        (const T*)Vg, (const T*)Vdg, (const T*)Vddg, (const T*)Vtg, (const T*)Vtdg, (const T*)Sfs, (T*)w, rows, n,          \
-        total, gamma, chirp_tol)
-    if (vec) SSQ_STFT2(true, (total + PTS - 1) / PTS);
-    else SSQ_STFT2(false, total);
-#undef SSQ_STFT2
-}
-
-template <typename T>
-static void launch_cwt2_phase(const void* W, const void* dW, const void* Wd, const void* dWd, const void* dW3,
-                              const double* rtab, void* w, int64_t na, int64_t n, int64_t total, double gamma,
-                              double chirp_tol, hipStream_t stream) {
-    constexpr int PTS = Stft2Vec<T>::PTS;
-    // as launch_stft2_phase: 16-byte loads only from 16-byte boundaries, the store of a step at its own width
-    bool vec = ((uintptr_t)w % (PTS * sizeof(T))) == 0;
-    for (const void* p : {W, dW, Wd, dWd, dW3}) vec = vec && ((uintptr_t)p % 16) == 0;
-#define SSQ_CWT2(V, steps) hipLaunchKernelGGL((cwt2_phase_kernel<T, V>), dim3(stream_grid(steps)), dim3(256), 0, stream, \
-        (const T*)W, (const T*)dW, (const T*)Wd, (const T*)dWd, (const T*)dW3, rtab, (T*)w, na, n, total, gamma, chirp_tol)
-    if (vec) SSQ_CWT2(true, (total + PTS - 1) / PTS);
-    else SSQ_CWT2(false, total);
-#undef SSQ_CWT2
+    for (const void* p : planes) vec = vec && ((uintptr_t)p % 16) == 0;
+    hipLaunchKernelGGL(vec ? vec_kernel : element_kernel, dim3(stream_grid(vec ? (total + PTS - 1) / PTS : total)),
+                       dim3(256), 0, stream, (const T*)planes[0], (const T*)planes[1], (const T*)planes[2],
+                       (const T*)planes[3], (const T*)planes[4], tab, (T*)w, rows, n, total, gamma, chirp_tol);
 }
 
 }  // namespace ssq
@@ -1067,22 +1050,30 @@ int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs, 
     return 0;
 }
 
+// What the two second-order entries check alike, in the order they always did (`entry` names the caller in the message)
+static int check_phase2(const char* entry, const void* const (&planes)[5], const void* tab, const void* w, int64_t batch,
+                        int64_t rows, int min_rows, int64_t n, double chirp_tol) {
+    SSQ_REQUIRE(planes[0] && planes[1] && planes[2] && planes[3] && planes[4] && tab && w, "%s: null pointer", entry);
+    SSQ_REQUIRE(batch >= 1 && rows >= min_rows && n >= 1, "%s: bad shape (%lld, %lld, %lld): rows >= %d, batch, n >= 1",
+                entry, (long long)batch, (long long)rows, (long long)n, min_rows);
+    SSQ_REQUIRE(chirp_tol >= 0.0, "%s: chirp_tol must be >= 0 (got %g)", entry, chirp_tol);
+    // (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
+    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
+                "%s: %lld x %lld x %lld points, at most 2^32 - 1", entry, (long long)batch, (long long)rows,
+                (long long)n);
+    return 0;
+}
+
 int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg, const void* Vtdg,
                     const void* Sfs, void* w, int64_t batch, int64_t rows, int64_t n, double gamma, double chirp_tol,
                     void* stream) {
     if (check_dtype(dtype)) return -1;
-    SSQ_REQUIRE(Vg && Vdg && Vddg && Vtg && Vtdg && Sfs && w, "ssq_stft2_phase: null pointer");
-    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "ssq_stft2_phase: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1",
-                (long long)batch, (long long)rows, (long long)n);
-    SSQ_REQUIRE(chirp_tol >= 0.0 && gamma >= 0.0, "ssq_stft2_phase: gamma and chirp_tol must be >= 0 (got %g, %g)",
-                gamma, chirp_tol);
-    // (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
-    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
-                "ssq_stft2_phase: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)rows,
-                (long long)n);
+    const void* const planes[5] = {Vg, Vdg, Vddg, Vtg, Vtdg};
+    if (check_phase2("ssq_stft2_phase", planes, Sfs, w, batch, rows, 2, n, chirp_tol)) return -1;
+    SSQ_REQUIRE(gamma >= 0.0, "ssq_stft2_phase: gamma must be >= 0 (got %g)", gamma);
     const int64_t total = batch * rows * n;
-    if (dtype == SSQ_F32) launch_stft2_phase<float>(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
-    else launch_stft2_phase<double>(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
+    if (dtype == SSQ_F32) launch_phase2<float>(stft2_phase_kernel<float, true>, stft2_phase_kernel<float, false>, planes, (const float*)Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
+    else launch_phase2<double>(stft2_phase_kernel<double, true>, stft2_phase_kernel<double, false>, planes, (const double*)Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -1132,20 +1123,14 @@ int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, con
                    const double* scales, void* w, int64_t batch, int64_t na, int64_t n, double fs, double gamma,
                    double chirp_tol, void* stream) {
     if (check_dtype(dtype)) return -1;
-    SSQ_REQUIRE(W && dW && Wd && dWd && dW3 && scales && w, "ssq_cwt2_phase: null pointer");
-    SSQ_REQUIRE(batch >= 1 && na >= 1 && n >= 1, "ssq_cwt2_phase: bad shape (%lld, %lld, %lld): batch, na, n >= 1",
-                (long long)batch, (long long)na, (long long)n);
-    SSQ_REQUIRE(chirp_tol >= 0.0, "ssq_cwt2_phase: chirp_tol must be >= 0 (got %g)", chirp_tol);
+    const void* const planes[5] = {W, dW, Wd, dWd, dW3};
+    if (check_phase2("ssq_cwt2_phase", planes, scales, w, batch, na, 1, n, chirp_tol)) return -1;
     SSQ_REQUIRE(fs > 0.0 && fs <= DBL_MAX, "ssq_cwt2_phase: fs must be positive and finite (got %g)", fs);
-    // (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
-    SSQ_REQUIRE(na <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (na * n),
-                "ssq_cwt2_phase: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)na,
-                (long long)n);
     const int64_t total = batch * na * n;
     const double* rdev = nullptr;
     if (cwt2_row_table(scales, na, fs, &rdev)) return -1;
-    if (dtype == SSQ_F32) launch_cwt2_phase<float>(W, dW, Wd, dWd, dW3, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
-    else launch_cwt2_phase<double>(W, dW, Wd, dWd, dW3, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
+    if (dtype == SSQ_F32) launch_phase2<float>(cwt2_phase_kernel<float, true>, cwt2_phase_kernel<float, false>, planes, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
+    else launch_phase2<double>(cwt2_phase_kernel<double, true>, cwt2_phase_kernel<double, false>, planes, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
     SSQ_LAUNCH_CHECK();
     return 0;
 }

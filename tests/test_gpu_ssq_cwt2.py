@@ -21,6 +21,8 @@ import os
 import numpy as np
 import pytest
 from conftest import report_measured
+import second_order
+from second_order import _np, default_gamma, _above_median
 
 pytestmark = pytest.mark.gpu
 DEV = 'cpu' if os.environ.get('SSQ_EMULATE') == '1' else 'cuda'
@@ -36,10 +38,6 @@ def S():
     yield from compute_module()
 
 
-def _np(t):
-    return t.detach().cpu().numpy() if hasattr(t, 'detach') else t
-
-
 def crossing_chirps(N, seed=0):
     """Two chirps that cross at 0.64 of the record, whatever its length, plus 1e-3 noise; `FS` Hz."""
     t = np.arange(N) / FS
@@ -47,10 +45,6 @@ def crossing_chirps(N, seed=0):
     noise = np.random.default_rng(seed).standard_normal(N)
     return (np.cos(2 * np.pi * (10 * t + 30 * t**2 / T)) + .7 * np.cos(2 * np.pi * (80 * t - 25 * t**2 / T))
             + 1e-3 * noise)
-
-
-def default_gamma(dtype):
-    return 10 * float(np.finfo(dtype).eps)
 
 
 def gmw(dtype, **kw):
@@ -93,38 +87,12 @@ def statement(W, dW, Wd, dWd, dW3, scales, fs, gamma, chirp_tol, ctype=np.comple
 
 
 def check_map(name, w_dev, planes, scales, fs, gamma, chirp_tol, rdtype, fallback32=False):
-    """`w_dev` against the float64 statement within ``8 E + spacing``; returns (E, measured max). `E` is
-    always that of the definition itself; with `fallback32` the reference carries `phase_cwt`'s float32
-    first-order value at the points that fall back."""
-    w64, ratio, aW = statement(*planes, scales, fs, gamma, chirp_tol)
-    if fallback32:
-        w64_ref, _, _ = statement(*planes, scales, fs, gamma, chirp_tol, fallback32=True)
-    else:
-        w64_ref = w64
-    wld, _, _ = statement(*planes, scales, fs, gamma, chirp_tol, np.clongdouble)
-    fin = np.isfinite(w64) & np.isfinite(wld)
-    with np.errstate(all='ignore'):
-        E = float(np.abs(w64 - wld.astype(np.float64))[fin].max()) if fin.any() else 0.
-        near = np.abs(aW - gamma) <= 1e-6 * gamma
-        if np.isfinite(chirp_tol):
-            near |= np.abs(ratio - chirp_tol) <= 1e-6 * chirp_tol
-    assert near.mean() <= 1e-4, (name, float(near.mean()))
-    w_ref = w64_ref.astype(rdtype)
-    keep = ~near
-    assert np.array_equal(np.isinf(w_dev)[keep], np.isinf(w_ref)[keep]), name
-    assert not np.isnan(w_dev).any(), name
-    both = keep & np.isfinite(w_ref)
-    with np.errstate(all='ignore'):
-        err = np.abs(w_dev.astype(np.float64) - w_ref.astype(np.float64))[both]
-        bound = (8 * E + np.spacing(w_ref).astype(np.float64))[both]
-    worst = float(err.max()) if err.size else 0.
-    with np.errstate(all='ignore'):
-        second = (np.abs(ratio) > chirp_tol) & both
-    report_measured(name, E=E, max_err=worst, excluded=int(near.sum()), n_inf=int(np.isinf(w_ref).sum()),
-                    n_second=int(second.sum()), n_first=int(both.sum() - second.sum()),
-                    max_err_over_bound=float((err / bound).max()) if err.size else 0.)
-    assert (err <= bound).all(), (name, E, worst)
-    return E, worst
+    """`second_order.check_map` on this module's `statement`; with `fallback32` the reference carries
+    `phase_cwt`'s float32 first-order value at the points that fall back."""
+    ref = statement(*planes, scales, fs, gamma, chirp_tol, fallback32=True)[0] if fallback32 else None
+    return second_order.check_map(name, w_dev, statement(*planes, scales, fs, gamma, chirp_tol),
+                                  statement(*planes, scales, fs, gamma, chirp_tol, np.clongdouble), gamma, chirp_tol,
+                                  rdtype, ref)
 
 
 def log_scales(N, na, dtype):
@@ -178,14 +146,6 @@ def test_map_vs_numpy_statement(S, shape, dtype):
         for b in range(batch):
             check_map('%s[%d]' % (name, b), _np(w)[b], [p[b] for p in planes], scales, FS, gamma, 1e-3,
                       np.dtype(dtype), fallback32=dtype == 'float32')
-
-
-def _above_median(v):
-    """A threshold "at the median" that is no sample itself: midway between the median sample and the
-    next one up (an odd count's median is a sample, and a point ON a threshold proves nothing)."""
-    v = np.sort(np.asarray(v, dtype=np.float64).reshape(-1))
-    k = len(v) // 2
-    return .5 * (v[k] + v[k + 1])
 
 
 @pytest.mark.parametrize('dtype', ['float32', 'float64'])
@@ -558,3 +518,44 @@ def test_offset_pointers_take_the_element_path(S, dtype, na=5, n=7):
     if DEV == 'cuda':
         torch.cuda.synchronize()
     assert torch.equal(wbuf[1:].reshape(na, n), ref)
+
+
+# ------------------------------------------- 7. the parent's bits, the walk
+@pytest.mark.parametrize('dtype', ['float32', 'float64'])
+@pytest.mark.parametrize('shape', second_order.PARENT_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+def test_parent_bits(S, shape, dtype):
+    """`w` on the planes of tests/golden/second_order_parent.npz, bit for bit what the parent commit's library gave
+    on the MI355X (recorded by tests/second_order.py)."""
+    second_order.assert_parent_bits(S, 'cwt', shape, dtype)
+
+
+@pytest.mark.parametrize('case', ['float32', 'float64', 'float32-offset'])
+def test_walk_second_trip(S, case, gamma=1., chirp_tol=1.):
+    """More steps than a launch has threads: the whole call against the same entry on blocks of rows
+    (`second_order.assert_walk`). `float32-offset`: every plane one element into its buffer, through the raw entry --
+    the element path's own second trip. Standard normal planes: `gamma` = 1 makes 39 % of the points `inf`; with
+    ``r = scales / fs`` <= 0.2, ``|den| / |W|^2`` scatters around 1, and `chirp_tol` = 1 splits the rest about evenly."""
+    import torch
+    from ssqueezepy_amd import _lib
+    dtype = case.split('-')[0]
+    planes = second_order.walk_planes(dtype, DEV, offset=int(case.endswith('offset')))
+    assert all(p.data_ptr() % 16 == (8 if case.endswith('offset') else 0) for p in planes)
+    scales = np.geomspace(2, 40, second_order.WALK_SHAPE[1])
+
+    def raw(planes, scales):
+        w = torch.empty(planes[0].shape, dtype=planes[0].real.dtype, device=DEV)
+        B, na, n = planes[0].shape if planes[0].ndim == 3 else (1,) + tuple(planes[0].shape)
+        sc = np.ascontiguousarray(scales, dtype=np.float64)
+        assert _lib.load().ssq_cwt2_phase(_lib.F32 if dtype == 'float32' else _lib.F64, *[p.data_ptr() for p in planes], sc.ctypes.data, w.data_ptr(), B,
+                                          na, n, FS, gamma, chirp_tol, None) == 0
+        if DEV == 'cuda':
+            torch.cuda.synchronize()
+        return w
+
+    def den(V, scales):
+        r = torch.as_tensor(scales / FS, dtype=V[0].real.dtype, device=DEV)[:, None]
+        return V[0] * (V[0] - 1j * r * V[3]) + 1j * r * V[2] * V[1]
+
+    second_order.assert_walk(raw if case.endswith('offset') else
+                             lambda planes, scales: S.phase_cwt2_gpu(*planes, scales, FS, gamma, chirp_tol),
+                             planes, scales, den, gamma, chirp_tol)

@@ -20,6 +20,8 @@ import os
 import numpy as np
 import pytest
 from conftest import report_measured
+import second_order
+from second_order import _np, default_gamma
 
 pytestmark = pytest.mark.gpu
 DEV = 'cpu' if os.environ.get('SSQ_EMULATE') == '1' else 'cuda'
@@ -34,10 +36,6 @@ def S():
     yield from compute_module()
 
 
-def _np(t):
-    return t.detach().cpu().numpy() if hasattr(t, 'detach') else t
-
-
 def gauss(n_fft, div):
     return np.exp(-.5 * ((np.arange(n_fft) - n_fft // 2) / (n_fft / div))**2)
 
@@ -47,10 +45,6 @@ def two_chirps_fs(N, seed=0):
     noise = np.random.default_rng(seed).standard_normal(N)
     return (np.cos(2 * np.pi * (10 * t + 6 * t**2)) + .7 * np.cos(2 * np.pi * (80 * t - 4.5 * t**2))
             + .05 * noise)
-
-
-def default_gamma(dtype):
-    return 10 * float(np.finfo(dtype).eps)
 
 
 def first_order_float32(Vg, Vdg, Sfs):
@@ -89,34 +83,12 @@ def statement(Vg, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol, ctype=np.complex1
 
 
 def check_map(name, w_dev, planes, Sfs, gamma, chirp_tol, rdtype, fallback32=False):
-    """`w_dev` against the float64 statement within ``8 E + spacing``; returns (E, measured max). `E` is
-    always that of the definition itself; with `fallback32` the reference carries `phase_stft`'s float32
-    first-order value at the points that fall back."""
-    w64, ratio, aVg = statement(*planes, Sfs, gamma, chirp_tol)
-    if fallback32:
-        w64_ref, _, _ = statement(*planes, Sfs, gamma, chirp_tol, fallback32=True)
-    else:
-        w64_ref = w64
-    wld, _, _ = statement(*planes, Sfs, gamma, chirp_tol, np.clongdouble)
-    fin = np.isfinite(w64) & np.isfinite(wld)
-    E = float(np.abs(w64 - wld.astype(np.float64))[fin].max()) if fin.any() else 0.
-    with np.errstate(all='ignore'):
-        near = np.abs(aVg - gamma) <= 1e-6 * gamma
-        if np.isfinite(chirp_tol):
-            near |= np.abs(ratio - chirp_tol) <= 1e-6 * chirp_tol
-    assert near.mean() <= 1e-4, (name, float(near.mean()))
-    w_ref = w64_ref.astype(rdtype)
-    keep = ~near
-    assert np.array_equal(np.isinf(w_dev)[keep], np.isinf(w_ref)[keep]), name
-    assert not np.isnan(w_dev).any(), name
-    both = keep & np.isfinite(w_ref)
-    err = np.abs(w_dev.astype(np.float64) - w_ref.astype(np.float64))[both]
-    bound = (8 * E + np.spacing(w_ref).astype(np.float64))[both]
-    worst = float(err.max()) if err.size else 0.
-    report_measured(name, E=E, max_err=worst, excluded=int(near.sum()), n_inf=int(np.isinf(w_ref).sum()),
-                    max_err_over_bound=float((err / bound).max()) if err.size else 0.)
-    assert (err <= bound).all(), (name, E, worst)
-    return E, worst
+    """`second_order.check_map` on this module's `statement`; with `fallback32` the reference carries
+    `phase_stft`'s float32 first-order value at the points that fall back."""
+    ref = statement(*planes, Sfs, gamma, chirp_tol, fallback32=True)[0] if fallback32 else None
+    return second_order.check_map(name, w_dev, statement(*planes, Sfs, gamma, chirp_tol),
+                                  statement(*planes, Sfs, gamma, chirp_tol, np.clongdouble), gamma, chirp_tol, rdtype,
+                                  ref)
 
 
 _PLANES = {}
@@ -400,3 +372,40 @@ def test_offset_pointers_take_the_element_path(S, dtype, rows=5, n=7):
     if DEV == 'cuda':
         torch.cuda.synchronize()
     assert torch.equal(w.reshape(rows, n), ref)
+
+
+# ------------------------------------------- 6. the parent's bits, the walk
+@pytest.mark.parametrize('dtype', ['float32', 'float64'])
+@pytest.mark.parametrize('shape', second_order.PARENT_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+def test_parent_bits(S, shape, dtype):
+    """`w` on the planes of tests/golden/second_order_parent.npz, bit for bit what the parent commit's library gave
+    on the MI355X (recorded by tests/second_order.py)."""
+    second_order.assert_parent_bits(S, 'stft', shape, dtype)
+
+
+@pytest.mark.parametrize('case', ['float32', 'float64', 'float32-offset'])
+def test_walk_second_trip(S, case, gamma=1., chirp_tol=.9):
+    """More steps than a launch has threads: the whole call against the same entry on blocks of rows
+    (`second_order.assert_walk`). `float32-offset`: every plane one element into its buffer, through the raw entry --
+    the element path's own second trip. Standard normal planes: `gamma` = 1 makes 39 % of the points `inf`,
+    `chirp_tol` = 0.9 splits the rest about evenly."""
+    import torch
+    from ssqueezepy_amd import _lib
+    dtype = case.split('-')[0]
+    planes = second_order.walk_planes(dtype, DEV, offset=int(case.endswith('offset')))
+    assert all(p.data_ptr() % 16 == (8 if case.endswith('offset') else 0) for p in planes)
+    Sfs = np.linspace(0, .5 * FS, second_order.WALK_SHAPE[1]).astype(dtype)
+
+    def raw(planes, Sfs):
+        w = torch.empty(planes[0].shape, dtype=planes[0].real.dtype, device=DEV)
+        B, rows, n = planes[0].shape if planes[0].ndim == 3 else (1,) + tuple(planes[0].shape)
+        sf = torch.as_tensor(Sfs, device=DEV)
+        assert _lib.load().ssq_stft2_phase(_lib.F32 if dtype == 'float32' else _lib.F64, *[p.data_ptr() for p in planes], sf.data_ptr(), w.data_ptr(), B,
+                                           rows, n, gamma, chirp_tol, None) == 0
+        if DEV == 'cuda':
+            torch.cuda.synchronize()
+        return w
+
+    second_order.assert_walk(raw if case.endswith('offset') else
+                             lambda planes, Sfs: S.phase_stft2_gpu(*planes, Sfs, gamma, chirp_tol),
+                             planes, Sfs, lambda V, Sfs: V[3] * V[1] - V[4] * V[0], gamma, chirp_tol)

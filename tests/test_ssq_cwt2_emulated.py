@@ -65,3 +65,9 @@ def test_abi_errors_leave_output_unwritten(S):
 @pytest.mark.parametrize('dtype', ['float32', 'float64'])
 def test_offset_pointers_take_the_element_path(S, dtype):
     T.test_offset_pointers_take_the_element_path(S, dtype)
+
+
+@pytest.mark.parametrize('dtype', ['float32', 'float64'])
+@pytest.mark.parametrize('shape', T.second_order.PARENT_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+def test_parent_bits(S, shape, dtype):
+    T.test_parent_bits(S, shape, dtype)
