@@ -153,6 +153,32 @@ void set_error(const char* fmt, ...);
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+// The one place where a call's data type picks the instantiation: `f(float{})` or `f(double{})`, a generic lambda
+// that takes the type from its argument (`using T = decltype(t)`); returns f's status. For sites whose two arms
+// are the same text but for the type -- an arm that differs in more stays written out.
+template <typename F>
+static inline int dispatch_dtype(int dtype, F&& f) { return dtype == SSQ_F32 ? f(float{}) : f(double{}); }
+
+// Stream-ordered temporaries of one host function: `alloc` is hipMallocAsync on the guard's stream, the
+// destructor hipFreeAsync on the same stream for everything handed out, in that order -- at every return.
+struct StreamScratch {
+    hipStream_t stream;
+    std::vector<void*> held;
+    explicit StreamScratch(hipStream_t s) : stream(s) {}
+    StreamScratch(const StreamScratch&) = delete;
+    StreamScratch& operator=(const StreamScratch&) = delete;
+    template <typename P>
+    int alloc(P** ptr, size_t bytes) {
+        void* p = nullptr;
+        *ptr = nullptr;
+        SSQ_CHECK_HIP(hipMallocAsync(&p, bytes, stream));
+        held.push_back(p);
+        *ptr = static_cast<P*>(p);
+        return 0;
+    }
+    ~StreamScratch() { for (void* p : held) (void)hipFreeAsync(p, stream); }
+};
+
 // A cached plan owns device workspaces that every execute reuses. Executes are asynchronous
 // and torch's side streams do not synchronise with each other, so two executes of one plan on
 // different streams (or from two host threads) would overwrite each other's workspace. `enter`

@@ -604,8 +604,9 @@ int ssq_cwt_execute(ssq_cwt_plan* pl, const void* x, int64_t batch, void* Wx, vo
     // (replaying the launches of small transforms from a hipGraph was built in round 2 and
     // measured slower than the eager launches on ROCm 7.2 -- config 1: 0.298 vs 0.126 ms -- so it
     // is gone; what helps small transforms is fewer launches)
-    const int rc = pl->d.dtype == SSQ_F32 ? cwt_execute_t<float>(pl, x, batch, Wx, dWx, Tx, w, rpadded, st)
-                                          : cwt_execute_t<double>(pl, x, batch, Wx, dWx, Tx, w, rpadded, st);
+    const int rc = dispatch_dtype(pl->d.dtype, [&](auto t) {
+        return cwt_execute_t<decltype(t)>(pl, x, batch, Wx, dWx, Tx, w, rpadded, st);
+    });
     pl->order.leave(st);
     return rc;
 }

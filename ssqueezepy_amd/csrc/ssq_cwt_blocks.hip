@@ -1135,12 +1135,14 @@ int BlockPlan::spectra(const void* xp, const void* xh, int64_t batch, hipStream_
             if (rc) return rc;
         } else {
             dim3 ga((unsigned)std::min<int64_t>((max_batch * M + 255) / 256, 4096));
-            if (dtype == SSQ_F32)
-                hipLaunchKernelGGL(analytic_spectrum_kernel<c32>, ga, dim3(256), 0, stream, (const c32*)xh, (c32*)xa, M, max_batch);
-            else
-                hipLaunchKernelGGL(analytic_spectrum_kernel<c64>, ga, dim3(256), 0, stream, (const c64*)xh, (c64*)xa, M, max_batch);
-            SSQ_LAUNCH_CHECK();
-            int rc = inv_m.execute(xa, nullptr, stream);
+            int rc = dispatch_dtype(dtype, [&](auto t) {
+                using C = cx<decltype(t)>;
+                hipLaunchKernelGGL(analytic_spectrum_kernel<C>, ga, dim3(256), 0, stream, (const C*)xh, (C*)xa, M, max_batch);
+                SSQ_LAUNCH_CHECK();
+                return 0;
+            });
+            if (rc) return rc;
+            rc = inv_m.execute(xa, nullptr, stream);
             if (rc) return rc;
         }
     }
@@ -1169,23 +1171,19 @@ int BlockPlan::spectra(const void* xp, const void* xh, int64_t batch, hipStream_
         int64_t most = 0;
         for (int c = lo[kind]; c <= hi[kind]; ++c) most = std::max<int64_t>(most, max_batch * hcls[c].nb * hcls[c].P);
         dim3 grid((unsigned)std::min<int64_t>((most + 255) / 256, 2048), (unsigned)(hi[kind] - lo[kind] + 1));
-        if (kind == 0) {
-            if (dtype == SSQ_F32)
-                hipLaunchKernelGGL((gather_blocks_kernel<float, false>), grid, dim3(256), 0, stream, (const float*)xp,
-                                   (float*)blocks, classes + lo[0], M, n1, max_batch);
+        const int rc = dispatch_dtype(dtype, [&](auto t) {
+            using T = decltype(t);
+            using C = cx<T>;
+            if (kind == 0)
+                hipLaunchKernelGGL((gather_blocks_kernel<T, false>), grid, dim3(256), 0, stream, (const T*)xp,
+                                   (T*)blocks, classes + lo[0], M, n1, max_batch);
             else
-                hipLaunchKernelGGL((gather_blocks_kernel<double, false>), grid, dim3(256), 0, stream, (const double*)xp,
-                                   (double*)blocks, classes + lo[0], M, n1, max_batch);
+                hipLaunchKernelGGL((gather_blocks_kernel<C, true>), grid, dim3(256), 0, stream, (const C*)xa,
+                                   (C*)xb, classes + lo[1], M, n1, max_batch);
             SSQ_LAUNCH_CHECK();
-        } else {
-            if (dtype == SSQ_F32)
-                hipLaunchKernelGGL((gather_blocks_kernel<c32, true>), grid, dim3(256), 0, stream, (const c32*)xa,
-                                   (c32*)xb, classes + lo[1], M, n1, max_batch);
-            else
-                hipLaunchKernelGGL((gather_blocks_kernel<c64, true>), grid, dim3(256), 0, stream, (const c64*)xa,
-                                   (c64*)xb, classes + lo[1], M, n1, max_batch);
-            SSQ_LAUNCH_CHECK();
-        }
+            return 0;
+        });
+        if (rc) return rc;
     }
     for (size_t f = 0; f < ffts.size(); ++f) {
         if (!run_on[f]) continue;

@@ -15,11 +15,8 @@
 #include "ssq_common.h"
 #include "ssq_fft.h"
 #include "ssq_stft.h"
-#include <rocfft/rocfft.h>
 #include <algorithm>
-#include <map>
 #include <mutex>
-#include <tuple>
 
 namespace ssq {
 
@@ -211,47 +208,34 @@ __global__ __launch_bounds__(256) void real_part_kernel(const T* __restrict__ S,
     if (k < n) out[k] = S[2 * k];
 }
 
-static std::mutex g_icwt2_mu;
-static std::map<std::tuple<int, int64_t, int64_t, hipStream_t>, std::pair<FftPlan, FftPlan>> g_icwt2_plans;
+static StreamPlanCache<FftPlanPair> g_icwt2_plans;
 
 template <typename T>
 static int icwt2_t(int dtype, void* Wp, const void* psih, void* out, int64_t na, int64_t n,
                    hipStream_t stream) {
     // plans (and their rocFFT work buffers) are per stream; the lock is held until everything
     // is enqueued, so two host threads cannot interleave set_stream / execute on one plan
-    std::pair<FftPlan, FftPlan>* pp = nullptr;
-    std::lock_guard<std::mutex> lock(g_icwt2_mu);
-    {
-        auto key = std::make_tuple(dtype, na, n, stream);
-        if (g_icwt2_plans.size() >= 16 && !g_icwt2_plans.count(key)) {
-            (void)hipDeviceSynchronize();
-            for (auto& kv : g_icwt2_plans) { kv.second.first.destroy(); kv.second.second.destroy(); }
-            g_icwt2_plans.clear();
-        }
-        auto it = g_icwt2_plans.find(key);
-        if (it == g_icwt2_plans.end()) {
-            std::pair<FftPlan, FftPlan> pr;
-            int rc = pr.first.create(2, dtype, (size_t)n, (size_t)na, 1.0);
-            if (rc) return rc;
-            rc = pr.second.create(1, dtype, (size_t)n, 1, 1.0 / (double)n);
-            if (rc) return rc;
-            it = g_icwt2_plans.emplace(key, pr).first;
-        }
-        pp = &it->second;
-    }
-    int rc = pp->first.execute(Wp, nullptr, stream);              // forward FFT of every row, in place
+    FftPlanPair* pp = nullptr;
+    std::lock_guard<std::mutex> lock(g_icwt2_plans.mu);
+    int rc = g_icwt2_plans.get(dtype, na, n, stream, &pp, [&](FftPlanPair& pr) {
+        const int r = pr.fwd.create(2, dtype, (size_t)n, (size_t)na, 1.0);
+        return r ? r : pr.inv.create(1, dtype, (size_t)n, 1, 1.0 / (double)n);
+    });
     if (rc) return rc;
+    rc = pp->fwd.execute(Wp, nullptr, stream);                    // forward FFT of every row, in place
+    if (rc) return rc;
+    StreamScratch scratch(stream);
     T* S = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&S, (size_t)n * 2 * sizeof(T), stream));
+    rc = scratch.alloc(&S, (size_t)n * 2 * sizeof(T));
+    if (rc) return rc;
     dim3 grid((unsigned)((n + 255) / 256));
     hipLaunchKernelGGL((mulsum_rows_kernel<T>), grid, dim3(256), 0, stream, (const T*)Wp, (const T*)psih, S, na, n);
-    rc = (hipGetLastError() == hipSuccess) ? pp->second.execute(S, nullptr, stream) : -3;
+    rc = (hipGetLastError() == hipSuccess) ? pp->inv.execute(S, nullptr, stream) : -3;
     if (!rc) {
         hipLaunchKernelGGL((real_part_kernel<T>), grid, dim3(256), 0, stream, (const T*)S, (T*)out, n);
         if (hipGetLastError() != hipSuccess) rc = -3;
     }
     if (rc == -3) set_error("icwt2 kernel launch failed");
-    (void)hipFreeAsync(S, stream);
     return rc;
 }
 
@@ -282,40 +266,26 @@ __global__ __launch_bounds__(256) void unpad_rows_kernel(const T* __restrict__ F
     }
 }
 
-static std::mutex g_trig_mu;
-static std::map<std::tuple<int, int64_t, int64_t, hipStream_t>, std::pair<FftPlan, FftPlan>> g_trig_plans;
+static StreamPlanCache<FftPlanPair> g_trig_plans;
 
 template <typename T>
 static int trigdiff_t(int dtype, void* Ap, const void* xi, double fs, void* out, int64_t rows,
                       int64_t n_up, int64_t n1, int64_t N, hipStream_t stream) {
-    std::pair<FftPlan, FftPlan>* pp = nullptr;
-    std::lock_guard<std::mutex> lock(g_trig_mu);          // per-stream plans; held until enqueued
-    {
-        auto key = std::make_tuple(dtype, rows, n_up, stream);
-        if (g_trig_plans.size() >= 16 && !g_trig_plans.count(key)) {
-            (void)hipDeviceSynchronize();
-            for (auto& kv : g_trig_plans) { kv.second.first.destroy(); kv.second.second.destroy(); }
-            g_trig_plans.clear();
-        }
-        auto it = g_trig_plans.find(key);
-        if (it == g_trig_plans.end()) {
-            std::pair<FftPlan, FftPlan> pr;
-            int rc = pr.first.create(2, dtype, (size_t)n_up, (size_t)rows, 1.0);
-            if (rc) return rc;
-            rc = pr.second.create(1, dtype, (size_t)n_up, (size_t)rows, 1.0 / (double)n_up);
-            if (rc) return rc;
-            it = g_trig_plans.emplace(key, pr).first;
-        }
-        pp = &it->second;
-    }
-    int rc = pp->first.execute(Ap, nullptr, stream);
+    FftPlanPair* pp = nullptr;
+    std::lock_guard<std::mutex> lock(g_trig_plans.mu);    // per-stream plans; held until enqueued
+    int rc = g_trig_plans.get(dtype, rows, n_up, stream, &pp, [&](FftPlanPair& pr) {
+        const int r = pr.fwd.create(2, dtype, (size_t)n_up, (size_t)rows, 1.0);
+        return r ? r : pr.inv.create(1, dtype, (size_t)n_up, (size_t)rows, 1.0 / (double)n_up);
+    });
+    if (rc) return rc;
+    rc = pp->fwd.execute(Ap, nullptr, stream);
     if (rc) return rc;
     const int64_t total = rows * n_up;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
     hipLaunchKernelGGL((mul_ixi_kernel<T>), dim3(blocks), dim3(256), 0, stream, (T*)Ap, (const T*)xi, (T)fs,
                        rows, n_up);
     SSQ_LAUNCH_CHECK();
-    rc = pp->second.execute(Ap, nullptr, stream);
+    rc = pp->inv.execute(Ap, nullptr, stream);
     if (rc) return rc;
     const unsigned blocks2 = (unsigned)std::min<int64_t>((rows * N + 255) / 256, 65536);
     hipLaunchKernelGGL((unpad_rows_kernel<T>), dim3(blocks2), dim3(256), 0, stream, (const T*)Ap, (T*)out, rows,
@@ -324,44 +294,16 @@ static int trigdiff_t(int dtype, void* Ap, const void* xi, double fs, void* out,
     return 0;
 }
 
-struct IstftFft {
-    rocfft_plan plan = nullptr; rocfft_execution_info info = nullptr; void* work = nullptr;
-};
-static std::mutex g_istft_mu;
-static std::map<std::tuple<int, int64_t, int64_t, hipStream_t>, IstftFft> g_istft_plans;   // one work buffer per stream
+// inverse real transforms of n_hops frames of n_fft samples: ssq_istft and the composed adjoint of the STFT
+static StreamPlanCache<FftPlan> g_istft_plans;             // one work buffer per stream
 
-// (the caller holds g_istft_mu until the transform is enqueued)
-static int istft_plan(int dtype, int64_t n_fft, int64_t n_hops, hipStream_t stream, IstftFft** out) {
-    auto key = std::make_tuple(dtype, n_fft, n_hops, stream);
-    if (g_istft_plans.size() >= 16 && !g_istft_plans.count(key)) {      // bounded cache
-        (void)hipDeviceSynchronize();
-        for (auto& kv : g_istft_plans) {
-            rocfft_execution_info_destroy(kv.second.info); rocfft_plan_destroy(kv.second.plan);
-            if (kv.second.work) (void)hipFree(kv.second.work);
-        }
-        g_istft_plans.clear();
-    }
-    auto it = g_istft_plans.find(key);
-    if (it == g_istft_plans.end()) {
-        if (fft_global_setup()) return -4;
-        IstftFft f;
-        size_t len = (size_t)n_fft;
-        rocfft_status st = rocfft_plan_create(&f.plan, rocfft_placement_notinplace,
-                rocfft_transform_type_real_inverse,
-                dtype == SSQ_F32 ? rocfft_precision_single : rocfft_precision_double, 1, &len,
-                (size_t)n_hops, nullptr);
-        if (st != rocfft_status_success) { set_error("rocfft_plan_create (istft) failed: %d", (int)st); return -4; }
-        size_t wb = 0;
-        rocfft_plan_get_work_buffer_size(f.plan, &wb);
-        rocfft_execution_info_create(&f.info);
-        if (wb) {
-            SSQ_CHECK_HIP(hipMalloc(&f.work, wb));
-            rocfft_execution_info_set_work_buffer(f.info, f.work, wb);
-        }
-        it = g_istft_plans.emplace(key, f).first;
-    }
-    *out = &it->second;
-    return 0;
+// (the caller holds g_istft_plans.mu until the transform is enqueued)
+static int istft_irfft(int dtype, int64_t n_fft, int64_t n_hops, void* St, void* frames, hipStream_t stream) {
+    FftPlan* f = nullptr;
+    const int rc = g_istft_plans.get(dtype, n_fft, n_hops, stream, &f, [&](FftPlan& p) {
+        return p.create(3, dtype, (size_t)n_fft, (size_t)n_hops, 1.0);
+    });
+    return rc ? rc : f->execute(St, frames, stream);
 }
 
 template <typename T>
@@ -369,35 +311,27 @@ static int istft_t(int dtype, const void* Sx, const void* win_a, const void* win
                    int64_t n_fft, int64_t n_hops, int64_t hop, int64_t N, int modulated,
                    hipStream_t stream) {
     const int64_t rows = n_fft / 2 + 1;
+    StreamScratch scratch(stream);
     T* St = nullptr; T* frames = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&St, (size_t)rows * n_hops * 2 * sizeof(T), stream));
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&frames, (size_t)(n_fft + 2) * n_hops * sizeof(T), stream));
+    int rc = scratch.alloc(&St, (size_t)rows * n_hops * 2 * sizeof(T));
+    if (!rc) rc = scratch.alloc(&frames, (size_t)(n_fft + 2) * n_hops * sizeof(T));
+    if (rc) return rc;
     const int64_t total = rows * n_hops;
     unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
     hipLaunchKernelGGL((spec_transpose_kernel<T>), dim3(g), dim3(256), 0, stream, (const T*)Sx, St, rows,
                        n_hops, (int)(n_fft % 2 == 0));
     SSQ_LAUNCH_CHECK();
-    IstftFft* f = nullptr;
-    std::unique_lock<std::mutex> lock(g_istft_mu);
-    int rc = istft_plan(dtype, n_fft, n_hops, stream, &f);
-    if (!rc) {
-        rocfft_execution_info_set_stream(f->info, stream);
-        void* ins[1] = {St}; void* outs[1] = {frames};
-        if (rocfft_execute(f->plan, ins, outs, f->info) != rocfft_status_success) {
-            set_error("rocfft_execute (istft) failed"); rc = -4;
-        }
+    {
+        std::lock_guard<std::mutex> lock(g_istft_plans.mu);
+        rc = istft_irfft(dtype, n_fft, n_hops, St, frames, stream);
     }
-    lock.unlock();
-    if (!rc) {
-        const T tiny = sizeof(T) == 4 ? (T)1.17549435e-38f : (T)2.2250738585072014e-308;
-        hipLaunchKernelGGL((istft_ola_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
-                           (const T*)frames, (const T*)win_a, (const T*)win_a1, (T*)x, n_fft, n_hops,
-                           hop, N, modulated, (T)(T(1) / (T)n_fft), tiny);
-        if (hipGetLastError() != hipSuccess) { set_error("istft_ola launch failed"); rc = -3; }
-    }
-    (void)hipFreeAsync(St, stream);
-    (void)hipFreeAsync(frames, stream);
-    return rc;
+    if (rc) return rc;
+    const T tiny = sizeof(T) == 4 ? (T)1.17549435e-38f : (T)2.2250738585072014e-308;
+    hipLaunchKernelGGL((istft_ola_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream,
+                       (const T*)frames, (const T*)win_a, (const T*)win_a1, (T*)x, n_fft, n_hops,
+                       hop, N, modulated, (T)(T(1) / (T)n_fft), tiny);
+    if (hipGetLastError() != hipSuccess) { set_error("istft_ola launch failed"); return -3; }
+    return 0;
 }
 
 // ---- batched inverse STFT and its backward ------------------------------------------------------------------
@@ -460,18 +394,17 @@ static int istft_batch_t(int dtype, const void* Sx, const void* win_a, const voi
                             n_fft, n_hops, hop, N, modulated, stream);
         return rc;
     }
+    StreamScratch scratch(stream);
     double* wn = nullptr; T* win_t = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&wn, (size_t)N * sizeof(double), stream));
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&win_t, (size_t)n_fft * sizeof(T), stream));
-    int rc = 0;
+    int rc = scratch.alloc(&wn, (size_t)N * sizeof(double));
+    if (!rc) rc = scratch.alloc(&win_t, (size_t)n_fft * sizeof(T));
+    if (rc) return rc;
     hipLaunchKernelGGL((istft_norm_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (const T*)win_a1,
                        wn, n_fft, hop, N);
     hipLaunchKernelGGL((window_rotate_kernel<T>), dim3((unsigned)((n_fft + 255) / 256)), dim3(256), 0, stream,
                        (const T*)win_a, win_t, n_fft, modulated);
     if (hipGetLastError() != hipSuccess) { set_error("istft norm / window launch failed"); rc = -3; }
     if (!rc) rc = istft_fused(Sx, win_t, wn, x, batch, n_fft, n_hops, hop, N, modulated, stream);
-    (void)hipFreeAsync(wn, stream);
-    (void)hipFreeAsync(win_t, stream);
     return rc;
 }
 
@@ -481,12 +414,13 @@ static int istft_adjoint_t(int dtype, const void* g, const void* win_a, const vo
     const bool fused = istft_takes_fused(dtype, n_fft, n_hops, hop, N);
     // fused: u (batch, N), the kernel extends it with zeros; composed: u between n_fft / 2 and the frames' end of zeros
     const int64_t lead = fused ? 0 : n_fft / 2, ulen = fused ? N : (n_hops - 1) * hop + n_fft;
+    StreamScratch scratch(stream);
     double* wn = nullptr; T* win_t = nullptr; T* u = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&wn, (size_t)N * sizeof(double), stream));
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&win_t, (size_t)n_fft * sizeof(T), stream));
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&u, (size_t)batch * ulen * sizeof(T), stream));
+    int rc = scratch.alloc(&wn, (size_t)N * sizeof(double));
+    if (!rc) rc = scratch.alloc(&win_t, (size_t)n_fft * sizeof(T));
+    if (!rc) rc = scratch.alloc(&u, (size_t)batch * ulen * sizeof(T));
+    if (rc) return rc;
     const T tiny = sizeof(T) == 4 ? (T)1.17549435e-38f : (T)2.2250738585072014e-308;
-    int rc = 0;
     hipLaunchKernelGGL((istft_norm_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (const T*)win_a1,
                        wn, n_fft, hop, N);
     hipLaunchKernelGGL((window_rotate_kernel<T>), dim3((unsigned)((n_fft + 255) / 256)), dim3(256), 0, stream,
@@ -496,9 +430,6 @@ static int istft_adjoint_t(int dtype, const void* g, const void* win_a, const vo
     if (hipGetLastError() != hipSuccess) { set_error("istft adjoint: norm / window / u launch failed"); rc = -3; }
     if (!rc) rc = fused ? istft_adjoint_fused(u, win_t, gSx, batch, n_fft, n_hops, hop, N, modulated, stream)
                         : istft_adjoint_composed(dtype, u, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated, stream);
-    (void)hipFreeAsync(wn, stream);
-    (void)hipFreeAsync(win_t, stream);
-    (void)hipFreeAsync(u, stream);
     return rc;
 }
 
@@ -545,11 +476,12 @@ static int stft_adjoint_composed_t(int dtype, const void* gSx, const void* gdSx,
                                    const void* diff_window, void* ypad, int64_t batch, int64_t n_fft, int64_t n_hops,
                                    int64_t hop, int64_t padlen, int modulated, hipStream_t stream) {
     const int64_t rows = n_fft / 2 + 1, total = rows * n_hops;
+    StreamScratch scratch(stream);
     T* St = nullptr; T* frames = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&St, (size_t)total * 2 * sizeof(T), stream));
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&frames, (size_t)(n_fft + 2) * n_hops * sizeof(T), stream));
+    int rc = scratch.alloc(&St, (size_t)total * 2 * sizeof(T));
+    if (!rc) rc = scratch.alloc(&frames, (size_t)(n_fft + 2) * n_hops * sizeof(T));
+    if (rc) return rc;
     const unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-    int rc = 0;
     for (int64_t b = 0; b < batch && !rc; ++b) {
         int accumulate = 0;
         for (int side = 0; side < 2 && !rc; ++side) {
@@ -559,16 +491,8 @@ static int stft_adjoint_composed_t(int dtype, const void* gSx, const void* gdSx,
                                src + (size_t)b * total * 2, St, rows, n_hops, (int)(n_fft % 2 == 0));
             if (hipGetLastError() != hipSuccess) { set_error("adjoint_spec_transpose launch failed"); rc = -3; break; }
             {
-                IstftFft* f = nullptr;
-                std::unique_lock<std::mutex> lock(g_istft_mu);
-                rc = istft_plan(dtype, n_fft, n_hops, stream, &f);
-                if (!rc) {
-                    rocfft_execution_info_set_stream(f->info, stream);
-                    void* ins[1] = {St}; void* outs[1] = {frames};
-                    if (rocfft_execute(f->plan, ins, outs, f->info) != rocfft_status_success) {
-                        set_error("rocfft_execute (stft adjoint) failed"); rc = -4;
-                    }
-                }
+                std::lock_guard<std::mutex> lock(g_istft_plans.mu);
+                rc = istft_irfft(dtype, n_fft, n_hops, St, frames, stream);
             }
             if (rc) break;
             hipLaunchKernelGGL((adjoint_ola_kernel<T>), dim3((unsigned)((padlen + 255) / 256)), dim3(256), 0, stream,
@@ -578,8 +502,6 @@ static int stft_adjoint_composed_t(int dtype, const void* gSx, const void* gdSx,
             accumulate = 1;
         }
     }
-    (void)hipFreeAsync(St, stream);
-    (void)hipFreeAsync(frames, stream);
     return rc;
 }
 
@@ -587,11 +509,10 @@ int stft_adjoint_composed(int dtype, const void* gSx, const void* gdSx, const vo
                           void* ypad, int64_t batch, int64_t n_fft, int64_t n_hops, int64_t hop, int64_t padlen,
                           int modulated, hipStream_t stream) {
     SSQ_REQUIRE(n_fft >= 2, "stft adjoint: n_fft %lld", (long long)n_fft);
-    if (dtype == SSQ_F32)
-        return stft_adjoint_composed_t<float>(dtype, gSx, gdSx, window, diff_window, ypad, batch, n_fft, n_hops, hop,
-                                              padlen, modulated, stream);
-    return stft_adjoint_composed_t<double>(dtype, gSx, gdSx, window, diff_window, ypad, batch, n_fft, n_hops, hop,
-                                           padlen, modulated, stream);
+    return dispatch_dtype(dtype, [&](auto t) {
+        return stft_adjoint_composed_t<decltype(t)>(dtype, gSx, gdSx, window, diff_window, ypad, batch, n_fft, n_hops,
+                                                    hop, padlen, modulated, stream);
+    });
 }
 
 }  // namespace ssq
@@ -608,13 +529,15 @@ int ssq_colsum(int dtype, const void* Z, const void* divisor, void* out, int64_t
                 (long long)batch, (long long)na, (long long)n);
     dim3 grid((unsigned)((n + 63) / 64), (unsigned)batch);
     hipStream_t s = as_stream(stream);
-#define LAUNCH(T, DIV) hipLaunchKernelGGL((colsum_kernel<T, DIV>), grid, dim3(64), 0, s, (const T*)Z, \
-                                          (const T*)divisor, (T*)out, na, n)
-    if (dtype == SSQ_F32) { if (divisor) LAUNCH(float, true); else LAUNCH(float, false); }
-    else { if (divisor) LAUNCH(double, true); else LAUNCH(double, false); }
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+#define LAUNCH(DIV) hipLaunchKernelGGL((colsum_kernel<T, DIV>), grid, dim3(64), 0, s, (const T*)Z, \
+                                       (const T*)divisor, (T*)out, na, n)
+        if (divisor) LAUNCH(true); else LAUNCH(false);
 #undef LAUNCH
-    SSQ_LAUNCH_CHECK();
-    return 0;
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_band_colsum(int dtype, const void* Z, const int32_t* lo, const int32_t* hi, int64_t ncomp,
@@ -634,14 +557,13 @@ int ssq_band_colsum_batch(int dtype, const void* Z, const int32_t* lo, const int
     dim3 grid((unsigned)((n + 255) / 256), (unsigned)(ncomp + 1), (unsigned)batch);
     const int64_t stride = bands_per_signal ? ncomp * n : 0;
     hipStream_t s = as_stream(stream);
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((band_colsum_kernel<float>), grid, dim3(256), 0, s, (const float*)Z, lo, hi,
-                           (int)ncomp, out, na, n, stride);
-    else
-        hipLaunchKernelGGL((band_colsum_kernel<double>), grid, dim3(256), 0, s, (const double*)Z, lo, hi,
-                           (int)ncomp, out, na, n, stride);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((band_colsum_kernel<T>), grid, dim3(256), 0, s, (const T*)Z, lo, hi, (int)ncomp, out, na, n,
+                           stride);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_band_colsum_adjoint(int dtype, const double* g, const int32_t* lo, const int32_t* hi, int bands_per_signal,
@@ -653,14 +575,13 @@ int ssq_band_colsum_adjoint(int dtype, const double* g, const int32_t* lo, const
     dim3 grid((unsigned)((n + 255) / 256), (unsigned)((na + CSA_ROWS - 1) / CSA_ROWS), (unsigned)batch);
     const int64_t stride = bands_per_signal ? ncomp * n : 0;
     hipStream_t s = as_stream(stream);
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((band_colsum_adjoint_kernel<float>), grid, dim3(256), 0, s, g, lo, hi, (int)ncomp,
-                           (float*)gZ, na, n, stride);
-    else
-        hipLaunchKernelGGL((band_colsum_adjoint_kernel<double>), grid, dim3(256), 0, s, g, lo, hi, (int)ncomp,
-                           (double*)gZ, na, n, stride);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((band_colsum_adjoint_kernel<T>), grid, dim3(256), 0, s, g, lo, hi, (int)ncomp, (T*)gZ, na, n,
+                           stride);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_colsum_adjoint(int dtype, const void* g, const void* divisor, void* gZ, int64_t batch, int64_t na,
@@ -688,8 +609,9 @@ int ssq_icwt2(int dtype, void* Wp, const void* psih, void* out, int64_t na, int6
     SSQ_REQUIRE(Wp && psih && out, "ssq_icwt2: null pointer");
     SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
     SSQ_REQUIRE(na >= 1 && n_up >= 2, "icwt2: bad shape (%lld, %lld)", (long long)na, (long long)n_up);
-    if (dtype == SSQ_F32) return icwt2_t<float>(dtype, Wp, psih, out, na, n_up, as_stream(stream));
-    return icwt2_t<double>(dtype, Wp, psih, out, na, n_up, as_stream(stream));
+    return dispatch_dtype(dtype, [&](auto t) {
+        return icwt2_t<decltype(t)>(dtype, Wp, psih, out, na, n_up, as_stream(stream));
+    });
 }
 
 int ssq_trigdiff(int dtype, void* Ap, const void* xi, double fs, void* out, int64_t rows, int64_t n_up,
@@ -699,8 +621,9 @@ int ssq_trigdiff(int dtype, void* Ap, const void* xi, double fs, void* out, int6
     SSQ_REQUIRE(rows >= 1 && n_up >= 2 && n1 >= 0 && N >= 1 && n1 + N <= n_up,
                 "trigdiff: bad shape (%lld, %lld) / slice (%lld, %lld)", (long long)rows, (long long)n_up,
                 (long long)n1, (long long)N);
-    if (dtype == SSQ_F32) return trigdiff_t<float>(dtype, Ap, xi, fs, out, rows, n_up, n1, N, as_stream(stream));
-    return trigdiff_t<double>(dtype, Ap, xi, fs, out, rows, n_up, n1, N, as_stream(stream));
+    return dispatch_dtype(dtype, [&](auto t) {
+        return trigdiff_t<decltype(t)>(dtype, Ap, xi, fs, out, rows, n_up, n1, N, as_stream(stream));
+    });
 }
 
 int ssq_istft(int dtype, const void* Sx, const void* win_a, const void* win_a1, void* x, int64_t n_fft,
@@ -708,9 +631,9 @@ int ssq_istft(int dtype, const void* Sx, const void* win_a, const void* win_a1, 
     SSQ_REQUIRE(Sx && win_a && win_a1 && x, "ssq_istft: null pointer");
     SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
     SSQ_REQUIRE(n_fft >= 2 && n_hops >= 1 && hop_len >= 1 && N >= 1, "istft: bad sizes");
-    if (dtype == SSQ_F32)
-        return istft_t<float>(dtype, Sx, win_a, win_a1, x, n_fft, n_hops, hop_len, N, modulated, as_stream(stream));
-    return istft_t<double>(dtype, Sx, win_a, win_a1, x, n_fft, n_hops, hop_len, N, modulated, as_stream(stream));
+    return dispatch_dtype(dtype, [&](auto t) {
+        return istft_t<decltype(t)>(dtype, Sx, win_a, win_a1, x, n_fft, n_hops, hop_len, N, modulated, as_stream(stream));
+    });
 }
 
 int ssq_istft_batch(int dtype, const void* Sx, const void* win_a, const void* win_a1, void* x, int64_t batch,
@@ -719,11 +642,10 @@ int ssq_istft_batch(int dtype, const void* Sx, const void* win_a, const void* wi
     SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
     SSQ_REQUIRE(n_fft >= 2 && n_hops >= 1 && hop_len >= 1 && N >= 1, "istft: bad sizes");
     SSQ_REQUIRE(batch >= 1 && batch <= 65535, "istft: batch %lld outside [1, 65535]", (long long)batch);
-    if (dtype == SSQ_F32)
-        return istft_batch_t<float>(dtype, Sx, win_a, win_a1, x, batch, n_fft, n_hops, hop_len, N, modulated,
-                                    as_stream(stream));
-    return istft_batch_t<double>(dtype, Sx, win_a, win_a1, x, batch, n_fft, n_hops, hop_len, N, modulated,
-                                 as_stream(stream));
+    return dispatch_dtype(dtype, [&](auto t) {
+        return istft_batch_t<decltype(t)>(dtype, Sx, win_a, win_a1, x, batch, n_fft, n_hops, hop_len, N, modulated,
+                                          as_stream(stream));
+    });
 }
 
 int ssq_istft_adjoint(int dtype, const void* g, const void* win_a, const void* win_a1, void* gSx, int64_t batch,
@@ -732,11 +654,10 @@ int ssq_istft_adjoint(int dtype, const void* g, const void* win_a, const void* w
     SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "bad dtype %d", dtype);
     SSQ_REQUIRE(n_fft >= 2 && n_hops >= 1 && hop_len >= 1 && N >= 1, "istft adjoint: bad sizes");
     SSQ_REQUIRE(batch >= 1 && batch <= 65535, "istft adjoint: batch %lld outside [1, 65535]", (long long)batch);
-    if (dtype == SSQ_F32)
-        return istft_adjoint_t<float>(dtype, g, win_a, win_a1, gSx, batch, n_fft, n_hops, hop_len, N, modulated,
-                                      as_stream(stream));
-    return istft_adjoint_t<double>(dtype, g, win_a, win_a1, gSx, batch, n_fft, n_hops, hop_len, N, modulated,
-                                   as_stream(stream));
+    return dispatch_dtype(dtype, [&](auto t) {
+        return istft_adjoint_t<decltype(t)>(dtype, g, win_a, win_a1, gSx, batch, n_fft, n_hops, hop_len, N, modulated,
+                                            as_stream(stream));
+    });
 }
 
 const char* ssq_istft_algo(int dtype, int64_t n_fft, int64_t n_hops, int64_t hop_len, int64_t N) {

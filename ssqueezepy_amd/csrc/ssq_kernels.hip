@@ -639,15 +639,14 @@ int launch_accumulate(int dtype, int binsrc, const void* Wx, const void* src, co
                 (long long)batch, (long long)na, (long long)n);
     SSQ_REQUIRE(batch <= 65535, "accumulate: batch %lld > 65535", (long long)batch);
     SSQ_REQUIRE(binsrc != BIN_FROM_KIDX || na < 65535, "bin map needs na < 65535");
-#define SSQ_ACC(T)                                                                                 \
-    switch (binsrc) {                                                                              \
-        case BIN_FROM_DWX: return launch_accumulate_b<T, BIN_FROM_DWX>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream); \
-        case BIN_FROM_W: return launch_accumulate_b<T, BIN_FROM_W>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);     \
-        default: return launch_accumulate_b<T, BIN_FROM_KIDX>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);          \
-    }
-    if (dtype == SSQ_F32) { SSQ_ACC(float) }
-    SSQ_ACC(double)
-#undef SSQ_ACC
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        switch (binsrc) {
+            case BIN_FROM_DWX: return launch_accumulate_b<T, BIN_FROM_DWX>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
+            case BIN_FROM_W: return launch_accumulate_b<T, BIN_FROM_W>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
+            default: return launch_accumulate_b<T, BIN_FROM_KIDX>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
+        }
+    });
 }
 
 // ------------------------------------------------- adjoint of the reassignment
@@ -1024,14 +1023,13 @@ int ssq_phase_cwt(int dtype, const void* Wx, const void* dWx, void* w, int64_t b
     SSQ_REQUIRE(Wx && dWx && w, "ssq_phase_cwt: null pointer");
     int64_t total = batch * na * n;
     if (total == 0) return 0;
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((phase_kernel<float, false>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const float*)Wx, (const float*)dWx, (const float*)nullptr, (float*)w, na, n, total, gamma);
-    else
-        hipLaunchKernelGGL((phase_kernel<double, false>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const double*)Wx, (const double*)dWx, (const double*)nullptr, (double*)w, na, n, total, gamma);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((phase_kernel<T, false>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
+                           (const T*)Wx, (const T*)dWx, (const T*)nullptr, (T*)w, na, n, total, gamma);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs, void* w,
@@ -1040,14 +1038,13 @@ int ssq_phase_stft(int dtype, const void* Sx, const void* dSx, const void* Sfs, 
     SSQ_REQUIRE(Sx && dSx && Sfs && w, "ssq_phase_stft: null pointer");
     int64_t total = batch * na * n;
     if (total == 0) return 0;
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((phase_kernel<float, true>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const float*)Sx, (const float*)dSx, (const float*)Sfs, (float*)w, na, n, total, gamma);
-    else
-        hipLaunchKernelGGL((phase_kernel<double, true>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const double*)Sx, (const double*)dSx, (const double*)Sfs, (double*)w, na, n, total, gamma);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((phase_kernel<T, true>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
+                           (const T*)Sx, (const T*)dSx, (const T*)Sfs, (T*)w, na, n, total, gamma);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // What the two second-order entries check alike, in the order they always did (`entry` names the caller in the message)
@@ -1072,10 +1069,13 @@ int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg
     if (check_phase2("ssq_stft2_phase", planes, Sfs, w, batch, rows, 2, n, chirp_tol)) return -1;
     SSQ_REQUIRE(gamma >= 0.0, "ssq_stft2_phase: gamma must be >= 0 (got %g)", gamma);
     const int64_t total = batch * rows * n;
-    if (dtype == SSQ_F32) launch_phase2<float>(stft2_phase_kernel<float, true>, stft2_phase_kernel<float, false>, planes, (const float*)Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
-    else launch_phase2<double>(stft2_phase_kernel<double, true>, stft2_phase_kernel<double, false>, planes, (const double*)Sfs, w, rows, n, total, gamma, chirp_tol, as_stream(stream));
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_phase2<T>(stft2_phase_kernel<T, true>, stft2_phase_kernel<T, false>, planes, (const T*)Sfs, w, rows, n, total,
+                         gamma, chirp_tol, as_stream(stream));
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // The rows' r = scale / fs and 1 / r in float64, (na, 2), on the current device: checked on the host, uploaded once per
@@ -1129,10 +1129,13 @@ int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, con
     const int64_t total = batch * na * n;
     const double* rdev = nullptr;
     if (cwt2_row_table(scales, na, fs, &rdev)) return -1;
-    if (dtype == SSQ_F32) launch_phase2<float>(cwt2_phase_kernel<float, true>, cwt2_phase_kernel<float, false>, planes, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
-    else launch_phase2<double>(cwt2_phase_kernel<double, true>, cwt2_phase_kernel<double, false>, planes, rdev, w, na, n, total, gamma, chirp_tol, as_stream(stream));
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_phase2<T>(cwt2_phase_kernel<T, true>, cwt2_phase_kernel<T, false>, planes, rdev, w, na, n, total, gamma,
+                         chirp_tol, as_stream(stream));
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 static int fill_params(SsqParams& sp, int grid, const double* params, int flipud, double gamma, int cst_f64) {
@@ -1192,14 +1195,13 @@ int ssq_replace_under_abs(int dtype, void* w, const void* ref, int64_t count, do
     if (check_dtype(dtype)) return -1;
     SSQ_REQUIRE(w && ref, "ssq_replace_under_abs: null pointer");
     if (count == 0) return 0;
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((replace_under_abs_kernel<float>), dim3(stream_grid(count)), dim3(256), 0, as_stream(stream),
-                           (float*)w, (const float*)ref, count, value, (float)replacement);
-    else
-        hipLaunchKernelGGL((replace_under_abs_kernel<double>), dim3(stream_grid(count)), dim3(256), 0, as_stream(stream),
-                           (double*)w, (const double*)ref, count, value, replacement);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((replace_under_abs_kernel<T>), dim3(stream_grid(count)), dim3(256), 0, as_stream(stream),
+                           (T*)w, (const T*)ref, count, value, (T)replacement);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_buffer(int dtype, const void* x, void* out, int64_t batch, int64_t n_x, int64_t seg_len,
@@ -1212,14 +1214,13 @@ int ssq_buffer(int dtype, const void* x, void* out, int64_t batch, int64_t n_x, 
     int64_t n_segs = (n_x - seg_len) / hop + 1;
     int64_t s20 = (seg_len + 1) / 2, s21 = (seg_len % 2 == 1) ? s20 - 1 : s20;
     int64_t total = batch * seg_len * n_segs;
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((buffer_kernel<float>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const float*)x, (float*)out, n_x, seg_len, n_segs, hop, s20, s21, modulated, total);
-    else
-        hipLaunchKernelGGL((buffer_kernel<double>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const double*)x, (double*)out, n_x, seg_len, n_segs, hop, s20, s21, modulated, total);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((buffer_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
+                           (const T*)x, (T*)out, n_x, seg_len, n_segs, hop, s20, s21, modulated, total);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_pad_signal(int dtype, const void* x, void* out, int64_t batch, int64_t n, int64_t n1,
@@ -1229,14 +1230,13 @@ int ssq_pad_signal(int dtype, const void* x, void* out, int64_t batch, int64_t n
     SSQ_REQUIRE(padtype >= SSQ_PAD_ZERO && padtype <= SSQ_PAD_WRAP, "unknown padtype %d", padtype);
     int64_t m = n1 + n + n2, total = batch * m;
     if (total == 0) return 0;
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((pad_kernel<float>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const float*)x, (float*)out, n, n1, m, padtype, total);
-    else
-        hipLaunchKernelGGL((pad_kernel<double>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
-                           (const double*)x, (double*)out, n, n1, m, padtype, total);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((pad_kernel<T>), dim3(stream_grid(total)), dim3(256), 0, as_stream(stream),
+                           (const T*)x, (T*)out, n, n1, m, padtype, total);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -496,13 +496,15 @@ int ssq_ridge_energy(int dtype, int is_complex, const void* Tf, void* energy, in
     const int64_t total = na * n;
     const unsigned blocks = (unsigned)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     hipStream_t s = as_stream(stream);
-#define LAUNCH(T, C) hipLaunchKernelGGL((ridge_energy_kernel<T, C>), dim3(blocks), dim3(256), 0, s, \
-                                        (const T*)Tf, (T*)energy, total)
-    if (dtype == SSQ_F32) { if (is_complex) LAUNCH(float, true); else LAUNCH(float, false); }
-    else { if (is_complex) LAUNCH(double, true); else LAUNCH(double, false); }
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+#define LAUNCH(C) hipLaunchKernelGGL((ridge_energy_kernel<T, C>), dim3(blocks), dim3(256), 0, s, \
+                                     (const T*)Tf, (T*)energy, total)
+        if (is_complex) LAUNCH(true); else LAUNCH(false);
 #undef LAUNCH
-    SSQ_LAUNCH_CHECK();
-    return 0;
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_ridge_neglog(int dtype, const void* energy, void* E, double eps, int64_t na, int64_t n,
@@ -518,14 +520,12 @@ int ssq_ridge_neglog_batch(int dtype, const void* energy, void* E, double eps, i
                 (long long)batch, (long long)na, (long long)n);
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)batch);
     hipStream_t s = as_stream(stream);
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((ridge_neglog_kernel<float>), grid, dim3(64), 0, s, (const float*)energy,
-                           (float*)E, (float)eps, na, n);
-    else
-        hipLaunchKernelGGL((ridge_neglog_kernel<double>), grid, dim3(64), 0, s, (const double*)energy,
-                           (double*)E, eps, na, n);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ridge_neglog_kernel<T>), grid, dim3(64), 0, s, (const T*)energy, (T*)E, (T)eps, na, n);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 int ssq_ridge_track(int dtype, int penalty_f32, const void* E, void* pe, const void* sc, double penalty,
@@ -563,14 +563,12 @@ int ssq_ridge_clear_batch(int dtype, void* energy, const int64_t* ridge, double 
     SSQ_REQUIRE(batch >= 1 && batch <= 65535, "ssq_ridge_clear: bad batch %lld", (long long)batch);
     const dim3 grid((unsigned)((n + 63) / 64), (unsigned)batch);
     hipStream_t s = as_stream(stream);
-    if (dtype == SSQ_F32)
-        hipLaunchKernelGGL((ridge_clear_kernel<float>), grid, dim3(64), 0, s, (float*)energy, ridge, bw,
-                           (float*)ridge_e, na, n);
-    else
-        hipLaunchKernelGGL((ridge_clear_kernel<double>), grid, dim3(64), 0, s, (double*)energy, ridge, bw,
-                           (double*)ridge_e, na, n);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((ridge_clear_kernel<T>), grid, dim3(64), 0, s, (T*)energy, ridge, bw, (T*)ridge_e, na, n);
+        SSQ_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // extern "C"

@@ -24,8 +24,6 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
-#include <tuple>
-#include <rocfft/rocfft.h>
 
 namespace ssq {
 
@@ -462,47 +460,6 @@ static int launch_stft_adjoint_fused(const StftAdjArgs& A, hipStream_t stream) {
     return 0;
 }
 
-// R2C with transposed (strided) output: transform c writes bin f at out[f*n_hops + c]
-struct StridedR2C {
-    rocfft_plan plan = nullptr; rocfft_execution_info info = nullptr;
-    void* work = nullptr; size_t work_bytes = 0;
-    int create(int dtype, size_t n_fft, size_t n_hops) {
-        if (fft_global_setup()) return -4;
-        rocfft_plan_description desc = nullptr;
-        if (rocfft_plan_description_create(&desc) != rocfft_status_success) { set_error("rocfft desc"); return -4; }
-        size_t offs = 0, in_stride = 1, out_stride = n_hops;
-        if (rocfft_plan_description_set_data_layout(desc, rocfft_array_type_real,
-                rocfft_array_type_hermitian_interleaved, &offs, &offs, 1, &in_stride, n_fft, 1,
-                &out_stride, 1) != rocfft_status_success) { set_error("rocfft layout"); return -4; }
-        rocfft_status st = rocfft_plan_create(&plan, rocfft_placement_notinplace,
-                rocfft_transform_type_real_forward,
-                dtype == SSQ_F32 ? rocfft_precision_single : rocfft_precision_double, 1, &n_fft,
-                n_hops, desc);
-        rocfft_plan_description_destroy(desc);
-        if (st != rocfft_status_success) { set_error("rocfft_plan_create (stft) failed: %d", (int)st); return -4; }
-        rocfft_plan_get_work_buffer_size(plan, &work_bytes);
-        rocfft_execution_info_create(&info);
-        if (work_bytes) {
-            SSQ_CHECK_HIP(hipMalloc(&work, work_bytes));
-            rocfft_execution_info_set_work_buffer(info, work, work_bytes);
-        }
-        return 0;
-    }
-    int execute(void* in, void* out, hipStream_t stream) {
-        rocfft_execution_info_set_stream(info, stream);
-        void* ins[1] = {in}; void* outs[1] = {out};
-        rocfft_status st = rocfft_execute(plan, ins, outs, info);
-        if (st != rocfft_status_success) { set_error("rocfft_execute (stft) failed: %d", (int)st); return -4; }
-        return 0;
-    }
-    void destroy() {
-        if (info) rocfft_execution_info_destroy(info);
-        if (plan) rocfft_plan_destroy(plan);
-        if (work) (void)hipFree(work);
-        info = nullptr; plan = nullptr; work = nullptr;
-    }
-};
-
 }  // namespace ssq
 
 using namespace ssq;
@@ -513,7 +470,7 @@ struct ssq_stft_plan {
     int rsize() const { return d.dtype == SSQ_F32 ? 4 : 8; }
     void* window = nullptr; void* diff_window = nullptr;
     void* xp = nullptr; void* frames = nullptr; void* dframes = nullptr; void* dSx_ws = nullptr;
-    StridedR2C fft;
+    FftPlan fft;                                  // R2C, transposed output: transform c writes bin f at Sx[f * n_hops + c]
     bool fused = false; void* ftw = nullptr;      // fused float32 path (power-of-two n_fft)
     void* wd = nullptr;                           // ... its (window, diff_window) pairs, one 8-byte load per sample
     // fused float32 path for the other sizes (prime factors <= 31): mixed-radix LDS transform
@@ -595,7 +552,7 @@ int ssq_stft_plan_create(ssq_stft_plan** out, const ssq_stft_desc* desc) {
         if (hipMalloc(&pl->frames, fb) != hipSuccess || hipMalloc(&pl->dframes, fb) != hipSuccess) {
             set_error("hipMalloc failed (stft plan)"); ssq_stft_plan_destroy(pl); return -2;
         }
-        rc = pl->fft.create(d.dtype, (size_t)d.n_fft, (size_t)pl->n_hops);
+        rc = pl->fft.create(0, d.dtype, (size_t)d.n_fft, (size_t)pl->n_hops, 1.0, (size_t)d.n_fft, 1, (size_t)pl->n_hops);
         if (rc) { ssq_stft_plan_destroy(pl); return rc; }
     }
     pl->d.window = nullptr; pl->d.diff_window = nullptr;
@@ -770,8 +727,9 @@ extern "C" int ssq_stft_execute(ssq_stft_plan* pl, const void* x, int64_t batch,
     SSQ_REQUIRE(!(Tx || w) || pl->have_ssq, "Tx / w requested but ssq parameters were not set");
     hipStream_t st = as_stream(stream);
     pl->order.enter(st);
-    const int rc = pl->d.dtype == SSQ_F32 ? stft_execute_t<float>(pl, x, batch, Sx, dSx, Tx, w, st)
-                                          : stft_execute_t<double>(pl, x, batch, Sx, dSx, Tx, w, st);
+    const int rc = dispatch_dtype(pl->d.dtype, [&](auto t) {
+        return stft_execute_t<decltype(t)>(pl, x, batch, Sx, dSx, Tx, w, st);
+    });
     pl->executed = true;
     pl->order.leave(st);
     return rc;
@@ -834,13 +792,14 @@ static int stft_adjoint_fused(ssq_stft_plan* pl, const void* gSx, const void* gd
     int rc = stft_adjoint_items(A, L, both ? G : 2 * G, batch);
     if (rc) return rc;
     const int64_t nf = A.nf;
+    StreamScratch scratch(stream);
     float* ws = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
+    rc = scratch.alloc(&ws, (size_t)batch * A.n_items * A.span * sizeof(float));
+    if (rc) return rc;
     A.ws = ws;
     rc = fft_dispatch<128, 2048>(L, [&](auto len) { return launch_stft_adjoint_fused<decltype(len)::value>(A, stream); });
     if (!rc) rc = stft_adjoint_unpad<float>(pl, ws, gx, batch, A.n_items, nf * hop, A.span,
                                             (pl->n_hops - 1) * (int64_t)hop + L, stream);
-    (void)hipFreeAsync(ws, stream);
     return rc;
 }
 
@@ -863,9 +822,9 @@ extern "C" int ssq_stft_adjoint(ssq_stft_plan* pl, const void* gSx, const void* 
             // composed: the overlap-added frames of the whole batch in the plan's padded-signal workspace, one strip
             rc = stft_adjoint_composed(d.dtype, gSx, gdSx, pl->window, pl->diff_window, pl->xp, batch, d.n_fft,
                                        pl->n_hops, d.hop_len, pl->padlen, d.modulated, st);
-            if (!rc) rc = d.dtype == SSQ_F32
-                ? stft_adjoint_unpad<float>(pl, pl->xp, gx, batch, 1, pl->padlen, pl->padlen, pl->padlen, st)
-                : stft_adjoint_unpad<double>(pl, pl->xp, gx, batch, 1, pl->padlen, pl->padlen, pl->padlen, st);
+            if (!rc) rc = dispatch_dtype(d.dtype, [&](auto t) {
+                return stft_adjoint_unpad<decltype(t)>(pl, pl->xp, gx, batch, 1, pl->padlen, pl->padlen, pl->padlen, st);
+            });
         }
     }
     pl->order.leave(st);
@@ -908,8 +867,10 @@ int istft_fused(const void* Sx, const void* win_t, const double* wn, void* x, in
     // slice b of a batched result has the bits of the single call)
     rc = stft_adjoint_items(A, L, 2 * G, 1);
     if (rc) return rc;
+    StreamScratch scratch(stream);
     float* ws = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&ws, (size_t)batch * A.n_items * A.span * sizeof(float), stream));
+    rc = scratch.alloc(&ws, (size_t)batch * A.n_items * A.span * sizeof(float));
+    if (rc) return rc;
     A.ws = ws;
     rc = fft_dispatch<128, 2048>(L, [&](auto len) { return launch_stft_adjoint_fused<decltype(len)::value, true>(A, stream); });
     if (!rc) {
@@ -918,7 +879,6 @@ int istft_fused(const void* Sx, const void* win_t, const double* wn, void* x, in
                            (int64_t)A.span, (n_hops - 1) * hop + L, 1.17549435e-38f);
         if (hipGetLastError() != hipSuccess) { set_error("istft_finish launch failed"); rc = -3; }
     }
-    (void)hipFreeAsync(ws, stream);
     return rc;
 }
 
@@ -951,8 +911,7 @@ __global__ __launch_bounds__(256) void irfft_adjoint_weights_kernel(T* __restric
     }
 }
 
-static std::mutex g_iadj_mu;
-static std::map<std::tuple<int, int64_t, int64_t, hipStream_t>, StridedR2C> g_iadj_plans;      // one work buffer per stream
+static StreamPlanCache<FftPlan> g_iadj_plans;             // R2C with transposed output; one work buffer per stream
 
 template <typename T>
 static int istft_adjoint_composed_t(int dtype, const void* upad, const void* win_t, void* gSx, int64_t batch,
@@ -960,47 +919,39 @@ static int istft_adjoint_composed_t(int dtype, const void* upad, const void* win
                                     hipStream_t stream) {
     const int64_t rows = n_fft / 2 + 1, total = n_fft * n_hops;
     const int64_t s20 = (n_fft + 1) / 2, s21 = n_fft / 2;
+    StreamScratch scratch(stream);
     T* frames = nullptr;
-    SSQ_CHECK_HIP(hipMallocAsync((void**)&frames, (size_t)total * sizeof(T), stream));
+    int rc = scratch.alloc(&frames, (size_t)total * sizeof(T));
+    if (rc) return rc;
     const unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
     const unsigned g2 = (unsigned)std::min<int64_t>((rows * n_hops + 255) / 256, 8192);
-    int rc = 0;
     for (int64_t b = 0; b < batch && !rc; ++b) {
         hipLaunchKernelGGL((frame_window_kernel<T>), dim3(g), dim3(256), 0, stream, (const T*)upad + (size_t)b * ulen,
                            (const T*)win_t, (const T*)nullptr, frames, (T*)nullptr, n_fft, n_hops, hop, s20, s21, modulated);
         if (hipGetLastError() != hipSuccess) { set_error("frame_window launch failed"); rc = -3; break; }
         T* out = (T*)gSx + (size_t)b * rows * n_hops * 2;
         {
-            std::lock_guard<std::mutex> lock(g_iadj_mu);          // held until the transform is enqueued
-            auto key = std::make_tuple(dtype, n_fft, n_hops, stream);
-            if (g_iadj_plans.size() >= 16 && !g_iadj_plans.count(key)) {
-                (void)hipDeviceSynchronize();
-                for (auto& kv : g_iadj_plans) kv.second.destroy();
-                g_iadj_plans.clear();
-            }
-            auto it = g_iadj_plans.find(key);
-            if (it == g_iadj_plans.end()) {
-                StridedR2C f;
-                rc = f.create(dtype, (size_t)n_fft, (size_t)n_hops);
-                if (rc) break;
-                it = g_iadj_plans.emplace(key, f).first;
-            }
-            rc = it->second.execute(frames, out, stream);
+            std::lock_guard<std::mutex> lock(g_iadj_plans.mu);    // held until the transform is enqueued
+            FftPlan* f = nullptr;
+            rc = g_iadj_plans.get(dtype, n_fft, n_hops, stream, &f, [&](FftPlan& p) {
+                return p.create(0, dtype, (size_t)n_fft, (size_t)n_hops, 1.0, (size_t)n_fft, 1, (size_t)n_hops);
+            });
+            if (!rc) rc = f->execute(frames, out, stream);
         }
         if (rc) break;
         hipLaunchKernelGGL((irfft_adjoint_weights_kernel<T>), dim3(g2), dim3(256), 0, stream, out, rows, n_hops,
                            (int)(n_fft % 2 == 0), (T)(T(1) / (T)n_fft));
         if (hipGetLastError() != hipSuccess) { set_error("irfft_adjoint_weights launch failed"); rc = -3; }
     }
-    (void)hipFreeAsync(frames, stream);
     return rc;
 }
 
 int istft_adjoint_composed(int dtype, const void* upad, const void* win_t, void* gSx, int64_t batch, int64_t n_fft,
                            int64_t n_hops, int64_t hop, int64_t ulen, int modulated, hipStream_t stream) {
-    if (dtype == SSQ_F32)
-        return istft_adjoint_composed_t<float>(dtype, upad, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated, stream);
-    return istft_adjoint_composed_t<double>(dtype, upad, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated, stream);
+    return dispatch_dtype(dtype, [&](auto t) {
+        return istft_adjoint_composed_t<decltype(t)>(dtype, upad, win_t, gSx, batch, n_fft, n_hops, hop, ulen, modulated,
+                                                     stream);
+    });
 }
 
 }  // namespace ssq

@@ -7,6 +7,7 @@ autograd functions. CPU-only."""
 import pytest
 import emu_backend
 import test_gpu_inverse_batched as T
+import test_gpu_inverse as TI
 
 
 @pytest.fixture(scope='module')
@@ -22,6 +23,7 @@ def host_tensors(monkeypatch):
     monkeypatch.setattr(T, 'DEV', 'cpu')        # emulated "device" tensors live on the host
     import test_gpu_autograd
     monkeypatch.setattr(test_gpu_autograd, 'DEV', 'cpu')
+    monkeypatch.setattr(TI, 'DEV', 'cpu')
 
 
 @pytest.mark.parametrize('dtype,n_fft,hop,N', T.BATCH_SHAPES)
@@ -88,3 +90,8 @@ def test_end_to_end(S):
 
 def test_nothing_asked_nothing_changed(S):
     T.test_nothing_asked_nothing_changed(S)
+
+
+@pytest.mark.parametrize('route', TI.CACHED_ROUTES)
+def test_plan_cache_eviction_keeps_the_bits(S, route):
+    TI.check_cache_eviction(S, route)
