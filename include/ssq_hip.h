@@ -143,6 +143,37 @@ int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, con
                    const double* scales, void* w, int64_t batch, int64_t na, int64_t n, double fs, double gamma,
                    double chirp_tol, void* stream);
 
+/* Multitaper synchrosqueezing, ConceFT (ABI 111; Daubechies, Wang, Wu 2016). J transforms of
+ * one signal taken with J orthonormal windows, V_j, and with the windows' derivatives, dV_j -- (batch, rows, n) complex
+ * planes each -- are combined into Q projections, each projection is synchrosqueezed, and the results are averaged.
+ *   V, dV   HOST arrays of J device pointers
+ *   Sfs     (rows,) real `dtype`, device
+ *   proj    HOST (Q, J, 2) float64: re, im of r[q][j]; read before the call returns (the entry keeps a device copy per
+ *           (device, contents), the eight most recent: a call whose copy exists only enqueues the kernel; the first
+ *           call with new contents uploads synchronously and must not be made under stream capture)
+ *   Cx      (batch, rows, n): real `dtype` (average = 0) or complex `dtype` (average = 1); overwritten
+ * Evaluated in float64 for both dtypes (float32 planes are promoted), no contraction. Per signal b, column c,
+ * projection q = 0 .. Q-1, with Tq a column of `rows` float64 complex cells, zero at first:
+ *   for i = 0 .. rows-1 (ascending):
+ *       Vq  = sum_j r[q][j] * V_j[b,i,c]     from 0, ascending j; each product as (ar*vr - ai*vi, ar*vi + ai*vr);
+ *                                            the real and the imaginary sum separate
+ *       dVq = the same over dV_j
+ *       if hypot(Vq.re, Vq.im) < gamma: continue
+ *       w = | Sfs[i] - (dVq.im*Vq.re - dVq.re*Vq.im) / ((Vq.re^2 + Vq.im^2) * 2pi) |
+ *       k = the nearest bin of w on the grid (grid, params: as ssq_indexed_sum; flipud: k -> rows-1-k)
+ *       Tq[k] += Vq                          a cell's terms in ascending i
+ *   average 0:  Cx[b,k,c] = ( sum_q hypot(Tq[k].re, Tq[k].im) ) / Q     ascending q; rounded once to `dtype`
+ *   average 1:  Cx[b,k,c] = ( sum_q Tq[k] ) / Q                         ascending q; rounded once
+ * Bit-reproducible from call to call; `batch` signals in one call equal `batch` calls of one signal bit for bit.
+ * One kernel: a workgroup per (signal, tile of 16 or 8 columns) holds Tq in LDS; the planes are read from HBM once,
+ * Cx is written once and nothing of size (Q, rows, n) is stored anywhere. Refused, with Cx unwritten: J outside
+ * 1 .. 8, Q outside 1 .. 1024, rows < 2, batch or n < 1, rows > 1280 (an 8-column tile of float64 complex cells in
+ * 160 KiB of LDS; 16 columns up to 640 rows), batch rows n >= 2^32, a null pointer, a proj entry that is not
+ * finite, gamma < 0 or NaN. No counterpart in the reference. */
+int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
+                int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
+                const double* params, int flipud, int average, void* stream);
+
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]
  * with k from `grid`/`params` (and mirrored, k -> na-1-k, if `flipud`).

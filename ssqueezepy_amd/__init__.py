@@ -25,6 +25,7 @@ def __getattr__(name):
         'cwt': '_cwt', 'cwt_higher_order': '_cwt', 'ssq_cwt': '_ssq_cwt', 'phase_cwt': '_ssq_cwt',
         'stft': '_stft', 'get_window': '_stft', 'ssq_stft': '_ssq_stft',
         'phase_stft': '_ssq_stft', 'ssq_stft2': '_ssq_stft2', 'ssq_cwt2': '_ssq_cwt2', 'ssqueeze': 'ssqueezing',
+        'conceft_stft': '_conceft', 'hermite_windows': '_conceft', 'conceft_gpu': 'algos',
         'ssqueeze_fast': 'algos', 'indexed_sum_onfly': 'algos', 'buffer': 'algos',
         'replace_under_abs': 'algos', 'phase_cwt_gpu': 'algos',
         'phase_stft_gpu': 'algos', 'phase_stft2_gpu': 'algos', 'phase_cwt2_gpu': 'algos',

@@ -78,6 +78,8 @@ _PROTOS = {
                                 c_void_p, c_int64, c_int64, c_int64, c_double, c_double, c_void_p]),
     'ssq_cwt2_phase': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_void_p]),
+    'ssq_conceft': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                            c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int, c_int, c_void_p]),
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
@@ -160,7 +162,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 110     # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 111     # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -4,19 +4,21 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` (multitaper synchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
 implementation behind them.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -289,6 +291,56 @@ def phase_cwt2_gpu(W, dW, Wd, dWd, dW3, scales, fs, gamma, chirp_tol=1e-3):
     check(lib.ssq_cwt2_phase(_CDT[w.dtype], *[_ptr(V) for V in planes], sc.ctypes.data, _ptr(w), B, na, n,
                              float(fs), float(gamma), float(chirp_tol), stream()))
     return w
+
+
+def conceft_gpu(V, dV, Sfs, proj, ssq_freqs, gamma, flipud=False, average='abs', out=None):
+    """Multitaper synchrosqueezing in one kernel (`ssq_conceft`, include/ssq_hip.h states the definition; DESIGN.md
+    4.5.5). `V`, `dV`: sequences of `J` complex planes, each (rows, n) or (B, rows, n) -- the STFTs of one signal with
+    `J` orthonormal windows and with the windows' derivatives; `proj`: (Q, J) complex, used as given (`conceft_stft`
+    normalises its rows); `Sfs`: (rows,); `ssq_freqs`: the linear grid the bins are taken on. Per projection `q` the
+    planes are mixed, ``Vq = sum_j proj[q, j] V[j]``, `Vq` is reassigned by ``|Sfs - Im(dVq / Vq) / 2pi|`` where
+    ``|Vq| >= gamma``, and the `Q` results are averaged: their magnitudes (``average='abs'``, a real array) or the
+    complex values (``'complex'``). Float64 arithmetic for both precisions, rounded once; bit-reproducible."""
+    if average not in ('abs', 'complex'):
+        raise ValueError("`average` must be 'abs' or 'complex' (got %r)" % (average,))
+    if gamma is None:
+        raise ValueError("`gamma` must not be None")
+    lib = _lib.load()
+    V, dV = list(V), list(dV)
+    if not V or len(V) != len(dV):
+        raise ValueError("`V` and `dV` must hold the same number of planes, at least one (got %d and %d)"
+                         % (len(V), len(dV)))
+    first = to_device(V[0])
+    if first.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("the planes must be complex64 or complex128 (got %s)" % first.dtype)
+    planes = [first] + [to_device(p, first.dtype) for p in V[1:] + dV]
+    for p in planes[1:]:
+        if p.shape != first.shape:
+            raise ValueError("the planes must share one shape (got %s and %s)" % (tuple(first.shape), tuple(p.shape)))
+    J = len(V)
+    B, rows, n = _shape3(first)
+    rdt = _real_of(first.dtype)
+    sfs = to_device(np.ascontiguousarray(np.asarray(Sfs).reshape(-1)), rdt)
+    if sfs.numel() != rows:
+        raise ValueError("`Sfs` must have one entry per row (%d != %d)" % (sfs.numel(), rows))
+    if hasattr(proj, 'detach'):
+        proj = proj.detach().cpu().numpy()
+    proj = np.asarray(proj, dtype=np.complex128)
+    if proj.ndim != 2 or proj.shape[1] != J:
+        raise ValueError("`proj` must be (Q, %d) (got %s)" % (J, proj.shape))
+    r = np.ascontiguousarray(np.stack([proj.real, proj.imag], axis=-1))      # a host array: the entry checks it
+    odt = rdt if average == 'abs' else first.dtype
+    if out is None:
+        out = torch.empty(first.shape, dtype=odt, device=first.device)
+    elif not (isinstance(out, torch.Tensor) and out.shape == first.shape and out.dtype == odt and out.is_cuda
+              and out.is_contiguous() and not out.is_conj()):
+        raise ValueError("`out` must be a contiguous GPU tensor of the planes' shape, %s" % odt)
+    kind, p = _grid(ssq_freqs, False)
+    ptrs = ctypes.c_void_p * J
+    check(lib.ssq_conceft(_CDT[first.dtype], ptrs(*[_ptr(t) for t in planes[:J]]), ptrs(*[_ptr(t) for t in planes[J:]]),
+                          _ptr(sfs), r.ctypes.data, _ptr(out), B, J, proj.shape[0], rows, n, float(gamma), kind, p,
+                          int(bool(flipud)), int(average == 'complex'), stream()))
+    return out
 
 
 def replace_under_abs(x, ref=None, value=1., replacement=0., parallel=None):

@@ -20,6 +20,8 @@
 //   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
 //   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
 //       (They share Phase2Vec and launch_phase2; why not more: DESIGN.md section 4.5.3.)
+//   conceft_kernel           multitaper synchrosqueezing: Q projections of J transforms mixed, reassigned into an
+//       LDS tile in row order and averaged, in one kernel (ssq_conceft.inl).
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
 #include "ssq_common.h"
 #include <cfloat>
@@ -958,6 +960,8 @@ static void launch_phase2(K vec_kernel, K element_kernel, const void* const (&pl
                        (const T*)planes[3], (const T*)planes[4], tab, (T*)w, rows, n, total, gamma, chirp_tol);
 }
 
+#include "ssq_conceft.inl"
+
 }  // namespace ssq
 
 using namespace ssq;
@@ -970,7 +974,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 110; }   // 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 111; }   // 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -1188,6 +1192,39 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const vo
     SsqParams sp;
     if (fill_params(sp, grid, params, flipud, 0.0, cst_f64)) return -1;
     return launch_accumulate(dtype, BIN_FROM_W, Wx, w, nullptr, Tx, cst, sp, batch, na, n, nullptr, as_stream(stream));
+}
+
+int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
+                int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid, const double* params,
+                int flipud, int average, void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(J >= 1 && J <= 8, "ssq_conceft: J = %lld, 1 .. 8 transforms", (long long)J);
+    SSQ_REQUIRE(Q >= 1 && Q <= 1024, "ssq_conceft: Q = %lld, 1 .. 1024 projections", (long long)Q);
+    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "ssq_conceft: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1",
+                (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(rows <= CONCEFT_MAX_ROWS, "ssq_conceft: %lld rows, at most %lld (an 8-column float64 tile in 160 KiB of LDS)",
+                (long long)rows, (long long)CONCEFT_MAX_ROWS);
+    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
+                "ssq_conceft: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(V && dV && Sfs && proj && Cx, "ssq_conceft: null pointer");
+    ConceftPlanes P = {};
+    for (int64_t j = 0; j < J; ++j) {
+        SSQ_REQUIRE(V[j] && dV[j], "ssq_conceft: plane %lld is a null pointer", (long long)j);
+        P.v[j] = V[j]; P.dv[j] = dV[j];
+    }
+    for (int64_t t = 0; t < 2 * Q * J; ++t)
+        SSQ_REQUIRE(proj[t] - proj[t] == 0.0, "ssq_conceft: proj[%lld][%lld] is not finite", (long long)(t / (2 * J)),
+                    (long long)(t / 2 % J));
+    SSQ_REQUIRE(gamma >= 0.0, "ssq_conceft: gamma must be >= 0 (got %g)", gamma);
+    SsqParams sp;
+    if (fill_params(sp, grid, params, flipud, gamma, 0)) return -1;
+    const double* rdev = nullptr;
+    if (conceft_proj_table(proj, (size_t)(2 * Q * J), &rdev)) return -1;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return average ? launch_conceft<T, true>(P, Sfs, rdev, Cx, sp, batch, J, Q, rows, n, as_stream(stream))
+                       : launch_conceft<T, false>(P, Sfs, rdev, Cx, sp, batch, J, Q, rows, n, as_stream(stream));
+    });
 }
 
 int ssq_replace_under_abs(int dtype, void* w, const void* ref, int64_t count, double value,
