@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 110 (109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 112 (111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -173,6 +173,30 @@ int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, con
 int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
                 int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
                 const double* params, int flipud, int average, void* stream);
+
+/* ConceFT for the CWT (ABI 112): ssq_conceft's kernel in its CWT form. The J transforms are
+ * CWTs of one signal over orthogonal wavelets of equal norm (generalized Morse wavelets of orders 0 .. J-1), W_j, with
+ * their time derivatives, dW_j. What differs from ssq_conceft: the phase has no Sfs term, every term carries its row's
+ * weight, and all three grids are accepted (the log grids map through log2(w); w = 0 -> bin 0).
+ *   W, dW   HOST arrays of J device pointers to (batch, rows, n) complex planes
+ *   cst     (rows,) float64, device: the weight of row i (ssq_ssqueeze's cst with cst_f64 = 1)
+ *   proj, Cx, average, flipud: as ssq_conceft; grid, params: as ssq_ssqueeze (params: 5 entries)
+ * Evaluated in float64 for both dtypes (float32 planes are promoted), no contraction. Per signal b, column c,
+ * projection q, with Tq a column of `rows` float64 complex cells, zero at first:
+ *   for i = 0 .. rows-1 (ascending):
+ *       Wq, dWq = sum_j r[q][j] * W_j[b,i,c], ... dW_j               exactly as ssq_conceft mixes V and dV
+ *       if hypot(Wq.re, Wq.im) < gamma: continue
+ *       w = | (dWq.im*Wq.re - dWq.re*Wq.im) / ((Wq.re^2 + Wq.im^2) * 2pi) |
+ *       k = the nearest bin of w on the grid (the exact map); flipud: k -> rows-1-k
+ *       Tq[k] += (Wq.re * cst[i], Wq.im * cst[i])                    a cell's terms in ascending i
+ *   average 0:  Cx[b,k,c] = ( sum_q hypot(Tq[k].re, Tq[k].im) ) / Q     ascending q; rounded once to `dtype`
+ *   average 1:  Cx[b,k,c] = ( sum_q Tq[k] ) / Q                         ascending q; rounded once
+ * Bit-reproducible; a batch equals its single-signal calls bit for bit; the device copies of `proj` are shared with
+ * ssq_conceft. Refused, with Cx unwritten, on ssq_conceft's conditions and for an unknown `grid`. No counterpart in
+ * the reference. */
+int ssq_conceft_cwt(int dtype, const void* const* W, const void* const* dW, const void* cst, const double* proj, void* Cx,
+                    int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
+                    const double* params, int flipud, int average, void* stream);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

@@ -80,6 +80,8 @@ _PROTOS = {
                                c_void_p, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_void_p]),
     'ssq_conceft': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                             c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int, c_int, c_void_p]),
+    'ssq_conceft_cwt': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int, c_int, c_void_p]),
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
@@ -162,7 +164,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 111     # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 112     # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` (multitaper synchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -293,14 +293,9 @@ def phase_cwt2_gpu(W, dW, Wd, dWd, dW3, scales, fs, gamma, chirp_tol=1e-3):
     return w
 
 
-def conceft_gpu(V, dV, Sfs, proj, ssq_freqs, gamma, flipud=False, average='abs', out=None):
-    """Multitaper synchrosqueezing in one kernel (`ssq_conceft`, include/ssq_hip.h states the definition; DESIGN.md
-    4.5.5). `V`, `dV`: sequences of `J` complex planes, each (rows, n) or (B, rows, n) -- the STFTs of one signal with
-    `J` orthonormal windows and with the windows' derivatives; `proj`: (Q, J) complex, used as given (`conceft_stft`
-    normalises its rows); `Sfs`: (rows,); `ssq_freqs`: the linear grid the bins are taken on. Per projection `q` the
-    planes are mixed, ``Vq = sum_j proj[q, j] V[j]``, `Vq` is reassigned by ``|Sfs - Im(dVq / Vq) / 2pi|`` where
-    ``|Vq| >= gamma``, and the `Q` results are averaged: their magnitudes (``average='abs'``, a real array) or the
-    complex values (``'complex'``). Float64 arithmetic for both precisions, rounded once; bit-reproducible."""
+def _conceft_call(entry, V, dV, row_values, proj, ssq_freqs, logscale, gamma, flipud, average, out):
+    """The checks and the call `conceft_gpu` and `conceft_cwt_gpu` share. `row_values(rows, rdt)` gives the entry's
+    per-row device vector: `Sfs` for `ssq_conceft`, the float64 weights for `ssq_conceft_cwt`."""
     if average not in ('abs', 'complex'):
         raise ValueError("`average` must be 'abs' or 'complex' (got %r)" % (average,))
     if gamma is None:
@@ -320,9 +315,7 @@ def conceft_gpu(V, dV, Sfs, proj, ssq_freqs, gamma, flipud=False, average='abs',
     J = len(V)
     B, rows, n = _shape3(first)
     rdt = _real_of(first.dtype)
-    sfs = to_device(np.ascontiguousarray(np.asarray(Sfs).reshape(-1)), rdt)
-    if sfs.numel() != rows:
-        raise ValueError("`Sfs` must have one entry per row (%d != %d)" % (sfs.numel(), rows))
+    rowv = row_values(rows, rdt)
     if hasattr(proj, 'detach'):
         proj = proj.detach().cpu().numpy()
     proj = np.asarray(proj, dtype=np.complex128)
@@ -335,12 +328,52 @@ def conceft_gpu(V, dV, Sfs, proj, ssq_freqs, gamma, flipud=False, average='abs',
     elif not (isinstance(out, torch.Tensor) and out.shape == first.shape and out.dtype == odt and out.is_cuda
               and out.is_contiguous() and not out.is_conj()):
         raise ValueError("`out` must be a contiguous GPU tensor of the planes' shape, %s" % odt)
-    kind, p = _grid(ssq_freqs, False)
+    kind, p = _grid(ssq_freqs, logscale)
     ptrs = ctypes.c_void_p * J
-    check(lib.ssq_conceft(_CDT[first.dtype], ptrs(*[_ptr(t) for t in planes[:J]]), ptrs(*[_ptr(t) for t in planes[J:]]),
-                          _ptr(sfs), r.ctypes.data, _ptr(out), B, J, proj.shape[0], rows, n, float(gamma), kind, p,
-                          int(bool(flipud)), int(average == 'complex'), stream()))
+    check(getattr(lib, entry)(_CDT[first.dtype], ptrs(*[_ptr(t) for t in planes[:J]]),
+                              ptrs(*[_ptr(t) for t in planes[J:]]), _ptr(rowv), r.ctypes.data, _ptr(out), B, J,
+                              proj.shape[0], rows, n, float(gamma), kind, p, int(bool(flipud)),
+                              int(average == 'complex'), stream()))
     return out
+
+
+def conceft_gpu(V, dV, Sfs, proj, ssq_freqs, gamma, flipud=False, average='abs', out=None):
+    """Multitaper synchrosqueezing in one kernel (`ssq_conceft`, include/ssq_hip.h states the definition; DESIGN.md
+    4.5.5). `V`, `dV`: sequences of `J` complex planes, each (rows, n) or (B, rows, n) -- the STFTs of one signal with
+    `J` orthonormal windows and with the windows' derivatives; `proj`: (Q, J) complex, used as given (`conceft_stft`
+    normalises its rows); `Sfs`: (rows,); `ssq_freqs`: the linear grid the bins are taken on. Per projection `q` the
+    planes are mixed, ``Vq = sum_j proj[q, j] V[j]``, `Vq` is reassigned by ``|Sfs - Im(dVq / Vq) / 2pi|`` where
+    ``|Vq| >= gamma``, and the `Q` results are averaged: their magnitudes (``average='abs'``, a real array) or the
+    complex values (``'complex'``). Float64 arithmetic for both precisions, rounded once; bit-reproducible."""
+    def sfs(rows, rdt):
+        vec = to_device(np.ascontiguousarray(np.asarray(Sfs).reshape(-1)), rdt)
+        if vec.numel() != rows:
+            raise ValueError("`Sfs` must have one entry per row (%d != %d)" % (vec.numel(), rows))
+        return vec
+    return _conceft_call('ssq_conceft', V, dV, sfs, proj, ssq_freqs, False, gamma, flipud, average, out)
+
+
+def conceft_cwt_gpu(W, dW, proj, ssq_freqs, const, gamma, flipud=False, average='abs', out=None):
+    """`conceft_gpu` for the CWT (`ssq_conceft_cwt`, include/ssq_hip.h). `W`, `dW`: sequences of `J`
+    complex planes, each (rows, n) or (B, rows, n) -- the CWTs of one signal over `J` orthogonal wavelets and their time
+    derivatives; `proj`: (Q, J) complex, used as given; `ssq_freqs`: (rows,), linear, 'log' or 'log-piecewise' (inferred
+    from its values, as `ssqueeze` does); `const`: the rows' weights, a scalar or (rows,), sent as float64. Per
+    projection `q` the planes are mixed, ``Wq = sum_j proj[q, j] W[j]``, ``Wq * const`` is reassigned by
+    ``|Im(dWq / Wq)| / 2pi`` where ``|Wq| >= gamma``, and the `Q` results are averaged as `conceft_gpu` averages them.
+    Float64 arithmetic for both precisions, rounded once; bit-reproducible."""
+    from .scales import infer_scaletype
+    if hasattr(ssq_freqs, 'detach'):
+        ssq_freqs = ssq_freqs.detach().cpu().numpy()
+    ssq_freqs = np.asarray(ssq_freqs)
+
+    def weights(rows, rdt):
+        c = const.detach().cpu().numpy() if hasattr(const, 'detach') else const
+        c = np.asarray(c, dtype=np.float64).reshape(-1)
+        if c.size not in (1, rows):
+            raise ValueError("`const` must be a scalar or have one entry per row (%d != %d)" % (c.size, rows))
+        return to_device(np.ascontiguousarray(np.broadcast_to(c, (rows,))), torch.float64)
+    logscale = infer_scaletype(ssq_freqs)[0].startswith('log')
+    return _conceft_call('ssq_conceft_cwt', W, dW, weights, proj, ssq_freqs, logscale, gamma, flipud, average, out)
 
 
 def replace_under_abs(x, ref=None, value=1., replacement=0., parallel=None):

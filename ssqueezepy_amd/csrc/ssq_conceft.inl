@@ -1,4 +1,5 @@
-// ssq_conceft.inl -- ssq_conceft: multitaper synchrosqueezing (ConceFT; Daubechies, Wang, Wu 2016) in one kernel.
+// ssq_conceft.inl -- ssq_conceft, ssq_conceft_cwt: multitaper synchrosqueezing (ConceFT; Daubechies, Wang, Wu 2016) in
+// one kernel, in its STFT and its CWT form.
 // Included by ssq_kernels.hip inside `namespace ssq`, after the accumulate kernels whose ordered row-lane combine
 // (FoldLower) it shares. include/ssq_hip.h states what is computed; DESIGN.md section 4.5.5 the sizing.
 //
@@ -11,15 +12,18 @@
 // registers, read through the constant address space --, thresholded, mapped to a bin by the exact map and added to
 // the tile in ascending row order; then every lane folds its cells into its sums and clears them.
 // HBM traffic: the 2J planes once, Cx once; nothing of size (Q, rows, n) exists anywhere.
+// CWT = false is ssq_conceft: a row's value is Sfs[i] (the planes' real dtype), w = |Sfs[i] - phase_ratio| and a term is
+// Vq. CWT = true is ssq_conceft_cwt: a row's value is the weight cst[i] (float64), w = |phase_ratio| and a term is
+// Vq * cst[i]; on the log grids the bin map takes log2(w), inside the branch that a point below gamma skips.
 struct ConceftPlanes { const void* v[8]; const void* dv[8]; };
 
 // rows a tile of TC columns supports: TC * 16 bytes per row in 160 KiB of LDS, 16 NC cells per column in registers
 constexpr int64_t CONCEFT_MAX_ROWS = 1280;
 
-template <typename T, int TC, int NC, bool CPLX>
+template <typename T, int TC, int NC, bool CPLX, bool CWT>
 __global__ __launch_bounds__(64 * (TC / 4)) void conceft_kernel(
-    ConceftPlanes P, const T* __restrict__ Sfs, const double* __restrict__ proj, T* __restrict__ Cx, SsqParams sp,
-    int J, int Q, int rows, int n, unsigned tiles) {
+    ConceftPlanes P, const std::conditional_t<CWT, double, T>* __restrict__ Sfs, const double* __restrict__ proj,
+    T* __restrict__ Cx, SsqParams sp, int J, int Q, int rows, int n, unsigned tiles) {
     constexpr int RL = 16, WC = 4;
     using TM = Term<double, false>;
     extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -70,7 +74,8 @@ __global__ __launch_bounds__(64 * (TC / 4)) void conceft_kernel(
                 }
             int k = -1;
             if (col_ok && i < rows && !(hypot(vr, vi) < sp.gamma)) {
-                k = (int)bin_from_w(fabs(sf - phase_ratio(dr, di, vr, vi)), sp, omax);
+                if constexpr (CWT) k = (int)bin_from_w(fabs(phase_ratio(dr, di, vr, vi)), sp, omax);
+                else k = (int)bin_from_w(fabs(sf - phase_ratio(dr, di, vr, vi)), sp, omax);
                 if (sp.flipud) k = (int)omax - k;
             }
             // the 16 rows of the step, combined in registers in ascending row order: one LDS read and one LDS write
@@ -78,7 +83,8 @@ __global__ __launch_bounds__(64 * (TC / 4)) void conceft_kernel(
             double tr = 0.0, ti = 0.0, ore = 0.0, oim = 0.0;
             double* cell = slab;
             if (k >= 0) {
-                tr = vr; ti = vi;
+                if constexpr (CWT) { tr = vr * sf; ti = vi * sf; }
+                else { tr = vr; ti = vi; }
                 cell = slab + 2 * (k * WC + ((cl + k) & (WC - 1)));
                 ore = cell[0]; oim = cell[1];
             }
@@ -148,19 +154,20 @@ static int conceft_proj_table(const double* proj, size_t count, const double** o
     return 0;
 }
 
-template <typename T, bool CPLX>
+template <typename T, bool CPLX, bool CWT>
 static int launch_conceft(const ConceftPlanes& P, const void* Sfs, const double* proj, void* Cx, const SsqParams& sp,
                           int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, hipStream_t stream) {
+    using R = std::conditional_t<CWT, double, T>;             // the row vector's element: Sfs, or the float64 weights
     // the widest tile whose rows fit the LDS and whose cells fit the lanes' registers
 #define SSQ_CONCEFT(TC, NC)                                                                                       \
     {                                                                                                             \
         const size_t lds = (size_t)rows * TC * 16;                                                                \
         const unsigned tiles = (unsigned)((n + TC - 1) / TC);                                                     \
-        auto kern = conceft_kernel<T, TC, NC, CPLX>;                                                              \
+        auto kern = conceft_kernel<T, TC, NC, CPLX, CWT>;                                                         \
         SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
         hipLaunchKernelGGL(kern, dim3(tiles * (unsigned)batch), dim3(64 * (TC / 4)), lds, stream, P,              \
-                           (const T*)Sfs, proj, (T*)Cx, sp, (int)J, (int)Q, (int)rows, (int)n, tiles);            \
+                           (const R*)Sfs, proj, (T*)Cx, sp, (int)J, (int)Q, (int)rows, (int)n, tiles);            \
     }
     if (rows <= 16 * 17) SSQ_CONCEFT(16, 17)
     else if (rows <= 16 * 40) SSQ_CONCEFT(16, 40)

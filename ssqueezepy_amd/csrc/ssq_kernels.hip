@@ -21,7 +21,7 @@
 //   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
 //       (They share Phase2Vec and launch_phase2; why not more: DESIGN.md section 4.5.3.)
 //   conceft_kernel           multitaper synchrosqueezing: Q projections of J transforms mixed, reassigned into an
-//       LDS tile in row order and averaged, in one kernel (ssq_conceft.inl).
+//       LDS tile in row order and averaged, in one kernel; an STFT and a CWT form (ssq_conceft.inl).
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
 #include "ssq_common.h"
 #include <cfloat>
@@ -974,7 +974,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 111; }   // 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 112; }   // 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -1194,37 +1194,57 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const vo
     return launch_accumulate(dtype, BIN_FROM_W, Wx, w, nullptr, Tx, cst, sp, batch, na, n, nullptr, as_stream(stream));
 }
 
-int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
-                int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid, const double* params,
-                int flipud, int average, void* stream) {
+// ssq_conceft and ssq_conceft_cwt: one set of checks, one launcher. `rowv` is Sfs (the planes' real dtype) for the STFT
+// form and the float64 weights cst for the CWT form; `name` opens every refusal's message.
+static int conceft_entry(bool cwt, const char* name, int dtype, const void* const* V, const void* const* dV,
+                         const void* rowv, const double* proj, void* Cx, int64_t batch, int64_t J, int64_t Q, int64_t rows,
+                         int64_t n, double gamma, int grid, const double* params, int flipud, int average, void* stream) {
     if (check_dtype(dtype)) return -1;
-    SSQ_REQUIRE(J >= 1 && J <= 8, "ssq_conceft: J = %lld, 1 .. 8 transforms", (long long)J);
-    SSQ_REQUIRE(Q >= 1 && Q <= 1024, "ssq_conceft: Q = %lld, 1 .. 1024 projections", (long long)Q);
-    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "ssq_conceft: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1",
+    SSQ_REQUIRE(J >= 1 && J <= 8, "%s: J = %lld, 1 .. 8 transforms", name, (long long)J);
+    SSQ_REQUIRE(Q >= 1 && Q <= 1024, "%s: Q = %lld, 1 .. 1024 projections", name, (long long)Q);
+    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "%s: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1", name,
                 (long long)batch, (long long)rows, (long long)n);
-    SSQ_REQUIRE(rows <= CONCEFT_MAX_ROWS, "ssq_conceft: %lld rows, at most %lld (an 8-column float64 tile in 160 KiB of LDS)",
+    SSQ_REQUIRE(rows <= CONCEFT_MAX_ROWS, "%s: %lld rows, at most %lld (an 8-column float64 tile in 160 KiB of LDS)", name,
                 (long long)rows, (long long)CONCEFT_MAX_ROWS);
     SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
-                "ssq_conceft: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)rows, (long long)n);
-    SSQ_REQUIRE(V && dV && Sfs && proj && Cx, "ssq_conceft: null pointer");
+                "%s: %lld x %lld x %lld points, at most 2^32 - 1", name, (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(V && dV && rowv && proj && Cx && params, "%s: null pointer", name);
     ConceftPlanes P = {};
     for (int64_t j = 0; j < J; ++j) {
-        SSQ_REQUIRE(V[j] && dV[j], "ssq_conceft: plane %lld is a null pointer", (long long)j);
+        SSQ_REQUIRE(V[j] && dV[j], "%s: plane %lld is a null pointer", name, (long long)j);
         P.v[j] = V[j]; P.dv[j] = dV[j];
     }
     for (int64_t t = 0; t < 2 * Q * J; ++t)
-        SSQ_REQUIRE(proj[t] - proj[t] == 0.0, "ssq_conceft: proj[%lld][%lld] is not finite", (long long)(t / (2 * J)),
+        SSQ_REQUIRE(proj[t] - proj[t] == 0.0, "%s: proj[%lld][%lld] is not finite", name, (long long)(t / (2 * J)),
                     (long long)(t / 2 % J));
-    SSQ_REQUIRE(gamma >= 0.0, "ssq_conceft: gamma must be >= 0 (got %g)", gamma);
+    SSQ_REQUIRE(gamma >= 0.0, "%s: gamma must be >= 0 (got %g)", name, gamma);
+    SSQ_REQUIRE(grid >= SSQ_GRID_LOG && grid <= SSQ_GRID_LIN, "%s: unknown grid kind %d", name, grid);
     SsqParams sp;
-    if (fill_params(sp, grid, params, flipud, gamma, 0)) return -1;
+    if (fill_params(sp, grid, params, flipud, gamma, cwt ? 1 : 0)) return -1;
     const double* rdev = nullptr;
     if (conceft_proj_table(proj, (size_t)(2 * Q * J), &rdev)) return -1;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        return average ? launch_conceft<T, true>(P, Sfs, rdev, Cx, sp, batch, J, Q, rows, n, as_stream(stream))
-                       : launch_conceft<T, false>(P, Sfs, rdev, Cx, sp, batch, J, Q, rows, n, as_stream(stream));
+        hipStream_t s = as_stream(stream);
+        if (cwt) return average ? launch_conceft<T, true, true>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s)
+                                : launch_conceft<T, false, true>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s);
+        return average ? launch_conceft<T, true, false>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s)
+                       : launch_conceft<T, false, false>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s);
     });
+}
+
+int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
+                int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid, const double* params,
+                int flipud, int average, void* stream) {
+    return conceft_entry(false, "ssq_conceft", dtype, V, dV, Sfs, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
+                         flipud, average, stream);
+}
+
+int ssq_conceft_cwt(int dtype, const void* const* W, const void* const* dW, const void* cst, const double* proj, void* Cx,
+                    int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
+                    const double* params, int flipud, int average, void* stream) {
+    return conceft_entry(true, "ssq_conceft_cwt", dtype, W, dW, cst, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
+                         flipud, average, stream);
 }
 
 int ssq_replace_under_abs(int dtype, void* w, const void* ref, int64_t count, double value,

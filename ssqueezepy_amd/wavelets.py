@@ -26,7 +26,7 @@ from .configs import fill_defaults
 pi = np.pi
 
 __all__ = ['Wavelet', 'center_frequency', 'xi_grid', 'find_maximum',
-           'find_first_occurrence', 'morsefreq', 'derived_wavelets']
+           'find_first_occurrence', 'morsefreq', 'derived_wavelets', 'morse_wavelets']
 
 
 # --------------------------------------------------------------------- grids
@@ -462,6 +462,24 @@ def derived_wavelets(wavelet):
         _DERIVED.pop(next(iter(_DERIVED)))
     _DERIVED[key] = out
     return out
+
+
+# --------------------------------------------------------- multitaper family
+def morse_wavelets(wavelet='gmw', n_tapers=3):
+    """The tapers of `conceft_cwt`: ``[Wavelet(('gmw', dict(order=k, ...))) for k in range(n_tapers)]``, built from
+    the configuration of `wavelet` (a GMW: name, ``(name, dict)`` or `Wavelet`) with its `order` replaced. For one
+    ``(gamma, beta)`` the generalized Morse wavelets of different orders are orthogonal (Olhede & Walden 2002), and
+    with ``norm='bandpass'`` the order-`k` wavelet is the orthonormal (``'energy'``) one times a factor that does not
+    depend on `k` (`_gmw_k_constants`), so the family is orthogonal with equal L2 norms in float32 too, where
+    ``'energy'`` is refused. ``1 <= n_tapers <= 8``."""
+    J = int(n_tapers)
+    if not 1 <= J <= 8:
+        raise ValueError("`n_tapers` must be 1 .. 8 (got %s)" % (n_tapers,))
+    wavelet = Wavelet._init_if_not_isinstance(wavelet)
+    if wavelet.family != 'gmw':
+        raise ValueError("`wavelet` must be a GMW: the tapers are its higher orders (got %s)" % wavelet.name)
+    opts = {k: v for k, v in wavelet.config.items() if k != 'order'}
+    return [Wavelet(('gmw', dict(order=k, **opts))) for k in range(J)]
 
 
 # ------------------------------------------------------------- 1-D searches
