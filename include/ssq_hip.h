@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 112 (111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 113 (112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -197,6 +197,41 @@ int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const vo
 int ssq_conceft_cwt(int dtype, const void* const* W, const void* const* dW, const void* cst, const double* proj, void* Cx,
                     int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
                     const double* params, int flipud, int average, void* stream);
+
+/* Time-reassigned synchrosqueezing, TSST (ABI 113; He, Cao, Zi, Zhou, Chen 2019): every
+ * coefficient of an STFT moves along the time axis, within its row, to its local group delay.
+ *   Sx, Vtg (batch, rows, n) complex `dtype`, device: the STFT with window g and the STFT with window tau g, tau the
+ *           window's time axis in seconds, 0 at the window's centre
+ *   rot     (n_fft,) complex128, device: the phase rotation table, e^{-2 pi i p / n_fft} made by the caller -- the
+ *           kernel and its NumPy statement use the same bits and no sincos runs on the device. NULL: no rotation, (1, 0)
+ *   Tx      (batch, rows, n) complex `dtype`; overwritten
+ *   cols_per_second  fs / hop_len;  dmax: the largest displacement kept, in columns
+ * Evaluated in float64 for both dtypes (float32 planes are promoted per point), basic IEEE operations only, no
+ * contraction. Per signal b and row i, with Tx[b,i,:] float64 zeros at first, for c = 0 .. n-1 (ascending):
+ *       gr, gi = Sx[b,i,c];  tr, ti = Vtg[b,i,c]
+ *       if hypot(gr, gi) < gamma: continue              float32 planes: sqrt(gr*gr + gi*gi) in float64 (the squares
+ *                                                       are exact and cannot leave the range); float64 planes: hypot
+ *       s  = (tr*gr + ti*gi) / (gr*gr + gi*gi)          Re(Vtg / Sx): the group delay relative to the frame centre, s
+ *       d  = rint(s * cols_per_second)                  round half to even
+ *       if not (|d| <= dmax): continue                  NaN and inf included
+ *       c2 = c + d;  if c2 < 0 or c2 >= n: continue
+ *       p  = (i * c * hop_len) mod n_fft                exact
+ *       (ur, ui) = rot ? rot[p] : (1, 0)
+ *       Tx[b,i,c2] += (ur*gr - ui*gi, ur*gi + ui*gr)    a cell's terms in ascending c; re and im separate sums
+ * and every cell is rounded once to `dtype`. Bit-reproducible from call to call; `batch` signals in one call equal
+ * `batch` calls of one signal bit for bit. One kernel: a wavefront per (signal, row, segment of
+ * ssq_time_reassign_segment() destination columns) holds its cells in LDS and walks the sources that can reach them,
+ * segment + 2 dmax columns, in ascending order; no global atomics, nothing of plane size is allocated. Planes that do
+ * not start on a 16-byte boundary take an element-load instance. Refused, with Tx unwritten and a message that begins
+ * with the entry's name: a null Sx, Vtg or Tx; batch, rows or n < 1; batch rows n >= 2^32; n_fft < 1 (or >= 2^31) or
+ * hop_len < 1; rows > n_fft; dmax < 0 or dmax > ssq_time_reassign_max_dmax() = 2^20 (a displacement and a wavefront's
+ * walk stay in 32 bits); cols_per_second not finite or <= 0; gamma < 0 or NaN. No counterpart in the reference. */
+int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* rot, void* Tx, int64_t batch, int64_t rows,
+                      int64_t n, int64_t n_fft, int64_t hop_len, double cols_per_second, int64_t dmax, double gamma,
+                      void* stream);
+/* The destination columns a wavefront of ssq_time_reassign owns, and the largest dmax the entry accepts. */
+int ssq_time_reassign_segment(void);
+int ssq_time_reassign_max_dmax(void);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

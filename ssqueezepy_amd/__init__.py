@@ -27,6 +27,7 @@ def __getattr__(name):
         'phase_stft': '_ssq_stft', 'ssq_stft2': '_ssq_stft2', 'ssq_cwt2': '_ssq_cwt2', 'ssqueeze': 'ssqueezing',
         'conceft_stft': '_conceft', 'hermite_windows': '_conceft', 'conceft_gpu': 'algos',
         'conceft_cwt': '_conceft_cwt', 'morse_wavelets': 'wavelets', 'conceft_cwt_gpu': 'algos',
+        'tssq_stft': '_tssq_stft', 'time_reassign_gpu': 'algos',
         'ssqueeze_fast': 'algos', 'indexed_sum_onfly': 'algos', 'buffer': 'algos',
         'replace_under_abs': 'algos', 'phase_cwt_gpu': 'algos',
         'phase_stft_gpu': 'algos', 'phase_stft2_gpu': 'algos', 'phase_cwt2_gpu': 'algos',

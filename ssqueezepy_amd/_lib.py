@@ -82,6 +82,10 @@ _PROTOS = {
                             c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int, c_int, c_void_p]),
     'ssq_conceft_cwt': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                                 c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int, c_int, c_void_p]),
+    'ssq_time_reassign': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                  c_int64, c_double, c_int64, c_double, c_void_p]),
+    'ssq_time_reassign_segment': (c_int, []),
+    'ssq_time_reassign_max_dmax': (c_int, []),
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
@@ -164,7 +168,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 112     # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 113     # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -374,6 +374,67 @@ def conceft_cwt_gpu(W, dW, proj, ssq_freqs, const, gamma, flipud=False, average=
         return to_device(np.ascontiguousarray(np.broadcast_to(c, (rows,))), torch.float64)
     logscale = infer_scaletype(ssq_freqs)[0].startswith('log')
     return _conceft_call('ssq_conceft_cwt', W, dW, weights, proj, ssq_freqs, logscale, gamma, flipud, average, out)
+
+
+_ROT_TABLES = {}
+
+
+def default_dmax(n_fft, hop_len):
+    """The largest displacement `time_reassign_gpu` keeps by default, in columns: half a window,
+    ``ceil((n_fft // 2) / hop_len)`` -- a centre of gravity outside the window is no estimate."""
+    return -(-(int(n_fft) // 2) // int(hop_len))
+
+
+def rotation_table(n_fft):
+    """``exp(-2j pi p / n_fft)``, ``p = 0 .. n_fft-1``, complex128 on the current device: NumPy's values, made once
+    per (device, n_fft) -- `time_reassign_gpu`'s default `rot`."""
+    key = (str(device()), int(n_fft))
+    if key not in _ROT_TABLES:
+        if len(_ROT_TABLES) >= 8:
+            _ROT_TABLES.pop(next(iter(_ROT_TABLES)))
+        _ROT_TABLES[key] = to_device(np.exp(-2j * np.pi * np.arange(int(n_fft)) / int(n_fft)))
+    return _ROT_TABLES[key]
+
+
+def time_reassign_gpu(Sx, Vtg, n_fft, hop_len, fs, gamma, rot=None, dmax=None, out=None):
+    """Time-reassigned synchrosqueezing in one kernel (`ssq_time_reassign`, include/ssq_hip.h states the definition;
+    DESIGN.md 4.5.7). `Sx`, `Vtg`: (rows, n) or (B, rows, n) complex -- the STFTs of one signal with the window `g` and
+    with ``tau g``, `tau` the window's time axis in seconds (0 at the centre). Every point with ``|Sx| >= gamma`` moves
+    along its row by ``d = rint(Re(Vtg / Sx) fs / hop_len)`` columns, if ``|d| <= dmax`` and the target is a column of
+    the plane, and is added there as ``Sx[i, c] rot[(i c hop_len) mod n_fft]``, a cell's terms in ascending `c`.
+    `rot`: None -> ``exp(-2j pi arange(n_fft) / n_fft)`` (cached per device and `n_fft`), False -> no rotation, or a
+    ``(n_fft,)`` complex table of the caller's. `dmax`: None -> ``ceil((n_fft // 2) / hop_len)``. Float64 arithmetic
+    for both precisions, rounded once; bit-reproducible."""
+    if gamma is None:
+        raise ValueError("`gamma` must not be None")
+    lib = _lib.load()
+    Sx = to_device(Sx)
+    if Sx.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Sx` must be complex64 or complex128 (got %s)" % Sx.dtype)
+    Vtg = to_device(Vtg, Sx.dtype)
+    if Vtg.shape != Sx.shape:
+        raise ValueError("`Sx` and `Vtg` must share one shape (got %s and %s)" % (tuple(Sx.shape), tuple(Vtg.shape)))
+    B, rows, n = _shape3(Sx)
+    n_fft, hop_len = int(n_fft), int(hop_len)
+    if n_fft < 1 or hop_len < 1:
+        raise ValueError("`n_fft` and `hop_len` must be >= 1 (got %d, %d)" % (n_fft, hop_len))
+    if rot is None:
+        rot = rotation_table(n_fft)
+    elif rot is False:
+        rot = None
+    else:
+        rot = to_device(rot, torch.complex128)
+        if rot.shape != (n_fft,):
+            raise ValueError("`rot` must be (n_fft,) = (%d,) (got %s)" % (n_fft, tuple(rot.shape)))
+    if dmax is None:
+        dmax = default_dmax(n_fft, hop_len)
+    if out is None:
+        out = torch.empty(Sx.shape, dtype=Sx.dtype, device=Sx.device)
+    else:
+        _check_out(out, Sx)
+    check(lib.ssq_time_reassign(_CDT[Sx.dtype], _ptr(Sx), _ptr(Vtg), _ptr(rot), _ptr(out), B, rows, n, n_fft, hop_len,
+                                float(fs) / hop_len, int(dmax), float(gamma), stream()))
+    return out
 
 
 def replace_under_abs(x, ref=None, value=1., replacement=0., parallel=None):

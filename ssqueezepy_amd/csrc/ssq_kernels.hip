@@ -22,6 +22,8 @@
 //       (They share Phase2Vec and launch_phase2; why not more: DESIGN.md section 4.5.3.)
 //   conceft_kernel           multitaper synchrosqueezing: Q projections of J transforms mixed, reassigned into an
 //       LDS tile in row order and averaged, in one kernel; an STFT and a CWT form (ssq_conceft.inl).
+//   time_reassign_kernel     time-reassigned synchrosqueezing: every point moves along its row to its group delay, a
+//       wavefront per destination segment adding into an LDS strip in source order (ssq_time_reassign.inl).
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
 #include "ssq_common.h"
 #include <cfloat>
@@ -961,6 +963,7 @@ static void launch_phase2(K vec_kernel, K element_kernel, const void* const (&pl
 }
 
 #include "ssq_conceft.inl"
+#include "ssq_time_reassign.inl"
 
 }  // namespace ssq
 
@@ -974,7 +977,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 112; }   // 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 113; }   // 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -1245,6 +1248,35 @@ int ssq_conceft_cwt(int dtype, const void* const* W, const void* const* dW, cons
                     const double* params, int flipud, int average, void* stream) {
     return conceft_entry(true, "ssq_conceft_cwt", dtype, W, dW, cst, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
                          flipud, average, stream);
+}
+
+int ssq_time_reassign_segment(void) { return TSSQ_SEG; }
+int ssq_time_reassign_max_dmax(void) { return (int)TSSQ_MAX_DMAX; }
+
+int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* rot, void* Tx, int64_t batch, int64_t rows,
+                      int64_t n, int64_t n_fft, int64_t hop_len, double cols_per_second, int64_t dmax, double gamma,
+                      void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(Sx && Vtg && Tx, "ssq_time_reassign: null pointer");
+    SSQ_REQUIRE(batch >= 1 && rows >= 1 && n >= 1, "ssq_time_reassign: bad shape (%lld, %lld, %lld): batch, rows, n >= 1",
+                (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
+                "ssq_time_reassign: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)rows,
+                (long long)n);
+    SSQ_REQUIRE(n_fft >= 1 && n_fft <= (int64_t)0x7FFFFFFF && hop_len >= 1,
+                "ssq_time_reassign: n_fft = %lld, hop_len = %lld: n_fft 1 .. 2^31 - 1, hop_len >= 1", (long long)n_fft,
+                (long long)hop_len);
+    SSQ_REQUIRE(rows <= n_fft, "ssq_time_reassign: %lld rows of an n_fft of %lld", (long long)rows, (long long)n_fft);
+    SSQ_REQUIRE(dmax >= 0 && dmax <= TSSQ_MAX_DMAX, "ssq_time_reassign: dmax = %lld, 0 .. %lld", (long long)dmax,
+                (long long)TSSQ_MAX_DMAX);
+    SSQ_REQUIRE(cols_per_second > 0.0 && cols_per_second <= DBL_MAX,
+                "ssq_time_reassign: cols_per_second must be positive and finite (got %g)", cols_per_second);
+    SSQ_REQUIRE(gamma >= 0.0, "ssq_time_reassign: gamma must be >= 0 (got %g)", gamma);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_time_reassign<T>(Sx, Vtg, rot, Tx, batch, rows, n, n_fft, hop_len, cols_per_second, dmax, gamma,
+                                       as_stream(stream));
+    });
 }
 
 int ssq_replace_under_abs(int dtype, void* w, const void* ref, int64_t count, double value,
