@@ -22,6 +22,8 @@ HIPCC = os.path.join(ROCM, 'bin', 'hipcc')
 # (source, extra flags)
 SOURCES = [
     ('ssq_kernels.hip', ['-ffp-contract=off']),
+    ('ssq_conceft.hip', ['-ffp-contract=off']),
+    ('ssq_time_reassign.hip', ['-ffp-contract=off']),
     ('ssq_cwt.hip', ['-ffp-contract=off']),
     ('ssq_cwt_blocks.hip', ['-ffp-contract=off']),
     ('ssq_cwt_tiles.hip', ['-ffp-contract=off']),

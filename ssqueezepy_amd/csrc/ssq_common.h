@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include "../../include/ssq_hip.h"
 
@@ -158,6 +159,85 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 // are the same text but for the type -- an arm that differs in more stays written out.
 template <typename F>
 static inline int dispatch_dtype(int dtype, F&& f) { return dtype == SSQ_F32 ? f(float{}) : f(double{}); }
+// ... and where a run-time flag does: `f(std::true_type{})` or `f(std::false_type{})`. Both arms are instantiated, so a
+// combination that must not exist (a float64 weight product for float64 data) is masked inside f:
+// `constexpr bool C64 = decltype(c)::value && sizeof(T) == 4`.
+template <typename F>
+static inline int dispatch_bool(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+template <int N> using int_c = std::integral_constant<int, N>;
+
+// Launch a kernel that takes `lds` bytes of dynamic LDS, up to the 160 KiB of a CU: raise the function's limit, launch,
+// check. The attribute is set at every launch (it belongs to the function ON THE CURRENT DEVICE, a flag per
+// instantiation would leave a second device of the process without it; the call costs well under a microsecond) and
+// always to the full 160 KiB, as the tile kernels always had it. The sites that used to set the launch's own size
+// could undercut each other -- thread A sets 100 KiB, thread B sets 50 KiB, A's launch is refused -- so the constant
+// is a fix of those sites, not only a fold.
+constexpr size_t LDS_CAP = 160 * 1024;
+template <typename K, typename... Args>
+static inline int launch_lds(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)LDS_CAP));
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    SSQ_LAUNCH_CHECK();
+    return 0;
+}
+
+// grid of a streaming kernel over `total` items
+static inline unsigned stream_grid(int64_t total, int block = 256) {
+    int64_t g = (total + block - 1) / block;
+    const int64_t cap = 256 * 8 * 4;   // 256 CUs x 8 blocks, grid-stride the rest
+    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// ---- refusals that several entries state word for word (`name` opens the message)
+static inline int check_dtype(int dtype) {
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "dtype must be SSQ_F32 or SSQ_F64 (got %d)", dtype);
+    return 0;
+}
+// (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
+static inline int check_point_count(const char* name, int64_t batch, int64_t rows, int64_t n) {
+    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
+                "%s: %lld x %lld x %lld points, at most 2^32 - 1", name, (long long)batch, (long long)rows, (long long)n);
+    return 0;
+}
+static inline int check_gamma(const char* name, double gamma) {
+    SSQ_REQUIRE(gamma >= 0.0, "%s: gamma must be >= 0 (got %g)", name, gamma);
+    return 0;
+}
+
+// A small table on the current device, keyed by (device, uploaded bytes): uploaded once and kept -- a call that finds
+// its table enqueues nothing (no allocation, no copy, nothing for the host to wait for), so it can be captured into a
+// graph once its table exists. The eight most recent tables stay; an older one is freed with hipFree, which waits for
+// the kernels that may still read it.
+struct DeviceTableCache {
+    struct Entry { int dev; std::vector<unsigned char> bytes; void* d; };
+    std::mutex mu;
+    std::vector<Entry> kept;
+    template <typename P>
+    int get(const P* host, size_t count, const P** out) {
+        const size_t bytes = count * sizeof(P);
+        int dev = 0;
+        SSQ_CHECK_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lock(mu);
+        for (const Entry& t : kept)
+            if (t.dev == dev && t.bytes.size() == bytes && memcmp(t.bytes.data(), host, bytes) == 0) {
+                *out = static_cast<const P*>(t.d);
+                return 0;
+            }
+        if (kept.size() >= 8) {
+            (void)hipFree(kept.front().d);
+            kept.erase(kept.begin());
+        }
+        void* d = nullptr;
+        SSQ_CHECK_HIP(hipMalloc(&d, bytes));
+        hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); SSQ_CHECK_HIP(e); }
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(host);
+        kept.push_back(Entry{dev, std::vector<unsigned char>(b, b + bytes), d});
+        *out = static_cast<const P*>(d);
+        return 0;
+    }
+};
 
 // Stream-ordered temporaries of one host function: `alloc` is hipMallocAsync on the guard's stream, the
 // destructor hipFreeAsync on the same stream for everything handed out, in that order -- at every return.
@@ -221,36 +301,39 @@ struct WeightVersions {
     void destroy() { for (void* p : bufs) (void)hipFree(p); bufs.clear(); }
 };
 
+// The signal-extension rule, for pad_kernel on the device and for its transpose below on the host:
+// t in [-n1, n + n2); returns the source index in [0, n) or -1 for zero fill
+__host__ __device__ static inline int64_t pad_source(int64_t t, int64_t n, int padtype) {
+    if (t >= 0 && t < n) return t;
+    switch (padtype) {
+        case SSQ_PAD_REFLECT: {
+            if (n == 1) return 0;
+            int64_t period = 2 * (n - 1);
+            int64_t m = t % period; if (m < 0) m += period;
+            return m < n ? m : period - m;
+        }
+        case SSQ_PAD_SYMMETRIC: {
+            int64_t period = 2 * n;
+            int64_t m = t % period; if (m < 0) m += period;
+            return m < n ? m : period - 1 - m;
+        }
+        case SSQ_PAD_REPLICATE: return t < 0 ? 0 : n - 1;
+        case SSQ_PAD_WRAP: { int64_t m = t % n; if (m < 0) m += n; return m; }
+        default: return -1;
+    }
+}
+
 // The transpose of a signal extension, for the adjoints (ssq_stft_adjoint, ssq_cwt_adjoint): the padded positions
-// p in [0, m) that copy signal sample j -- position p reads sample p - n1 through the rule of pad_kernel --, per j,
+// p in [0, m) that copy signal sample j -- position p reads sample p - n1 through pad_source --, per j,
 // ascending: `idx[off[j] .. off[j + 1])`. Zero padding has no source and is left out. m < 2^31.
 static inline void inverse_pad_table(int64_t n, int64_t m, int64_t n1, int padtype, std::vector<int32_t>& off,
                                      std::vector<int32_t>& idx) {
-    auto source = [&](int64_t t) -> int64_t {
-        if (t >= 0 && t < n) return t;
-        switch (padtype) {
-            case SSQ_PAD_REFLECT: {
-                if (n == 1) return 0;
-                const int64_t period = 2 * (n - 1);
-                int64_t q = t % period; if (q < 0) q += period;
-                return q < n ? q : period - q;
-            }
-            case SSQ_PAD_SYMMETRIC: {
-                const int64_t period = 2 * n;
-                int64_t q = t % period; if (q < 0) q += period;
-                return q < n ? q : period - 1 - q;
-            }
-            case SSQ_PAD_REPLICATE: return t < 0 ? 0 : n - 1;
-            case SSQ_PAD_WRAP: { int64_t q = t % n; if (q < 0) q += n; return q; }
-            default: return -1;
-        }
-    };
     off.assign((size_t)n + 1, 0);
-    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) ++off[(size_t)j + 1]; }
+    for (int64_t p = 0; p < m; ++p) { const int64_t j = pad_source(p - n1, n, padtype); if (j >= 0) ++off[(size_t)j + 1]; }
     for (int64_t j = 0; j < n; ++j) off[(size_t)j + 1] += off[(size_t)j];
     idx.assign((size_t)off[(size_t)n], 0);
     std::vector<int32_t> fill(off.begin(), off.end() - 1);
-    for (int64_t p = 0; p < m; ++p) { const int64_t j = source(p - n1); if (j >= 0) idx[(size_t)fill[(size_t)j]++] = (int32_t)p; }
+    for (int64_t p = 0; p < m; ++p) { const int64_t j = pad_source(p - n1, n, padtype); if (j >= 0) idx[(size_t)fill[(size_t)j]++] = (int32_t)p; }
 }
 
 template <typename T> struct cplx { T re, im; };
@@ -292,6 +375,20 @@ static inline void finalize_params(SsqParams& sp) {
     }
     if (!(g < 0.25)) g = 1.0;
     sp.guard = (float)g;
+}
+
+// the parameters of a C-ABI call; `name`, where given, opens the refusals' messages
+static inline int fill_params(SsqParams& sp, int grid, const double* params, int flipud, double gamma, int cst_f64,
+                              const char* name = nullptr) {
+    const bool known = grid >= SSQ_GRID_LOG && grid <= SSQ_GRID_LIN;
+    if (name) SSQ_REQUIRE(known, "%s: unknown grid kind %d", name, grid);
+    SSQ_REQUIRE(known, "unknown grid kind %d", grid);
+    SSQ_REQUIRE(params, "grid params must not be null");
+    for (int t = 0; t < 5; ++t) sp.p[t] = params[t];
+    sp.grid = grid; sp.flipud = flipud ? 1 : 0; sp.gamma = gamma; sp.cst_f64 = cst_f64 ? 1 : 0;
+    sp.cst_uniform = 0;                   // weights are a device array here: not inspected
+    finalize_params(sp);
+    return 0;
 }
 
 // ---- launchers implemented in ssq_kernels.hip, used by the plans --------------

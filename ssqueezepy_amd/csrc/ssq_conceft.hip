@@ -1,7 +1,7 @@
-// ssq_conceft.inl -- ssq_conceft, ssq_conceft_cwt: multitaper synchrosqueezing (ConceFT; Daubechies, Wang, Wu 2016) in
-// one kernel, in its STFT and its CWT form.
-// Included by ssq_kernels.hip inside `namespace ssq`, after the accumulate kernels whose ordered row-lane combine
-// (FoldLower) it shares. include/ssq_hip.h states what is computed; DESIGN.md section 4.5.5 the sizing.
+// ssq_conceft.hip -- ssq_conceft, ssq_conceft_cwt: multitaper synchrosqueezing (ConceFT; Daubechies, Wang, Wu 2016) in
+// one kernel, in its STFT and its CWT form: kernel, projection table, launcher and the two C-ABI entries.
+// include/ssq_hip.h states what is computed; DESIGN.md section 4.5.5 the sizing. Compiled with -ffp-contract=off (bin
+// indices), like ssq_kernels.hip, whose ordered row-lane combine it shares (ssq_reassign_dev.h).
 //
 // A workgroup owns a tile of TC adjacent columns of one signal, a wavefront WC = 4 of them x 16 row-lanes (lane =
 // 16 * column + row-lane) -- the float64 layout of accumulate_tile16_kernel. Its wavefronts never synchronise with each
@@ -15,6 +15,14 @@
 // CWT = false is ssq_conceft: a row's value is Sfs[i] (the planes' real dtype), w = |Sfs[i] - phase_ratio| and a term is
 // Vq. CWT = true is ssq_conceft_cwt: a row's value is the weight cst[i] (float64), w = |phase_ratio| and a term is
 // Vq * cst[i]; on the log grids the bin map takes log2(w), inside the branch that a point below gamma skips.
+#include "ssq_common.h"
+#include "ssq_reassign_dev.h"
+#include <type_traits>
+
+namespace ssq {
+
+#include "ssq_point_math.inl"
+
 struct ConceftPlanes { const void* v[8]; const void* dv[8]; };
 
 // rows a tile of TC columns supports: TC * 16 bytes per row in 160 KiB of LDS, 16 NC cells per column in registers
@@ -125,54 +133,82 @@ __global__ __launch_bounds__(64 * (TC / 4)) void conceft_kernel(
     }
 }
 
-// r[q][j] on the current device, (Q, J, 2) float64: uploaded once per (device, contents) and kept, like the row
-// tables of ssq_cwt2_phase -- a call that finds its table enqueues the kernel and nothing else. The eight most
-// recent stay; an older one is freed with hipFree, which waits for the kernels that may still read it.
-struct ConceftTable { int dev; std::vector<double> proj; double* d; };
-static std::mutex g_conceft_mutex;
-static std::vector<ConceftTable> g_conceft_tables;
-
-static int conceft_proj_table(const double* proj, size_t count, const double** out) {
-    int dev = 0;
-    SSQ_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_conceft_mutex);
-    for (const ConceftTable& t : g_conceft_tables)
-        if (t.dev == dev && t.proj.size() == count && memcmp(t.proj.data(), proj, count * sizeof(double)) == 0) {
-            *out = t.d;
-            return 0;
-        }
-    if (g_conceft_tables.size() >= 8) {
-        (void)hipFree(g_conceft_tables.front().d);
-        g_conceft_tables.erase(g_conceft_tables.begin());
-    }
-    double* d = nullptr;
-    SSQ_CHECK_HIP(hipMalloc((void**)&d, count * sizeof(double)));
-    hipError_t e = hipMemcpy(d, proj, count * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); SSQ_CHECK_HIP(e); }
-    g_conceft_tables.push_back(ConceftTable{dev, std::vector<double>(proj, proj + count), d});
-    *out = d;
-    return 0;
-}
+// r[q][j] on the current device, (Q, J, 2) float64: uploaded once per (device, contents) and kept
+static DeviceTableCache g_conceft_tables;
 
 template <typename T, bool CPLX, bool CWT>
 static int launch_conceft(const ConceftPlanes& P, const void* Sfs, const double* proj, void* Cx, const SsqParams& sp,
                           int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, hipStream_t stream) {
     using R = std::conditional_t<CWT, double, T>;             // the row vector's element: Sfs, or the float64 weights
     // the widest tile whose rows fit the LDS and whose cells fit the lanes' registers
-#define SSQ_CONCEFT(TC, NC)                                                                                       \
-    {                                                                                                             \
-        const size_t lds = (size_t)rows * TC * 16;                                                                \
-        const unsigned tiles = (unsigned)((n + TC - 1) / TC);                                                     \
-        auto kern = conceft_kernel<T, TC, NC, CPLX, CWT>;                                                         \
-        SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                                    \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
-        hipLaunchKernelGGL(kern, dim3(tiles * (unsigned)batch), dim3(64 * (TC / 4)), lds, stream, P,              \
-                           (const R*)Sfs, proj, (T*)Cx, sp, (int)J, (int)Q, (int)rows, (int)n, tiles);            \
-    }
-    if (rows <= 16 * 17) SSQ_CONCEFT(16, 17)
-    else if (rows <= 16 * 40) SSQ_CONCEFT(16, 40)
-    else SSQ_CONCEFT(8, 80)
-#undef SSQ_CONCEFT
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    auto launch = [&](auto tc, auto nc) -> int {
+        constexpr int TC = decltype(tc)::value, NC = decltype(nc)::value;
+        const unsigned tiles = (unsigned)((n + TC - 1) / TC);
+        return launch_lds(conceft_kernel<T, TC, NC, CPLX, CWT>, dim3(tiles * (unsigned)batch), dim3(64 * (TC / 4)),
+                          (size_t)rows * TC * 16, stream, P, (const R*)Sfs, proj, (T*)Cx, sp, (int)J, (int)Q, (int)rows,
+                          (int)n, tiles);
+    };
+    if (rows <= 16 * 17) return launch(int_c<16>{}, int_c<17>{});
+    if (rows <= 16 * 40) return launch(int_c<16>{}, int_c<40>{});
+    return launch(int_c<8>{}, int_c<80>{});
 }
+
+}  // namespace ssq
+
+using namespace ssq;
+
+// ssq_conceft and ssq_conceft_cwt: one set of checks, one launcher. `rowv` is Sfs (the planes' real dtype) for the STFT
+// form and the float64 weights cst for the CWT form; `name` opens every refusal's message.
+static int conceft_entry(bool cwt, const char* name, int dtype, const void* const* V, const void* const* dV,
+                         const void* rowv, const double* proj, void* Cx, int64_t batch, int64_t J, int64_t Q, int64_t rows,
+                         int64_t n, double gamma, int grid, const double* params, int flipud, int average, void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(J >= 1 && J <= 8, "%s: J = %lld, 1 .. 8 transforms", name, (long long)J);
+    SSQ_REQUIRE(Q >= 1 && Q <= 1024, "%s: Q = %lld, 1 .. 1024 projections", name, (long long)Q);
+    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "%s: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1", name,
+                (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(rows <= CONCEFT_MAX_ROWS, "%s: %lld rows, at most %lld (an 8-column float64 tile in 160 KiB of LDS)", name,
+                (long long)rows, (long long)CONCEFT_MAX_ROWS);
+    if (check_point_count(name, batch, rows, n)) return -1;
+    SSQ_REQUIRE(V && dV && rowv && proj && Cx && params, "%s: null pointer", name);
+    ConceftPlanes P = {};
+    for (int64_t j = 0; j < J; ++j) {
+        SSQ_REQUIRE(V[j] && dV[j], "%s: plane %lld is a null pointer", name, (long long)j);
+        P.v[j] = V[j]; P.dv[j] = dV[j];
+    }
+    for (int64_t t = 0; t < 2 * Q * J; ++t)
+        SSQ_REQUIRE(proj[t] - proj[t] == 0.0, "%s: proj[%lld][%lld] is not finite", name, (long long)(t / (2 * J)),
+                    (long long)(t / 2 % J));
+    if (check_gamma(name, gamma)) return -1;
+    SsqParams sp;
+    if (fill_params(sp, grid, params, flipud, gamma, cwt ? 1 : 0, name)) return -1;
+    const double* rdev = nullptr;
+    if (g_conceft_tables.get(proj, (size_t)(2 * Q * J), &rdev)) return -1;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dispatch_bool(cwt, [&](auto c) {
+            return dispatch_bool(average != 0, [&](auto a) {
+                return launch_conceft<T, decltype(a)::value, decltype(c)::value>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n,
+                                                                                as_stream(stream));
+            });
+        });
+    });
+}
+
+extern "C" {
+
+int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
+                int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid, const double* params,
+                int flipud, int average, void* stream) {
+    return conceft_entry(false, "ssq_conceft", dtype, V, dV, Sfs, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
+                         flipud, average, stream);
+}
+
+int ssq_conceft_cwt(int dtype, const void* const* W, const void* const* dW, const void* cst, const double* proj, void* Cx,
+                    int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
+                    const double* params, int flipud, int average, void* stream) {
+    return conceft_entry(true, "ssq_conceft_cwt", dtype, W, dW, cst, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
+                         flipud, average, stream);
+}
+
+}  // extern "C"

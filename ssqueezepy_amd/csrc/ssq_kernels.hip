@@ -20,15 +20,13 @@
 //   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
 //   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
 //       (They share Phase2Vec and launch_phase2; why not more: DESIGN.md section 4.5.3.)
-//   conceft_kernel           multitaper synchrosqueezing: Q projections of J transforms mixed, reassigned into an
-//       LDS tile in row order and averaged, in one kernel; an STFT and a CWT form (ssq_conceft.inl).
-//   time_reassign_kernel     time-reassigned synchrosqueezing: every point moves along its row to its group delay, a
-//       wavefront per destination segment adding into an LDS strip in source order (ssq_time_reassign.inl).
 //   replace_under_abs_kernel, buffer_kernel, pad_kernel.
+// See also: conceft_kernel (ssq_conceft.hip) and time_reassign_kernel (ssq_time_reassign.hip), which share the ordered
+// row-lane combine of accumulate_tile16_kernel through ssq_reassign_dev.h.
 #include "ssq_common.h"
+#include "ssq_reassign_dev.h"
 #include <cfloat>
 #include <cstdlib>
-#include <mutex>
 #include <string>
 
 namespace ssq {
@@ -46,7 +44,9 @@ void set_error(const char* fmt, ...) {
 
 #include "ssq_point_math.inl"
 
-// out += z * cst   in the CPU path's arithmetic
+// out += z * cst   in the CPU path's arithmetic: Term::fold(o, Term::make(z, w)), kept written out for
+// accumulate_tile_kernel -- through Term the float64-weight build converts the cell after the product instead of before
+// it and the kernel's instructions come out in another order (profiles/reassign_fold_isa.txt)
 template <typename T, bool CST64>
 __device__ __forceinline__ void weighted_add(T& o_re, T& o_im, T c, T d, const void* cst, int64_t i) {
     if constexpr (CST64 && sizeof(T) == 4) {
@@ -197,74 +197,8 @@ __global__ __launch_bounds__(64) void accumulate_tile_kernel(
 //     depth U; loads unconditional so that the compiler can count them);
 //   * cells are stored skewed (cell (k, c) at WC*k + ((c + k) & (WC-1)) of the wave's
 //     slab) to spread the columns of a wave over LDS banks.
-template <int CTRL> __device__ __forceinline__ int dpp_mov(int old, int v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL> __device__ __forceinline__ float dpp_mov(float old, float v) {
-    return __int_as_float(dpp_mov<CTRL>(__float_as_int(old), __float_as_int(v)));
-}
-template <int CTRL> __device__ __forceinline__ double dpp_mov(double old, double v) {
-    int lo = dpp_mov<CTRL>(__double2loint(old), __double2loint(v));
-    int hi = dpp_mov<CTRL>(__double2hiint(old), __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
-// the additive term of one point and how it is folded into a cell, in the CPU path's
-// arithmetic: float32 data with a float64 weight vector accumulates through double
-template <typename T, bool CST64> struct Term {
-    using type = T;
-    using wtype = T;
-    static __device__ __forceinline__ T make(T z, T w) { return z * w; }
-    static __device__ __forceinline__ T fold(T o, T t) { return o + t; }
-};
-template <> struct Term<float, true> {
-    using type = double;
-    using wtype = double;
-    static __device__ __forceinline__ double make(float z, double w) { return (double)z * w; }
-    static __device__ __forceinline__ float fold(float o, double t) { return (float)((double)o + t); }
-};
-
-// fold in the terms of row-lanes rl-15 .. rl-1 that target the same cell, ascending.
-// The match test of distance N yields a wave mask (one compare); from it come, for
-// free on the scalar unit, (a) the decision whether anything has to move at this
-// distance and (b) the "a higher row-lane hits my cell" mask: lane L+N matching at
-// distance N is lane L having a higher partner at distance N (row_shr never crosses a
-// 16-lane row, so mask >> N stays inside the column).
-// SC (scalar combine): the per-distance decision is one DPP move + one compare, the rest
-// scalar -- measured faster with 8 row-lanes (245 vs 263 us), slower with 16 (263 vs 257),
-// so each layout keeps the form that suits it.
-template <int N, bool SC, typename TM, typename T, typename term_t>
-struct FoldLower {
-    static __device__ __forceinline__ void run(int k, unsigned long long valid, term_t tr, term_t ti,
-                                               T& ore, T& oim, unsigned long long& higher) {
-        // row_shr:N with bound_ctrl: lanes without a source in their row read 0. Keys are
-        // bin + 1 (0 = "takes no part", `valid` = the wave mask of k != 0), so a lane that
-        // takes part never matches a missing source.
-        const int ks = __builtin_amdgcn_update_dpp(0, k, 0x110 + N, 0xF, 0xF, true);
-        bool m;
-        unsigned long long mask;
-        if constexpr (SC) {
-            const bool e = ks == k;
-            mask = __builtin_amdgcn_ballot_w64(e) & valid;
-            m = e & (k != 0);
-        } else {
-            m = (ks == k) & (k != 0);
-            mask = __ballot(m);
-        }
-        if (mask) {                                         // wave-uniform
-            higher |= mask >> N;
-            term_t rs = dpp_mov<0x110 + N>(term_t(0), tr), is = dpp_mov<0x110 + N>(term_t(0), ti);
-            if (m) { ore = TM::fold(ore, rs); oim = TM::fold(oim, is); }
-        }
-        FoldLower<N - 1, SC, TM, T, term_t>::run(k, valid, tr, ti, ore, oim, higher);
-    }
-};
-template <bool SC, typename TM, typename T, typename term_t>
-struct FoldLower<0, SC, TM, T, term_t> {
-    static __device__ __forceinline__ void run(int, unsigned long long, term_t, term_t, T&, T&,
-                                               unsigned long long&) {}
-};
-
+// (dpp_mov, Term and FoldLower: ssq_reassign_dev.h)
+//
 // RL = row-lanes per column (16 or 8): a wavefront covers WC = 64/RL columns and the
 // 16-column tile takes 16/WC wavefronts. With RL = 8 two columns share a 16-lane DPP
 // row; their keys are made distinct so that a shift across the boundary never matches.
@@ -493,20 +427,13 @@ static int launch_accumulate_f64(const void* Wx, const void* kidx, void* Tx, con
     constexpr int NW = 8, U = 4;                   // wavefronts per tile, rows in flight per lane
     const size_t lds = (size_t)na * cols * 16;
     dim3 grid((unsigned)(((n + cols - 1) / cols + 7) / 8 * 8), (unsigned)batch);
-#define SSQ_ACC64(C)                                                                               \
-    {                                                                                              \
-        auto kern = accumulate_f64_kernel<T, CST64, C, NW, U>;                                     \
-        SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                     \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));  \
-        hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, stream, (const T*)Wx,                   \
-                           (const unsigned short*)kidx, (T*)Tx, cst, (int)sp.cst_uniform, (int)na, \
-                           (int)n);                                                                \
-    }
-    if (cols == 32) SSQ_ACC64(32)
-    else if (cols == 16) SSQ_ACC64(16)
-    else if constexpr (sizeof(T) == 8) SSQ_ACC64(8)      // (8 columns: float64 data only, see f64_tile_cols)
-#undef SSQ_ACC64
-    SSQ_LAUNCH_CHECK();
+    auto launch = [&](auto c) -> int {
+        return launch_lds(accumulate_f64_kernel<T, CST64, decltype(c)::value, NW, U>, grid, dim3(64 * NW), lds, stream,
+                          (const T*)Wx, (const unsigned short*)kidx, (T*)Tx, cst, (int)sp.cst_uniform, (int)na, (int)n);
+    };
+    if (cols == 32) return launch(int_c<32>{});
+    if (cols == 16) return launch(int_c<16>{});
+    if constexpr (sizeof(T) == 8) return launch(int_c<8>{});    // (8 columns: float64 data only, see f64_tile_cols)
     return 0;
 }
 
@@ -517,6 +444,8 @@ __global__ __launch_bounds__(256) void accumulate_global_kernel(
     const T* __restrict__ Wx, const void* __restrict__ src, const T* __restrict__ Sfs,
     T* __restrict__ Tx, const void* __restrict__ cst, SsqParams sp, int64_t na, int64_t n,
     int32_t* __restrict__ kmap) {
+    using TM = Term<T, CST64>;
+    using w_t = typename TM::wtype;
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const int64_t base = (int64_t)blockIdx.y * na * n;
@@ -530,9 +459,9 @@ __global__ __launch_bounds__(256) void accumulate_global_kernel(
         if (kmap) kmap[q] = (int32_t)k;
         if (k < 0) continue;
         T* o = Tx + 2 * (base + k * n + j);
-        T ore = o[0], oim = o[1];
-        weighted_add<T, CST64>(ore, oim, c, d, cst, i);
-        o[0] = ore; o[1] = oim;
+        const T ore = o[0], oim = o[1];
+        const w_t w = ((const w_t*)cst)[i];
+        o[0] = TM::fold(ore, TM::make(c, w)); o[1] = TM::fold(oim, TM::make(d, w));
     }
 }
 
@@ -541,7 +470,7 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
                                const void* cst, const SsqParams& sp, int64_t batch,
                                int64_t na, int64_t n, int32_t* kmap, hipStream_t stream) {
     const size_t cell = 2 * sizeof(T);
-    const size_t lds_cap = 160 * 1024;
+    const size_t lds_cap = LDS_CAP;
     if constexpr (BINSRC == BIN_FROM_KIDX) {
         // known bins: the unordered float64 tile (see accumulate_f64_kernel) unless the caller
         // asked for the ordered sums or wants the bin map back
@@ -549,68 +478,45 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
         if (!reassign_ordered() && !kmap && cols && (size_t)na * (size_t)n < ((size_t)1 << 31))
             return launch_accumulate_f64<T, CST64>(Wx, src, Tx, cst, sp, batch, na, n, cols, stream);
     }
-    auto launch_tile = [&](auto tc_tag) -> int {
-        constexpr int TC = decltype(tc_tag)::value;
-        size_t lds = (size_t)na * TC * cell;
-        auto kern = accumulate_tile_kernel<T, BINSRC, STFT, CST64, TC>;
-        SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        dim3 grid((unsigned)((n + TC - 1) / TC), (unsigned)batch);
-        hipLaunchKernelGGL(kern, grid, dim3(64), lds, stream, (const T*)Wx, src, (const T*)Sfs,
-                           (T*)Tx, cst, sp, na, n, kmap);
-        SSQ_LAUNCH_CHECK();
-        return 0;
+    auto launch_tile = [&](auto tc) -> int {
+        constexpr int TC = decltype(tc)::value;
+        return launch_lds(accumulate_tile_kernel<T, BINSRC, STFT, CST64, TC>, dim3((unsigned)((n + TC - 1) / TC), (unsigned)batch),
+                          dim3(64), (size_t)na * TC * cell, stream, (const T*)Wx, src, (const T*)Sfs, (T*)Tx, cst, sp, na, n,
+                          kmap);
     };
-    // 16-column tiles use the DPP-combined, double-buffered kernel
-    if ((size_t)na * 16 * cell <= lds_cap) {
-        size_t lds = (size_t)na * 16 * cell;
-        if ((size_t)na * (size_t)n < ((size_t)1 << 31)) {      // 32-bit offsets inside
-            dim3 grid((unsigned)(((n + 15) / 16 + 7) / 8 * 8), (unsigned)batch);
-            // Row batches in flight per lane. Measured (config 2, float32), 16 row-lanes:
-            // U = 2: 257 us, 3: 263, 4: 259, 8: 278; 8 row-lanes: U = 1: 314, 2: 246, 3: 240,
-            // 4: 243, 8: 267 -- the resident wavefronts cover most of the latency, and a
-            // deep prefetch spreads each wavefront's requests over more DRAM pages.
-            // float32: 8 row-lanes x 8 columns per wavefront, 2 wavefronts per 16-column tile (240 us
-            // at config 2 vs 250 with 16 row-lanes); float64: 16 row-lanes x 4 columns, 4 wavefronts
-            // (config 5: 22.7 vs 23.6 ms).
-            if constexpr (sizeof(T) == 4) {
-                constexpr int U8 = 3;
-                if ((size_t)na * 32 * cell <= lds_cap / 2) {
-                    // 32-column tiles of four 8-lane wavefronts (256-byte row segments per workgroup,
-                    // 2 workgroups per CU): 232 us at config 2 vs 240 with 16-column tiles (64-column
-                    // tiles, one workgroup per CU: 231)
-                    auto kern = accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U8, 2, 8, 32>;
-                    const size_t lds32 = (size_t)na * 32 * cell;
-                    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds32));
-                    dim3 grid32((unsigned)(((n + 31) / 32 + 7) / 8 * 8), (unsigned)batch);
-                    hipLaunchKernelGGL(kern, grid32, dim3(256), lds32, stream, (const T*)Wx, src, (const T*)Sfs,
-                                       (T*)Tx, cst, sp, na, n, kmap);
-                } else {
-                    auto kern = accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U8, 2, 8>;
-                    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    hipLaunchKernelGGL(kern, grid, dim3(128), lds, stream, (const T*)Wx, src, (const T*)Sfs,
-                                       (T*)Tx, cst, sp, na, n, kmap);
-                }
-            } else {
-                constexpr int U = 4;
-                auto kern = accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U, 4, 16>;
-                SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)Wx, src, (const T*)Sfs,
-                                   (T*)Tx, cst, sp, na, n, kmap);
-            }
-            SSQ_LAUNCH_CHECK();
-            return 0;
+    // the DPP-combined, double-buffered kernel: U row batches in flight, RL row-lanes x 64 / RL columns per wavefront,
+    // TC-column tiles
+    auto launch_tile16 = [&](auto u, auto wps, auto rl, auto tc) -> int {
+        constexpr int U = decltype(u)::value, WPS = decltype(wps)::value, RL = decltype(rl)::value, TC = decltype(tc)::value;
+        return launch_lds(accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U, WPS, RL, TC>,
+                          dim3((unsigned)(((n + TC - 1) / TC + 7) / 8 * 8), (unsigned)batch), dim3(64 * (TC / (64 / RL))),
+                          (size_t)na * TC * cell, stream, (const T*)Wx, src, (const T*)Sfs, (T*)Tx, cst, sp, na, n, kmap);
+    };
+    // 32-bit offsets inside
+    if ((size_t)na * 16 * cell <= lds_cap && (size_t)na * (size_t)n < ((size_t)1 << 31)) {
+        // Row batches in flight per lane. Measured (config 2, float32), 16 row-lanes:
+        // U = 2: 257 us, 3: 263, 4: 259, 8: 278; 8 row-lanes: U = 1: 314, 2: 246, 3: 240,
+        // 4: 243, 8: 267 -- the resident wavefronts cover most of the latency, and a
+        // deep prefetch spreads each wavefront's requests over more DRAM pages.
+        // float32: 8 row-lanes x 8 columns per wavefront, 2 wavefronts per 16-column tile (240 us
+        // at config 2 vs 250 with 16 row-lanes); float64: 16 row-lanes x 4 columns, 4 wavefronts
+        // (config 5: 22.7 vs 23.6 ms).
+        if constexpr (sizeof(T) == 4) {
+            // 32-column tiles of four 8-lane wavefronts (256-byte row segments per workgroup,
+            // 2 workgroups per CU): 232 us at config 2 vs 240 with 16-column tiles (64-column
+            // tiles, one workgroup per CU: 231)
+            if ((size_t)na * 32 * cell <= lds_cap / 2) return launch_tile16(int_c<3>{}, int_c<2>{}, int_c<8>{}, int_c<32>{});
+            return launch_tile16(int_c<3>{}, int_c<2>{}, int_c<8>{}, int_c<16>{});
+        } else {
+            return launch_tile16(int_c<4>{}, int_c<4>{}, int_c<16>{}, int_c<16>{});
         }
     }
     // larger `na`: shrink the tile before giving up on LDS
-    if ((size_t)na * 16 * cell <= lds_cap / 2) return launch_tile(std::integral_constant<int, 16>{});
-    if ((size_t)na * 8 * cell <= lds_cap / 2) return launch_tile(std::integral_constant<int, 8>{});
-    if ((size_t)na * 16 * cell <= lds_cap) return launch_tile(std::integral_constant<int, 16>{});
-    if ((size_t)na * 8 * cell <= lds_cap) return launch_tile(std::integral_constant<int, 8>{});
-    if ((size_t)na * 4 * cell <= lds_cap) return launch_tile(std::integral_constant<int, 4>{});
+    if ((size_t)na * 16 * cell <= lds_cap / 2) return launch_tile(int_c<16>{});
+    if ((size_t)na * 8 * cell <= lds_cap / 2) return launch_tile(int_c<8>{});
+    if ((size_t)na * 16 * cell <= lds_cap) return launch_tile(int_c<16>{});
+    if ((size_t)na * 8 * cell <= lds_cap) return launch_tile(int_c<8>{});
+    if ((size_t)na * 4 * cell <= lds_cap) return launch_tile(int_c<4>{});
     SSQ_CHECK_HIP(hipMemsetAsync(Tx, 0, (size_t)batch * na * n * cell, stream));
     dim3 grid((unsigned)((n + 255) / 256), (unsigned)batch);
     hipLaunchKernelGGL((accumulate_global_kernel<T, BINSRC, STFT, CST64>), grid, dim3(256), 0,
@@ -623,17 +529,16 @@ template <typename T, int BINSRC>
 static int launch_accumulate_b(const void* Wx, const void* src, const void* Sfs, void* Tx,
                                const void* cst, const SsqParams& sp, int64_t batch,
                                int64_t na, int64_t n, int32_t* kmap, hipStream_t stream) {
-    // (a float64 weight vector changes the product for float32 data only: float64 data multiplies in float64 anyway)
-    if constexpr (sizeof(T) == 4) {
-        if (sp.cst_f64) {
-            if constexpr (BINSRC == BIN_FROM_DWX)
-                if (Sfs) return launch_accumulate_t<T, BINSRC, true, true>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
-            return launch_accumulate_t<T, BINSRC, false, true>(Wx, src, nullptr, Tx, cst, sp, batch, na, n, kmap, stream);
-        }
-    }
-    if constexpr (BINSRC == BIN_FROM_DWX)
-        if (Sfs) return launch_accumulate_t<T, BINSRC, true, false>(Wx, src, Sfs, Tx, cst, sp, batch, na, n, kmap, stream);
-    return launch_accumulate_t<T, BINSRC, false, false>(Wx, src, nullptr, Tx, cst, sp, batch, na, n, kmap, stream);
+    return dispatch_bool(sp.cst_f64 != 0, [&](auto c) {
+        return dispatch_bool(Sfs != nullptr, [&](auto st) {
+            // (a float64 weight vector changes the product for float32 data only: float64 data multiplies in float64
+            // anyway; Sfs is read when the bins come from dWx only)
+            constexpr bool C64 = decltype(c)::value && sizeof(T) == 4;
+            constexpr bool STFT = decltype(st)::value && BINSRC == BIN_FROM_DWX;
+            return launch_accumulate_t<T, BINSRC, STFT, C64>(Wx, src, STFT ? Sfs : nullptr, Tx, cst, sp, batch, na, n, kmap,
+                                                             stream);
+        });
+    });
 }
 
 int launch_accumulate(int dtype, int binsrc, const void* Wx, const void* src, const void* Sfs,
@@ -662,6 +567,8 @@ __global__ __launch_bounds__(256) void ssqueeze_adjoint_kernel(
     const T* __restrict__ Wx, const T* __restrict__ dWx, const T* __restrict__ Sfs, const T* __restrict__ gTx,
     T* __restrict__ gWx, const void* __restrict__ cst, SsqParams sp, int64_t batch, int64_t na, int64_t n,
     int accumulate) {
+    using TM = Term<T, CST64>;
+    using w_t = typename TM::wtype;
     const int64_t total = batch * na * n, omax = na - 1;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = q / (na * n), i = (q - b * na * n) / n, j = q - (b * na + i) * n;
@@ -672,13 +579,8 @@ __global__ __launch_bounds__(256) void ssqueeze_adjoint_kernel(
         T gr = T(0), gi = T(0);
         if (k >= 0) {
             const T* g = gTx + 2 * ((b * na + k) * n + j);
-            if constexpr (CST64 && sizeof(T) == 4) {
-                const double w = ((const double*)cst)[i];
-                gr = (T)((double)g[0] * w); gi = (T)((double)g[1] * w);
-            } else {
-                const T w = ((const T*)cst)[i];
-                gr = g[0] * w; gi = g[1] * w;
-            }
+            const w_t w = ((const w_t*)cst)[i];
+            gr = (T)TM::make(g[0], w); gi = (T)TM::make(g[1], w);
         }
         if (accumulate) { gr = gWx[2 * q] + gr; gi = gWx[2 * q + 1] + gi; }
         gWx[2 * q] = gr; gWx[2 * q + 1] = gi;
@@ -714,9 +616,6 @@ __global__ __launch_bounds__(256) void phase_kernel(const T* __restrict__ Wx,
 // phase_ratio on the stored values -- for float32 data its float32 numerator and |Vg|^2, the reference's arithmetic --
 // so that chirp_tol = inf is phase_stft. Everything is computed and the thresholds select at the end: a point below
 // gamma may carry NaN on the way, never in the result.
-__device__ __forceinline__ double phase2_abs(double x, double y, float) { return sqrt(x * x + y * y); }   // (float32 data: the squares cannot leave float64's range)
-__device__ __forceinline__ double phase2_abs(double x, double y, double) { return hypot(x, y); }
-
 // Im(P / Q) by Smith's division
 __device__ __forceinline__ double smith_im(double pr, double pi, double qr, double qi) {
     const bool wide = fabs(qr) >= fabs(qi);
@@ -747,14 +646,7 @@ __device__ __forceinline__ T stft2_point(T g_re, T g_im, T d_re, T d_im, double 
     return (T)w;
 }
 
-// 16 bytes of a complex plane: two float32 points or one float64 point
-typedef float phase2_f4v __attribute__((ext_vector_type(4)));
-typedef float phase2_f2v __attribute__((ext_vector_type(2)));
-typedef double phase2_d2v __attribute__((ext_vector_type(2)));
-template <typename T> struct Phase2Vec;
-template <> struct Phase2Vec<float> { using load_t = phase2_f4v; using store_t = phase2_f2v; static constexpr int PTS = 2; };
-template <> struct Phase2Vec<double> { using load_t = phase2_d2v; using store_t = double; static constexpr int PTS = 1; };
-
+// (Phase2Vec, the 16 bytes of a complex plane, and phase2_abs: ssq_reassign_dev.h)
 // Streaming map over the flat (batch, rows, n) index; a thread takes PTS adjacent points per step -- one 16-byte load
 // per plane (VEC; the host checks the alignment) or one point with element loads. The row of a point, for Sfs, comes
 // from one 32-bit division per step; the second point of a pair may begin the next row.
@@ -909,27 +801,7 @@ __global__ __launch_bounds__(256) void buffer_kernel(const T* __restrict__ x, T*
 }
 
 // ---------------------------------------------------------------- padding
-__device__ __forceinline__ int64_t pad_source(int64_t t, int64_t n, int padtype) {
-    // t in [-n1, n + n2); returns source index in [0, n) or -1 for zero fill
-    if (t >= 0 && t < n) return t;
-    switch (padtype) {
-        case SSQ_PAD_REFLECT: {
-            if (n == 1) return 0;
-            int64_t period = 2 * (n - 1);
-            int64_t m = t % period; if (m < 0) m += period;
-            return m < n ? m : period - m;
-        }
-        case SSQ_PAD_SYMMETRIC: {
-            int64_t period = 2 * n;
-            int64_t m = t % period; if (m < 0) m += period;
-            return m < n ? m : period - 1 - m;
-        }
-        case SSQ_PAD_REPLICATE: return t < 0 ? 0 : n - 1;
-        case SSQ_PAD_WRAP: { int64_t m = t % n; if (m < 0) m += n; return m; }
-        default: return -1;
-    }
-}
-
+// (the extension rule, pad_source: ssq_common.h, with its transpose)
 template <typename T>
 __global__ __launch_bounds__(256) void pad_kernel(const T* __restrict__ x, T* __restrict__ out,
                                                   int64_t n, int64_t n1, int64_t m, int padtype,
@@ -940,12 +812,6 @@ __global__ __launch_bounds__(256) void pad_kernel(const T* __restrict__ x, T* __
         int64_t s = pad_source(p - n1, n, padtype);
         out[t] = s < 0 ? T(0) : x[b * n + s];
     }
-}
-
-static inline unsigned stream_grid(int64_t total, int block = 256) {
-    int64_t g = (total + block - 1) / block;
-    const int64_t cap = 256 * 8 * 4;   // 256 CUs x 8 blocks, grid-stride the rest
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 // Either second-order map: its kernel's 16-byte and element instances, its planes and its row table
@@ -961,9 +827,6 @@ static void launch_phase2(K vec_kernel, K element_kernel, const void* const (&pl
                        dim3(256), 0, stream, (const T*)planes[0], (const T*)planes[1], (const T*)planes[2],
                        (const T*)planes[3], (const T*)planes[4], tab, (T*)w, rows, n, total, gamma, chirp_tol);
 }
-
-#include "ssq_conceft.inl"
-#include "ssq_time_reassign.inl"
 
 }  // namespace ssq
 
@@ -1019,11 +882,6 @@ int ssq_stream_synchronize(void* stream) {
     return 0;
 }
 
-static int check_dtype(int dtype) {
-    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "dtype must be SSQ_F32 or SSQ_F64 (got %d)", dtype);
-    return 0;
-}
-
 int ssq_phase_cwt(int dtype, const void* Wx, const void* dWx, void* w, int64_t batch, int64_t na,
                   int64_t n, double gamma, void* stream) {
     if (check_dtype(dtype)) return -1;
@@ -1061,11 +919,7 @@ static int check_phase2(const char* entry, const void* const (&planes)[5], const
     SSQ_REQUIRE(batch >= 1 && rows >= min_rows && n >= 1, "%s: bad shape (%lld, %lld, %lld): rows >= %d, batch, n >= 1",
                 entry, (long long)batch, (long long)rows, (long long)n, min_rows);
     SSQ_REQUIRE(chirp_tol >= 0.0, "%s: chirp_tol must be >= 0 (got %g)", entry, chirp_tol);
-    // (32-bit point indices inside; five complex64 planes of 2^32 points would be 172 GB)
-    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
-                "%s: %lld x %lld x %lld points, at most 2^32 - 1", entry, (long long)batch, (long long)rows,
-                (long long)n);
-    return 0;
+    return check_point_count(entry, batch, rows, n);
 }
 
 int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg, const void* Vtg, const void* Vtdg,
@@ -1074,7 +928,7 @@ int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg
     if (check_dtype(dtype)) return -1;
     const void* const planes[5] = {Vg, Vdg, Vddg, Vtg, Vtdg};
     if (check_phase2("ssq_stft2_phase", planes, Sfs, w, batch, rows, 2, n, chirp_tol)) return -1;
-    SSQ_REQUIRE(gamma >= 0.0, "ssq_stft2_phase: gamma must be >= 0 (got %g)", gamma);
+    if (check_gamma("ssq_stft2_phase", gamma)) return -1;
     const int64_t total = batch * rows * n;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -1086,12 +940,8 @@ int ssq_stft2_phase(int dtype, const void* Vg, const void* Vdg, const void* Vddg
 }
 
 // The rows' r = scale / fs and 1 / r in float64, (na, 2), on the current device: checked on the host, uploaded once per
-// (device, fs, scales) and kept -- a call that finds its table enqueues the kernel and nothing else (no allocation, no
-// copy, nothing for the host to wait for), so it can be captured into a graph once its table exists. The eight most
-// recent tables stay; an older one is freed with hipFree, which waits for the kernels that may still read it.
-struct Cwt2Table { int dev; double fs; std::vector<double> scales; double* rtab; };
-static std::mutex g_cwt2_mutex;
-static std::vector<Cwt2Table> g_cwt2_tables;
+// (device, contents) and kept
+static DeviceTableCache g_cwt2_tables;
 
 static int cwt2_row_table(const double* scales, int64_t na, double fs, const double** out) {
     std::vector<double> rtab((size_t)na * 2);
@@ -1102,28 +952,7 @@ static int cwt2_row_table(const double* scales, int64_t na, double fs, const dou
                     (long long)i, scales[i]);
         rtab[2 * i] = r; rtab[2 * i + 1] = 1.0 / r;
     }
-    int dev = 0;
-    SSQ_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_cwt2_mutex);
-    for (size_t k = 0; k < g_cwt2_tables.size(); ++k) {
-        const Cwt2Table& t = g_cwt2_tables[k];
-        if (t.dev == dev && t.fs == fs && (int64_t)t.scales.size() == na &&
-            memcmp(t.scales.data(), scales, (size_t)na * sizeof(double)) == 0) {
-            *out = t.rtab;
-            return 0;
-        }
-    }
-    if (g_cwt2_tables.size() >= 8) {
-        (void)hipFree(g_cwt2_tables.front().rtab);
-        g_cwt2_tables.erase(g_cwt2_tables.begin());
-    }
-    double* d = nullptr;
-    SSQ_CHECK_HIP(hipMalloc((void**)&d, rtab.size() * sizeof(double)));
-    hipError_t e = hipMemcpy(d, rtab.data(), rtab.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); SSQ_CHECK_HIP(e); }
-    g_cwt2_tables.push_back(Cwt2Table{dev, fs, std::vector<double>(scales, scales + na), d});
-    *out = d;
-    return 0;
+    return g_cwt2_tables.get(rtab.data(), rtab.size(), out);
 }
 
 int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, const void* dWd, const void* dW3,
@@ -1143,16 +972,6 @@ int ssq_cwt2_phase(int dtype, const void* W, const void* dW, const void* Wd, con
         SSQ_LAUNCH_CHECK();
         return 0;
     });
-}
-
-static int fill_params(SsqParams& sp, int grid, const double* params, int flipud, double gamma, int cst_f64) {
-    SSQ_REQUIRE(grid >= SSQ_GRID_LOG && grid <= SSQ_GRID_LIN, "unknown grid kind %d", grid);
-    SSQ_REQUIRE(params, "grid params must not be null");
-    for (int t = 0; t < 5; ++t) sp.p[t] = params[t];
-    sp.grid = grid; sp.flipud = flipud ? 1 : 0; sp.gamma = gamma; sp.cst_f64 = cst_f64 ? 1 : 0;
-    sp.cst_uniform = 0;                   // weights are a device array here: not inspected
-    finalize_params(sp);
-    return 0;
 }
 
 int ssq_ssqueeze(int dtype, const void* Wx, const void* dWx, const void* Sfs, void* Tx,
@@ -1176,15 +995,18 @@ int ssq_ssqueeze_adjoint(int dtype, const void* Wx, const void* dWx, const void*
     if (fill_params(sp, grid, params, flipud, gamma, cst_f64)) return -1;
     const dim3 g(stream_grid(batch * na * n));
     hipStream_t s = as_stream(stream);
-#define SSQ_ADJ(T, STFT, C64) hipLaunchKernelGGL((ssqueeze_adjoint_kernel<T, STFT, C64>), g, dim3(256), 0, s, \
-        (const T*)Wx, (const T*)dWx, (const T*)Sfs, (const T*)gTx, (T*)gWx, cst, sp, batch, na, n, accumulate)
-    if (dtype == SSQ_F32) {
-        if (cst_f64) { if (Sfs) SSQ_ADJ(float, true, true); else SSQ_ADJ(float, false, true); }
-        else { if (Sfs) SSQ_ADJ(float, true, false); else SSQ_ADJ(float, false, false); }
-    } else { if (Sfs) SSQ_ADJ(double, true, false); else SSQ_ADJ(double, false, false); }
-#undef SSQ_ADJ
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dispatch_bool(cst_f64 != 0, [&](auto c) {
+            return dispatch_bool(Sfs != nullptr, [&](auto st) {
+                constexpr bool C64 = decltype(c)::value && sizeof(T) == 4;    // (as launch_accumulate_b)
+                hipLaunchKernelGGL((ssqueeze_adjoint_kernel<T, decltype(st)::value, C64>), g, dim3(256), 0, s, (const T*)Wx,
+                                   (const T*)dWx, (const T*)Sfs, (const T*)gTx, (T*)gWx, cst, sp, batch, na, n, accumulate);
+                SSQ_LAUNCH_CHECK();
+                return 0;
+            });
+        });
+    });
 }
 
 int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const void* cst, int cst_f64,
@@ -1195,88 +1017,6 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const vo
     SsqParams sp;
     if (fill_params(sp, grid, params, flipud, 0.0, cst_f64)) return -1;
     return launch_accumulate(dtype, BIN_FROM_W, Wx, w, nullptr, Tx, cst, sp, batch, na, n, nullptr, as_stream(stream));
-}
-
-// ssq_conceft and ssq_conceft_cwt: one set of checks, one launcher. `rowv` is Sfs (the planes' real dtype) for the STFT
-// form and the float64 weights cst for the CWT form; `name` opens every refusal's message.
-static int conceft_entry(bool cwt, const char* name, int dtype, const void* const* V, const void* const* dV,
-                         const void* rowv, const double* proj, void* Cx, int64_t batch, int64_t J, int64_t Q, int64_t rows,
-                         int64_t n, double gamma, int grid, const double* params, int flipud, int average, void* stream) {
-    if (check_dtype(dtype)) return -1;
-    SSQ_REQUIRE(J >= 1 && J <= 8, "%s: J = %lld, 1 .. 8 transforms", name, (long long)J);
-    SSQ_REQUIRE(Q >= 1 && Q <= 1024, "%s: Q = %lld, 1 .. 1024 projections", name, (long long)Q);
-    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "%s: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1", name,
-                (long long)batch, (long long)rows, (long long)n);
-    SSQ_REQUIRE(rows <= CONCEFT_MAX_ROWS, "%s: %lld rows, at most %lld (an 8-column float64 tile in 160 KiB of LDS)", name,
-                (long long)rows, (long long)CONCEFT_MAX_ROWS);
-    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
-                "%s: %lld x %lld x %lld points, at most 2^32 - 1", name, (long long)batch, (long long)rows, (long long)n);
-    SSQ_REQUIRE(V && dV && rowv && proj && Cx && params, "%s: null pointer", name);
-    ConceftPlanes P = {};
-    for (int64_t j = 0; j < J; ++j) {
-        SSQ_REQUIRE(V[j] && dV[j], "%s: plane %lld is a null pointer", name, (long long)j);
-        P.v[j] = V[j]; P.dv[j] = dV[j];
-    }
-    for (int64_t t = 0; t < 2 * Q * J; ++t)
-        SSQ_REQUIRE(proj[t] - proj[t] == 0.0, "%s: proj[%lld][%lld] is not finite", name, (long long)(t / (2 * J)),
-                    (long long)(t / 2 % J));
-    SSQ_REQUIRE(gamma >= 0.0, "%s: gamma must be >= 0 (got %g)", name, gamma);
-    SSQ_REQUIRE(grid >= SSQ_GRID_LOG && grid <= SSQ_GRID_LIN, "%s: unknown grid kind %d", name, grid);
-    SsqParams sp;
-    if (fill_params(sp, grid, params, flipud, gamma, cwt ? 1 : 0)) return -1;
-    const double* rdev = nullptr;
-    if (conceft_proj_table(proj, (size_t)(2 * Q * J), &rdev)) return -1;
-    return dispatch_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        hipStream_t s = as_stream(stream);
-        if (cwt) return average ? launch_conceft<T, true, true>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s)
-                                : launch_conceft<T, false, true>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s);
-        return average ? launch_conceft<T, true, false>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s)
-                       : launch_conceft<T, false, false>(P, rowv, rdev, Cx, sp, batch, J, Q, rows, n, s);
-    });
-}
-
-int ssq_conceft(int dtype, const void* const* V, const void* const* dV, const void* Sfs, const double* proj, void* Cx,
-                int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid, const double* params,
-                int flipud, int average, void* stream) {
-    return conceft_entry(false, "ssq_conceft", dtype, V, dV, Sfs, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
-                         flipud, average, stream);
-}
-
-int ssq_conceft_cwt(int dtype, const void* const* W, const void* const* dW, const void* cst, const double* proj, void* Cx,
-                    int64_t batch, int64_t J, int64_t Q, int64_t rows, int64_t n, double gamma, int grid,
-                    const double* params, int flipud, int average, void* stream) {
-    return conceft_entry(true, "ssq_conceft_cwt", dtype, W, dW, cst, proj, Cx, batch, J, Q, rows, n, gamma, grid, params,
-                         flipud, average, stream);
-}
-
-int ssq_time_reassign_segment(void) { return TSSQ_SEG; }
-int ssq_time_reassign_max_dmax(void) { return (int)TSSQ_MAX_DMAX; }
-
-int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* rot, void* Tx, int64_t batch, int64_t rows,
-                      int64_t n, int64_t n_fft, int64_t hop_len, double cols_per_second, int64_t dmax, double gamma,
-                      void* stream) {
-    if (check_dtype(dtype)) return -1;
-    SSQ_REQUIRE(Sx && Vtg && Tx, "ssq_time_reassign: null pointer");
-    SSQ_REQUIRE(batch >= 1 && rows >= 1 && n >= 1, "ssq_time_reassign: bad shape (%lld, %lld, %lld): batch, rows, n >= 1",
-                (long long)batch, (long long)rows, (long long)n);
-    SSQ_REQUIRE(rows <= (int64_t)0xFFFFFFFFll / n && batch <= (int64_t)0xFFFFFFFFll / (rows * n),
-                "ssq_time_reassign: %lld x %lld x %lld points, at most 2^32 - 1", (long long)batch, (long long)rows,
-                (long long)n);
-    SSQ_REQUIRE(n_fft >= 1 && n_fft <= (int64_t)0x7FFFFFFF && hop_len >= 1,
-                "ssq_time_reassign: n_fft = %lld, hop_len = %lld: n_fft 1 .. 2^31 - 1, hop_len >= 1", (long long)n_fft,
-                (long long)hop_len);
-    SSQ_REQUIRE(rows <= n_fft, "ssq_time_reassign: %lld rows of an n_fft of %lld", (long long)rows, (long long)n_fft);
-    SSQ_REQUIRE(dmax >= 0 && dmax <= TSSQ_MAX_DMAX, "ssq_time_reassign: dmax = %lld, 0 .. %lld", (long long)dmax,
-                (long long)TSSQ_MAX_DMAX);
-    SSQ_REQUIRE(cols_per_second > 0.0 && cols_per_second <= DBL_MAX,
-                "ssq_time_reassign: cols_per_second must be positive and finite (got %g)", cols_per_second);
-    SSQ_REQUIRE(gamma >= 0.0, "ssq_time_reassign: gamma must be >= 0 (got %g)", gamma);
-    return dispatch_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return launch_time_reassign<T>(Sx, Vtg, rot, Tx, batch, rows, n, n_fft, hop_len, cols_per_second, dmax, gamma,
-                                       as_stream(stream));
-    });
 }
 
 int ssq_replace_under_abs(int dtype, void* w, const void* ref, int64_t count, double value,
@@ -1329,3 +1069,12 @@ int ssq_pad_signal(int dtype, const void* x, void* out, int64_t batch, int64_t n
 }
 
 }  // extern "C"
+
+// hipcc (build.py) and the tests' CPU emulator (tests/emu/Makefile, which says SSQ_EMU_UNITS_SPLIT) compile
+// ssq_conceft.hip and ssq_time_reassign.hip as units of their own. Only an emulator build from a unit list older than
+// the split -- the tests directory of an earlier commit run against these sources -- lacks them and gets them here, so
+// that its library still has every entry.
+#if !defined(__HIPCC__) && !defined(SSQ_EMU_UNITS_SPLIT)
+#include "ssq_conceft.hip"
+#include "ssq_time_reassign.hip"
+#endif

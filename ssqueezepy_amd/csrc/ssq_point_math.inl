@@ -3,6 +3,7 @@
 // of which are compiled with -ffp-contract=off: the operations below are specified
 // one by one (oracle/ssq_oracle.c, "numba typing") so bin indices reproduce the CPU
 // path bit for bit.
+#pragma once
 // ------------------------------------------------------------ device math
 #define SSQ_TWO_PI 6.283185307179586
 

@@ -446,21 +446,18 @@ static int ridge_track_t(const T* E, T* pe, const TP* sc, double penalty, double
     const RidgeGeom g = ridge_geometry<T, TP>(na);
     SSQ_REQUIRE(g.lds <= 160 * 1024, "ssq_ridge_track: %lld rows do not fit the workgroup's LDS",
                 (long long)na);
-#define FW_LAUNCH(NT, F, CREG)                                                                     \
-    do {                                                                                           \
-        auto fw = ridge_fw_kernel<T, TP, NT, F, CREG>;                                             \
-        SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fw),                       \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds)); \
-        hipLaunchKernelGGL(fw, dim3((unsigned)batch), dim3(NT), g.lds, stream, E, pe, sc, (TP)penalty, (int)na, n, \
-                           g.nf, g.S, g.C, g.TT);                                                  \
-    } while (0)
+    auto fw_launch = [&](auto nt, auto f, auto creg) -> int {
+        constexpr int NT = decltype(nt)::value;
+        return launch_lds(ridge_fw_kernel<T, TP, NT, decltype(f)::value, decltype(creg)::value>, dim3((unsigned)batch),
+                          dim3(NT), g.lds, stream, E, pe, sc, (TP)penalty, (int)na, n, g.nf, g.S, g.C, g.TT);
+    };
     constexpr bool PF = sizeof(TP) == 4, TF = sizeof(T) == 4;   // register variants: see ridge_geometry
-    if (PF && g.creg == 16) FW_LAUNCH(512, 4, (PF ? 16 : 0));
-    else if (PF && TF && g.creg == 32) FW_LAUNCH(512, 4, (PF && TF ? 32 : 0));
-    else if (PF && TF && g.creg == 40) FW_LAUNCH(512, 5, (PF && TF ? 40 : 0));
-    else FW_LAUNCH(1024, 4, 0);
-#undef FW_LAUNCH
-    SSQ_LAUNCH_CHECK();
+    int st;
+    if (PF && g.creg == 16) st = fw_launch(int_c<512>{}, int_c<4>{}, int_c<(PF ? 16 : 0)>{});
+    else if (PF && TF && g.creg == 32) st = fw_launch(int_c<512>{}, int_c<4>{}, int_c<(PF && TF ? 32 : 0)>{});
+    else if (PF && TF && g.creg == 40) st = fw_launch(int_c<512>{}, int_c<5>{}, int_c<(PF && TF ? 40 : 0)>{});
+    else st = fw_launch(int_c<1024>{}, int_c<4>{}, int_c<0>{});
+    if (st) return st;
     hipLaunchKernelGGL((ridge_argmin_kernel<T>), dim3((unsigned)((n + 63) / 64), (unsigned)batch), dim3(64), 0, stream,
                        (const T*)pe, ridge, na, n);
     SSQ_LAUNCH_CHECK();
@@ -473,13 +470,8 @@ static int ridge_track_t(const T* E, T* pe, const TP* sc, double penalty, double
     }
     SSQ_REQUIRE(lds <= 160 * 1024, "ssq_ridge_track: %lld rows do not fit the workgroup's LDS",
                 (long long)na);
-    auto bwk = ridge_bw_kernel<T, TP>;
-    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bwk),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(bwk, dim3((unsigned)batch), dim3(RIDGE_BW_NT), lds, stream, E, (const T*)pe, sc, (TP)penalty, (T)eps,
-                       (int)na, n, ridge, TT);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(ridge_bw_kernel<T, TP>, dim3((unsigned)batch), dim3(RIDGE_BW_NT), lds, stream, E, (const T*)pe, sc,
+                      (TP)penalty, (T)eps, (int)na, n, ridge, TT);
 }
 
 }  // namespace ssq

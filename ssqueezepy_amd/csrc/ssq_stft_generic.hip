@@ -275,8 +275,6 @@ int launch_stft_generic(const StftFusedArgs& A, const SsqParams& sp, const c32* 
     B.F.xcd = nb >= 64;
     if (B.F.xcd) nb = (nb + 7u) & ~7u;
     const size_t lds = (size_t)2 * n * G * sizeof(c32);
-    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_generic_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, GEN_LDS_BYTES));
     // (the batch rides on grid.y: slices of at most 65535 signals)
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
         const int64_t nb_sig = std::min<int64_t>(65535, batch - b0);
@@ -287,8 +285,7 @@ int launch_stft_generic(const StftFusedArgs& A, const SsqParams& sp, const c32* 
         C.F.dSx = A.dSx ? A.dSx + pts : nullptr;
         C.F.kidx = A.kidx ? A.kidx + pts : nullptr;
         C.F.Tx = A.Tx ? A.Tx + pts : nullptr;
-        hipLaunchKernelGGL(stft_generic_kernel, dim3(nb, (unsigned)nb_sig), dim3(GEN_NT), lds, stream, C, sp);
-        SSQ_LAUNCH_CHECK();
+        if (int st = launch_lds(stft_generic_kernel, dim3(nb, (unsigned)nb_sig), dim3(GEN_NT), lds, stream, C, sp)) return st;
     }
     return 0;
 }

@@ -1,6 +1,7 @@
 // ssq_tile_dev.h -- device-side pieces shared by the three column-tile kernels of the fused ssq_cwt form
 // (ssq_tile_ordered.hip: the ticketed float32 tile; ssq_tile_f64.hip / ssq_tile_pair.hip: the float64 tile with
-// unordered adds, one / two columns per lane). Include inside namespace ssq, after ssq_point_math.inl.
+// unordered adds, one / two columns per lane). Include inside namespace ssq, after ssq_point_math.inl. The term of a
+// point and its fold into a cell (Term) come from ssq_reassign_dev.h.
 #pragma once
 
 constexpr int TILE_W = 8;         // taps
@@ -139,18 +140,3 @@ __device__ __forceinline__ void tile_count(unsigned long long* counters) {
     if (threadIdx.x == 0 && counters)
         __scoped_atomic_fetch_add(counters, 1ull, __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE);
 }
-
-// the additive term of one point and how it is folded into a cell, in the CPU path's arithmetic:
-// float32 data with a float64 weight vector accumulates through double (algos.py:66-79)
-template <bool CST64> struct TileTerm {
-    using type = float;
-    using wtype = float;
-    static __device__ __forceinline__ float make(float z, float w) { return z * w; }
-    static __device__ __forceinline__ float fold(float o, float t) { return o + t; }
-};
-template <> struct TileTerm<true> {
-    using type = double;
-    using wtype = double;
-    static __device__ __forceinline__ double make(float z, double w) { return (double)z * w; }
-    static __device__ __forceinline__ float fold(float o, double t) { return (float)((double)o + t); }
-};

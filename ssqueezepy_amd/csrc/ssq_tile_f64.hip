@@ -38,6 +38,7 @@
 // double sum's own rounding error is ~1e-16 relative: the float32 result differs between two
 // arrival orders only when the exact sum lies within that of a float32 rounding boundary.
 #include "ssq_common.h"
+#include "ssq_reassign_dev.h"
 #include "ssq_tiles.h"
 #include <algorithm>
 #include <cmath>
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(64 * NW) void tile2_kernel(TileWalkArgs A, SsqParam
     const float g2 = (float)(A.gamma * A.gamma);
     const float m2hi = g2 * 1.000004f, m2lo = g2 * 0.999996f;
     const int fx = sp.flipud ? -1 : 0, fa = sp.flipud ? na : 0;
-    using TM = TileTerm<CSTK == 2>;
+    using TM = Term<float, CSTK == 2>;
     using w_t = typename TM::wtype;
     const auto* cstv = SSQ_CONST_PTR(w_t, A.cst);
 

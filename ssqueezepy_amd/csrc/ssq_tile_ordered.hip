@@ -37,6 +37,7 @@
 // Compiled with -ffp-contract=off (bin indices); multiply-adds that may fuse are written as
 // explicit fmaf so every instantiation rounds identically.
 #include "ssq_common.h"
+#include "ssq_reassign_dev.h"
 #include "ssq_tiles.h"
 #include <algorithm>
 #include <cmath>
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(64 * NW) void tile_kernel(TileArgs A, SsqParams sp)
     const float g2 = (float)(A.gamma * A.gamma);
     const float m2hi = g2 * 1.000004f, m2lo = g2 * 0.999996f;
     const int fx = sp.flipud ? -1 : 0, fa = sp.flipud ? na : 0;
-    using TM = TileTerm<CSTK == 2>;
+    using TM = Term<float, CSTK == 2>;
     using term_t = typename TM::type;
     using w_t = typename TM::wtype;
     const w_t* cstv = (const w_t*)A.cst;

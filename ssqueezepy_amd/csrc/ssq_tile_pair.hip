@@ -30,6 +30,7 @@
 // the tiles start one column early (column -1 dead). Wx / Tx pairs and bin pairs are accessed as 16- / 4-byte words at
 // whatever 8- / 2-byte boundary the signal's length and that shift leave them. Compiled with -ffp-contract=off (bin indices); explicit fmaf where a multiply-add may fuse.
 #include "ssq_common.h"
+#include "ssq_reassign_dev.h"
 #include "ssq_tiles.h"
 #include <algorithm>
 #include <cmath>
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(64 * TILE3_NW) void tile3_kernel(TileWalkArgs A, Ss
     const float g2 = (float)(A.gamma * A.gamma);
     const float m2hi = g2 * 1.000004f, m2lo = g2 * 0.999996f;
     const int fx = sp.flipud ? -1 : 0, fa = sp.flipud ? na : 0;
-    using TM = TileTerm<CSTK == 2>;
+    using TM = Term<float, CSTK == 2>;
     using w_t = typename TM::wtype;
     const w_t* const cstv = reinterpret_cast<const w_t*>(A.cst);
 

@@ -191,16 +191,10 @@ int tile_dispatch(const SsqParams& sp, bool store_d, bool store_k, F&& f) {
     if (sp.grid == SSQ_GRID_LOG_PIECEWISE) return by_d(integral_constant<int, SSQ_GRID_LOG_PIECEWISE>{});
     return by_d(integral_constant<int, SSQ_GRID_LIN>{});
 }
-// grid workgroups of 64 nw work-items with `lds` bytes of dynamic LDS. Every tile kernel may take up to 160 KB: the
-// attribute is set at every launch (it belongs to the function ON THE CURRENT DEVICE, a flag per instantiation would
-// leave a second device of the process without it; the call costs well under a microsecond).
+// grid workgroups of 64 nw work-items with `lds` bytes of dynamic LDS (launch_lds: every tile kernel may take up to 160 KB)
 template <class Kern, class Args>
 int tile_launch(Kern kern, int64_t grid, int nw, size_t lds, const Args& A, const SsqParams& sp, hipStream_t stream) {
-    SSQ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * nw), lds, stream, A, sp);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(kern, dim3((unsigned)grid), dim3(64 * nw), lds, stream, A, sp);
 }
 
 }  // namespace ssq

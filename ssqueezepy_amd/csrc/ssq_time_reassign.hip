@@ -1,8 +1,8 @@
-// ssq_time_reassign.inl -- ssq_time_reassign: the time-reassigned synchrosqueezing transform (TSST; He, Cao, Zi, Zhou,
-// Chen 2019) -- every coefficient of a (batch, rows, n) plane moves along its row to its local group delay.
-// Included by ssq_kernels.hip inside `namespace ssq`, after the kernels whose ordered row-lane combine (FoldLower) and
-// 16-byte point types (Phase2Vec) it shares. include/ssq_hip.h states what is computed; DESIGN.md section 4.5.7 the
-// sizing.
+// ssq_time_reassign.hip -- ssq_time_reassign: the time-reassigned synchrosqueezing transform (TSST; He, Cao, Zi, Zhou,
+// Chen 2019) -- every coefficient of a (batch, rows, n) plane moves along its row to its local group delay. Kernel,
+// launcher and C-ABI entries. include/ssq_hip.h states what is computed; DESIGN.md section 4.5.7 the sizing. Compiled
+// with -ffp-contract=off, like ssq_kernels.hip, whose ordered row-lane combine and 16-byte point types it shares
+// (ssq_reassign_dev.h).
 //
 // A wavefront (a workgroup of 64) owns the destination cells [c0, c0 + TSSQ_SEG) of one row of one signal as an LDS
 // strip of float64 complex cells. It walks the sources [c0 - dmax, c0 + len + dmax) in ascending blocks of 64 -- lane =
@@ -17,6 +17,13 @@
 // Which lane's tag survives a clash does not matter: only "all found their own" is used. Nothing is shared between
 // wavefronts, so there are no atomics and the result does not depend on the grid; the strip leaves in full lines,
 // rounded once.
+#include "ssq_common.h"
+#include "ssq_reassign_dev.h"
+#include <cfloat>
+#include <type_traits>
+
+namespace ssq {
+
 constexpr int TSSQ_SEG = 960;                   // cells of a strip: 15 KiB of LDS + 960 tag bytes, ten strips per CU
 constexpr int64_t TSSQ_MAX_DMAX = 1 << 20;      // keeps a displacement and a wavefront's walk (SEG + 2 dmax) in 32 bits
 constexpr int64_t TSSQ_MAX_GRID = 1 << 24;      // workgroups of a launch; a workgroup takes units grid-stride
@@ -137,10 +144,43 @@ static int launch_time_reassign(const void* Sx, const void* Vtg, const void* rot
     const size_t lds = (size_t)(n < TSSQ_SEG ? n : TSSQ_SEG) * 17;          // a cell and its tag byte
     // one load per point needs every plane on a 16-byte boundary (a caller's offset pointer need not be)
     const bool vec = (uintptr_t)Sx % 16 == 0 && (uintptr_t)Vtg % 16 == 0 && (uintptr_t)Tx % 16 == 0;
-    hipLaunchKernelGGL((vec ? time_reassign_kernel<T, true> : time_reassign_kernel<T, false>),
-                       dim3((unsigned)(units < TSSQ_MAX_GRID ? units : TSSQ_MAX_GRID)), dim3(64), lds, stream,
-                       (const T*)Sx, (const T*)Vtg, (const double*)rot, (T*)Tx, units, (unsigned)rows, (unsigned)n,
-                       (unsigned)segs, (unsigned)n_fft, (unsigned)(hop_len % n_fft), cps, (int)dmax, gamma);
-    SSQ_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(vec ? time_reassign_kernel<T, true> : time_reassign_kernel<T, false>,
+                      dim3((unsigned)(units < TSSQ_MAX_GRID ? units : TSSQ_MAX_GRID)), dim3(64), lds, stream, (const T*)Sx,
+                      (const T*)Vtg, (const double*)rot, (T*)Tx, units, (unsigned)rows, (unsigned)n, (unsigned)segs,
+                      (unsigned)n_fft, (unsigned)(hop_len % n_fft), cps, (int)dmax, gamma);
 }
+
+}  // namespace ssq
+
+using namespace ssq;
+
+extern "C" {
+
+int ssq_time_reassign_segment(void) { return TSSQ_SEG; }
+int ssq_time_reassign_max_dmax(void) { return (int)TSSQ_MAX_DMAX; }
+
+int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* rot, void* Tx, int64_t batch, int64_t rows,
+                      int64_t n, int64_t n_fft, int64_t hop_len, double cols_per_second, int64_t dmax, double gamma,
+                      void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(Sx && Vtg && Tx, "ssq_time_reassign: null pointer");
+    SSQ_REQUIRE(batch >= 1 && rows >= 1 && n >= 1, "ssq_time_reassign: bad shape (%lld, %lld, %lld): batch, rows, n >= 1",
+                (long long)batch, (long long)rows, (long long)n);
+    if (check_point_count("ssq_time_reassign", batch, rows, n)) return -1;
+    SSQ_REQUIRE(n_fft >= 1 && n_fft <= (int64_t)0x7FFFFFFF && hop_len >= 1,
+                "ssq_time_reassign: n_fft = %lld, hop_len = %lld: n_fft 1 .. 2^31 - 1, hop_len >= 1", (long long)n_fft,
+                (long long)hop_len);
+    SSQ_REQUIRE(rows <= n_fft, "ssq_time_reassign: %lld rows of an n_fft of %lld", (long long)rows, (long long)n_fft);
+    SSQ_REQUIRE(dmax >= 0 && dmax <= TSSQ_MAX_DMAX, "ssq_time_reassign: dmax = %lld, 0 .. %lld", (long long)dmax,
+                (long long)TSSQ_MAX_DMAX);
+    SSQ_REQUIRE(cols_per_second > 0.0 && cols_per_second <= DBL_MAX,
+                "ssq_time_reassign: cols_per_second must be positive and finite (got %g)", cols_per_second);
+    if (check_gamma("ssq_time_reassign", gamma)) return -1;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_time_reassign<T>(Sx, Vtg, rot, Tx, batch, rows, n, n_fft, hop_len, cols_per_second, dmax, gamma,
+                                       as_stream(stream));
+    });
+}
+
+}  // extern "C"

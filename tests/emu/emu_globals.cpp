@@ -1,7 +1,7 @@
 // emu_globals.cpp -- state shared by the translation units of the emulated library (see
 // hip/hip_runtime.h): the per-OS-thread fiber scheduler and the dynamic-LDS buffers that the
-// `extern __shared__` arrays of csrc/ssq_kernels.hip and csrc/ssq_ridge.hip resolve to (one
-// workgroup at a time per OS thread). TEST INFRASTRUCTURE ONLY.
+// `extern __shared__` arrays of the Makefile's DYN_LDS units (csrc/ssq_kernels.hip, csrc/ssq_ridge.hip, ...) resolve to
+// (one workgroup at a time per OS thread). TEST INFRASTRUCTURE ONLY.
 #include "hip/hip_runtime.h"
 
 namespace emu {
