@@ -397,7 +397,12 @@ int ssq_ridge_neglog(int dtype, const void* energy, void* E, double eps, int64_t
  *   |pe[r, t+1] - E[r, t+1] - (pe[f, t] + P[r, f])| < eps, r = ridge[t+1], if any.
  * `sc` (na,): the (log) scales in the penalty dtype -- float32 when `penalty_f32`
  * (every input but complex128, :113-117), else float64; `pe` (na, n) and `ridge` (n,)
- * int64 are outputs. Bit-identical to the reference's loops for identical E. */
+ * int64 are outputs. Bit-identical to the reference's loops for identical E.
+ * Rows: one workgroup walks the time axis with a column of `pe` and of `E` in its 160 KiB
+ * of LDS, which holds at most 4549 rows of float32 data, 2408 rows of float64 data with
+ * float32 penalties, 2274 rows of float64 data with float64 penalties. One row more is
+ * refused (-1, "... rows do not fit the workgroup's LDS") before anything is launched:
+ * `pe` and `ridge` keep what they held. */
 int ssq_ridge_track(int dtype, int penalty_f32, const void* E, void* pe, const void* sc,
                     double penalty, double eps, int64_t na, int64_t n, int64_t* ridge,
                     void* stream);

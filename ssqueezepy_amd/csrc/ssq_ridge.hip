@@ -444,8 +444,17 @@ template <typename T, typename TP>
 static int ridge_track_t(const T* E, T* pe, const TP* sc, double penalty, double eps, int64_t na,
                          int64_t n, int64_t* ridge, int64_t batch, hipStream_t stream) {
     const RidgeGeom g = ridge_geometry<T, TP>(na);
-    SSQ_REQUIRE(g.lds <= 160 * 1024, "ssq_ridge_track: %lld rows do not fit the workgroup's LDS",
-                (long long)na);
+    // the backward pass's tile: sized here so that a row count either pass cannot hold is refused
+    // before anything is launched (the outputs of a refused call are untouched)
+    int TT = 32;
+    size_t lds;
+    for (;;) {
+        lds = (size_t)2 * na * (TT + 3) * sizeof(T) + (size_t)(na + 2) * sizeof(TP) + (size_t)TT * 4 + 64;
+        if (lds <= 150 * 1024 || TT == 1) break;
+        TT /= 2;
+    }
+    SSQ_REQUIRE(g.lds <= 160 * 1024 && lds <= 160 * 1024,
+                "ssq_ridge_track: %lld rows do not fit the workgroup's LDS", (long long)na);
     auto fw_launch = [&](auto nt, auto f, auto creg) -> int {
         constexpr int NT = decltype(nt)::value;
         return launch_lds(ridge_fw_kernel<T, TP, NT, decltype(f)::value, decltype(creg)::value>, dim3((unsigned)batch),
@@ -461,15 +470,6 @@ static int ridge_track_t(const T* E, T* pe, const TP* sc, double penalty, double
     hipLaunchKernelGGL((ridge_argmin_kernel<T>), dim3((unsigned)((n + 63) / 64), (unsigned)batch), dim3(64), 0, stream,
                        (const T*)pe, ridge, na, n);
     SSQ_LAUNCH_CHECK();
-    int TT = 32;
-    size_t lds;
-    for (;;) {
-        lds = (size_t)2 * na * (TT + 3) * sizeof(T) + (size_t)(na + 2) * sizeof(TP) + (size_t)TT * 4 + 64;
-        if (lds <= 150 * 1024 || TT == 1) break;
-        TT /= 2;
-    }
-    SSQ_REQUIRE(lds <= 160 * 1024, "ssq_ridge_track: %lld rows do not fit the workgroup's LDS",
-                (long long)na);
     return launch_lds(ridge_bw_kernel<T, TP>, dim3((unsigned)batch), dim3(RIDGE_BW_NT), lds, stream, E, (const T*)pe, sc,
                       (TP)penalty, (T)eps, (int)na, n, ridge, TT);
 }

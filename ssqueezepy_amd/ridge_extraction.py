@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, F32, F64
+from ._lib import check, SsqError, F32, F64
 from .algos import to_device, stream, _ptr
 from .configs import EPS32, EPS64
 
@@ -22,6 +22,8 @@ __all__ = ['extract_ridges']
 # transforms per launch: the batch entry points put the transform index on a grid dimension (blockIdx.y / x),
 # which holds at most 65535 workgroups; longer batches are walked in chunks of this size
 MAX_BATCH_PER_LAUNCH = 32768
+# rows of `ssq_ridge_track` (include/ssq_hip.h) by (float64 data, float64 penalties)
+MAX_ROWS = {(False, False): 4549, (True, False): 2408, (True, True): 2274}
 
 
 def extract_ridges(Tf, scales, penalty=2., n_ridges=1, bw=15, transform='cwt',
@@ -56,6 +58,10 @@ def extract_ridges(Tf, scales, penalty=2., n_ridges=1, bw=15, transform='cwt',
     if Tf.ndim not in (2, 3):
         raise ValueError("`Tf` must be 2D, (scales, timeshifts), or a batch of such, 3D (got shape %s)"
                          % (tuple(Tf.shape),))
+    # what ssq_ridge_track would answer, before anything is allocated (any type but these two is tracked as float64)
+    name = str(Tf.dtype).replace('torch.', '')
+    if Tf.shape[-2] > MAX_ROWS[(name not in ('complex64', 'float32'), name == 'complex128')]:
+        raise SsqError("libssq_hip: ssq_ridge_track: %d rows do not fit the workgroup's LDS (code -1)" % Tf.shape[-2])
     Tf = to_device(Tf)
     if Tf.dtype not in (torch.complex64, torch.complex128, torch.float32, torch.float64):
         Tf = Tf.to(torch.float64)
@@ -76,11 +82,11 @@ def extract_ridges(Tf, scales, penalty=2., n_ridges=1, bw=15, transform='cwt',
         return out if as_tensor else out.cpu().numpy().astype(int)
     if not batched:
         Tf = Tf[None]
-    Tf = Tf.contiguous()
     B, na, n = Tf.shape
-
     # ridge_extraction.py:113-121: float64 only for complex128 input
     c128 = Tf.dtype == torch.complex128
+    Tf = Tf.contiguous()
+
     pdt = np.float64 if c128 else np.float32
     eps = EPS64 if c128 else EPS32
     if isinstance(scales, torch.Tensor):

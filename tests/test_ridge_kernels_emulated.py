@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 import emu_backend
+import ridge_cases
 
 
 @pytest.fixture(scope='module')
@@ -103,6 +104,76 @@ def test_emulated_batch_entry_points(emu, cdtype, na, n):
         assert emu.ssq_ridge_clear(code, _p(e1), _p(r1), dbl(4), _p(re1), i64(na), i64(n), None) == 0
         assert np.array_equal(Eb[b], E1) and np.array_equal(peb[b], pe1) and np.array_equal(rb[b], r1)
         assert np.array_equal(enb[b], e1) and np.array_equal(reb[b], re1)
+
+
+class Emulated:
+    """The driver of tests/ridge_cases.py over host memory (the twin of test_gpu_ridge_shapes.Device)."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        lib.ssq_last_error.restype = ctypes.c_char_p
+
+    def last_error(self):
+        return (self.lib.ssq_last_error() or b'').decode()
+
+    def track(self, E, sc, penalty, eps, pe0=None, ridge0=None):
+        i64, dbl = ctypes.c_int64, ctypes.c_double
+        E, sc = np.ascontiguousarray(E), np.ascontiguousarray(sc)
+        pe = np.empty_like(E) if pe0 is None else pe0.copy()
+        ridge = np.empty(E.shape[:-2] + E.shape[-1:], np.int64) if ridge0 is None else ridge0.copy()
+        head = (int(E.dtype == np.float64), int(sc.dtype == np.float32), _p(E), _p(pe), _p(sc), dbl(float(penalty)),
+                dbl(float(eps)), i64(E.shape[-2]), i64(E.shape[-1]), _p(ridge))
+        rc_ = (self.lib.ssq_ridge_track(*head, None) if E.ndim == 2
+               else self.lib.ssq_ridge_track_batch(*head, i64(E.shape[0]), None))
+        return rc_, pe, ridge
+
+    def clear(self, en, ridge, bw, with_e):
+        i64 = ctypes.c_int64
+        en, ridge = en.copy(), np.ascontiguousarray(ridge)
+        r_e = np.full(ridge.shape, -1., en.dtype) if with_e else None
+        head = (int(en.dtype == np.float64), _p(en), _p(ridge), ctypes.c_double(float(bw)),
+                _p(r_e) if with_e else None, i64(en.shape[-2]), i64(en.shape[-1]))
+        rc_ = (self.lib.ssq_ridge_clear(*head, None) if en.ndim == 2
+               else self.lib.ssq_ridge_clear_batch(*head, i64(en.shape[0]), None))
+        return rc_, en, r_e
+
+
+@pytest.fixture(scope='module')
+def drv(emu):
+    return Emulated(emu)
+
+
+_TRACK = ridge_cases.tracking_cases(ridge_cases.SHAPES_EMULATED)
+
+
+@pytest.mark.parametrize('combo,shape,kind', _TRACK, ids=[ridge_cases.case_id(*c) for c in _TRACK])
+def test_emulated_tracking_by_row_count(drv, orc, combo, shape, kind):
+    """Ties, all-rows-tie, steps without a match and the random kind, one shape per forward variant and the last
+    row count that fits (the full list runs on the GPU: tests/test_gpu_ridge_shapes.py)."""
+    ridge_cases.check_tracking(drv, orc, kind, combo, shape)
+
+
+@pytest.mark.parametrize('combo', ridge_cases.COMBOS, ids=[ridge_cases.case_id(c) for c in ridge_cases.COMBOS])
+def test_emulated_refusal_leaves_the_outputs_alone(drv, combo):
+    ridge_cases.check_refusal(drv, combo)
+
+
+@pytest.mark.parametrize('combo', ridge_cases.COMBOS, ids=[ridge_cases.case_id(c) for c in ridge_cases.COMBOS])
+def test_emulated_tracking_batch(drv, orc, combo):
+    ridge_cases.check_tracking_batch(drv, orc, combo)
+
+
+@pytest.mark.parametrize('dtype', ['float32', 'float64'])
+def test_emulated_clear_follows_python_slices(drv, dtype):
+    ridge_cases.check_clear(drv, dtype)
+
+
+def test_emulated_extract_ridges_refuses_too_many_rows():
+    from ssqueezepy_amd._lib import SsqError
+    na = ridge_cases.MAX_ROWS[('float32', 'float32')] + 1
+    with emu_backend.emulated() as S:
+        with pytest.raises(SsqError, match="%d rows do not fit the workgroup's LDS" % na):
+            S.extract_ridges(np.ones((na, 3), dtype='complex64'), np.arange(1., na + 1))
 
 
 @pytest.mark.parametrize('as_numpy', [True, False])
