@@ -33,6 +33,7 @@ struct BlockPlan {
     int group = 1;                   // signals per launch (kernels take them as a grid dimension)
     int ncu = 256;                   // CUs of the plan's device (BlockPlan::create asks the runtime)
     int nc = 0;
+    DeviceArena mem;                 // every device pointer below
     std::vector<BlockClassDev> hcls;
     BlockClassDev* classes = nullptr;
     BlockRowDev* rows = nullptr;
@@ -64,14 +65,15 @@ struct BlockPlan {
     const int32_t* e_rows = nullptr;
     int setup_exact(const float* bank_dev, const int64_t* band_off_dev, const int32_t* band_lo_dev,
                     const int32_t* gen_rows_dev, const std::vector<int64_t>& h_off,
-                    const std::vector<int32_t>& h_lo, const std::vector<int32_t>& h_gen, int64_t& bytes);
+                    const std::vector<int32_t>& h_lo, const std::vector<int32_t>& h_gen);
     // exact rows of signals sig .. sig+nsig-1 (nsig <= group); xh_all: spectra of the whole batch
     int run_exact(int sig, int nsig, const void* xh_all, float* Wx, float* dWx, float* w, unsigned short* kidx,
                   const float* row_scale, double dt, const SsqParams& sp, hipStream_t stream);
 
     int create(const ssq_cwt_blocks_desc& d, int dtype, int64_t M, int64_t N, int64_t n1, int64_t na,
-               int64_t max_batch, int64_t& bytes);
+               int64_t max_batch);
     void destroy();
+    int64_t bytes() const;           // device memory of the tables, workspaces and transforms
     // block spectra of all classes for the padded batch xp (max_batch x M) and its half
     // spectrum xh (max_batch x (M / 2 + 1), what the analytic classes start from)
     // `need`: per class, 0 = skip (no row of the launch uses it), or nullptr for all

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -259,6 +260,46 @@ struct StreamScratch {
     ~StreamScratch() { for (void* p : held) (void)hipFreeAsync(p, stream); }
 };
 
+// The device allocations of one plan object (hipMalloc; StreamScratch above is the stream-ordered kind for one call's
+// temporaries): `alloc` / `upload` hand memory out -- 1 byte where 0 are asked for, so that every table has an
+// address --, `bytes` is what was asked for so far, `release` frees it all. A setup that must complete or leave the
+// plan as it found it notes `count()` first and, on failure, gives `release` that number: what came after it is freed.
+struct DeviceArena {
+    struct Held { void* p; size_t bytes; };
+    std::vector<Held> held;
+    DeviceArena() = default;
+    DeviceArena(const DeviceArena&) = delete;
+    DeviceArena& operator=(const DeviceArena&) = delete;
+    template <typename P>
+    int alloc(P** ptr, size_t bytes) {
+        void* p = nullptr;
+        *ptr = nullptr;
+        SSQ_CHECK_HIP(hipMalloc(&p, bytes ? bytes : 1));
+        held.push_back(Held{p, bytes});
+        *ptr = static_cast<P*>(p);
+        return 0;
+    }
+    template <typename P>
+    int upload(P** ptr, const void* host, size_t bytes) {
+        const int rc = alloc(ptr, bytes);
+        if (rc) return rc;
+        if (bytes) SSQ_CHECK_HIP(hipMemcpy(*ptr, host, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    size_t count() const { return held.size(); }
+    int64_t bytes() const {
+        int64_t total = 0;
+        for (const Held& h : held) total += (int64_t)h.bytes;
+        return total;
+    }
+    void release(size_t keep = 0) {
+        while (held.size() > keep) { (void)hipFree(held.back().p); held.pop_back(); }
+    }
+};
+
+// A plan under construction, from `new` to the line that hands it over (`release`): destroyed at every other return.
+template <typename P> using PlanGuard = std::unique_ptr<P, void (*)(P*)>;
+
 // A cached plan owns device workspaces that every execute reuses. Executes are asynchronous
 // and torch's side streams do not synchronise with each other, so two executes of one plan on
 // different streams (or from two host threads) would overwrite each other's workspace. `enter`
@@ -389,6 +430,26 @@ static inline int fill_params(SsqParams& sp, int grid, const double* params, int
     sp.cst_uniform = 0;                   // weights are a device array here: not inspected
     finalize_params(sp);
     return 0;
+}
+
+// ssq_cwt_plan_set_ssq / ssq_stft_plan_set_ssq: the parameters of a plan of `dtype` from the call's arguments, and a new
+// version of its `rows` per-row weights, which come from the host here (float64 where cst_f64 or the plan is float64;
+// a float64 plan's kernels read them as their own type, so cst_f64 is not set for one). Notes when the weights are one
+// scalar repeated, and the first of them. The caller holds the plan's PlanOrder::mu: kernels receive SsqParams by value
+// at launch, so an execute already enqueued keeps its own, and the lock orders this update against an execute that
+// another host thread is enqueuing.
+static inline int set_ssq_params(SsqParams& sp, WeightVersions& weights, void** cst_dev, float* cst0, int dtype,
+                                 int64_t rows, int grid, const double* params, const void* cst, int cst_f64, int flipud,
+                                 double gamma) {
+    const int rc = fill_params(sp, grid, params, flipud, gamma, cst_f64 && dtype == SSQ_F32);
+    if (rc) return rc;
+    const bool wide = cst_f64 || dtype == SSQ_F64;
+    bool uni = true;
+    for (int64_t i = 1; i < rows && uni; ++i)
+        uni = wide ? ((const double*)cst)[i] == ((const double*)cst)[0] : ((const float*)cst)[i] == ((const float*)cst)[0];
+    sp.cst_uniform = uni ? 1 : 0;
+    *cst0 = wide ? (float)((const double*)cst)[0] : ((const float*)cst)[0];
+    return weights.upload(cst_dev, cst, (size_t)rows * (wide ? 8 : 4));
 }
 
 // ---- launchers implemented in ssq_kernels.hip, used by the plans --------------

@@ -132,10 +132,52 @@ __global__ __launch_bounds__(256) void cwt_epilogue_kernel(const T* __restrict__
 
 using namespace ssq;
 
+// Optional per-stage HIP-event timing of an execute (ssq_cwt_plan_timing; bench.py --full reads it): 0 = pad + forward
+// FFT + block spectra + the tile path's decimated samples, 1 = block rows, 2 = exact / generic rows, 3 = reassignment.
+// Two events bracket the front of an execute, six belong to each launch group: the four boundaries of its stages 1 - 3
+// and the pair around its decimated samples.
+struct StageTimer {
+    enum Mark { ROWS = 0, OTHER_ROWS = 1, REASSIGN = 2, GROUP_END = 3, SAMPLES = 4, SAMPLES_END = 5 };
+    bool enabled = false;                 // what ssq_cwt_plan_timing asked for
+    bool on = false;                      // this execute is timed
+    std::vector<hipEvent_t> tev;
+    hipStream_t stream = nullptr;
+    double stage_ms[4] = {0, 0, 0, 0};
+    int64_t signals = 0;
+    int begin(int64_t groups, hipStream_t s) {
+        on = enabled; stream = s;
+        while (on && tev.size() < (size_t)(2 + 6 * groups)) {
+            hipEvent_t e; SSQ_CHECK_HIP(hipEventCreate(&e)); tev.push_back(e);
+        }
+        if (on) (void)hipEventRecord(tev[0], stream);
+        return 0;
+    }
+    void front_done() { if (on) (void)hipEventRecord(tev[1], stream); }
+    void mark(int64_t group, Mark m) { if (on) (void)hipEventRecord(tev[(size_t)(2 + 6 * group + m)], stream); }
+    // waits for the last group and adds the execute's stages up
+    int finish(int64_t groups, bool samples, int64_t batch) {
+        if (!on) return 0;
+        SSQ_CHECK_HIP(hipEventSynchronize(tev[(size_t)(2 + 6 * (groups - 1) + GROUP_END)]));
+        auto add = [&](int stage, size_t from, size_t to) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, tev[from], tev[to]); stage_ms[stage] += ms;
+        };
+        add(0, 0, 1);
+        for (int64_t g = 0; samples && g < groups; ++g) add(0, (size_t)(2 + 6 * g + SAMPLES), (size_t)(2 + 6 * g + SAMPLES_END));
+        for (int64_t g = 0; g < groups; ++g)
+            for (int st = 0; st < 3; ++st) add(1 + st, (size_t)(2 + 6 * g + st), (size_t)(2 + 6 * g + st + 1));
+        signals += batch;
+        return 0;
+    }
+    void reset(bool enable) { enabled = enable; for (double& v : stage_ms) v = 0; signals = 0; }
+    void destroy() { for (hipEvent_t e : tev) (void)hipEventDestroy(e); tev.clear(); }
+};
+
 struct ssq_cwt_plan {
     ssq_cwt_desc d;
     int csize() const { return d.dtype == SSQ_F32 ? 8 : 16; }
     int rsize() const { return d.dtype == SSQ_F32 ? 4 : 8; }
+    DeviceArena mem;                      // every device pointer below, the lazily made ones too
     // device copies
     void* bank = nullptr; int64_t* band_off = nullptr; int32_t* band_lo = nullptr;
     void* row_scale = nullptr;
@@ -144,7 +186,6 @@ struct ssq_cwt_plan {
     void* xp = nullptr; void* xh = nullptr; void* prod = nullptr; unsigned short* kidx = nullptr;
     int64_t rows_chunk = 0;
     size_t prod_bytes = 0;                // size of `prod` once it is allocated
-    int64_t bytes = 0;
     // signals per launch group: the fast-path kernels and the reassignment take `group`
     // signals as a grid dimension (fewer, longer launches; the bin map holds `group` maps)
     int group = 1;
@@ -170,23 +211,33 @@ struct ssq_cwt_plan {
     void* adj_spec = nullptr;
     int32_t* adj_off = nullptr; int32_t* adj_idx = nullptr; int32_t* adj_seg = nullptr;
     std::map<int64_t, FftPlan> adj_fwd;
-    // optional per-stage HIP-event timing (bench.py reads it): 0 = pad + forward FFT +
-    // block spectra, 1 = block rows, 2 = exact / generic rows, 3 = reassignment
-    bool timing = false;
-    std::vector<hipEvent_t> tev;          // 5 events per signal slot + 2 per execute
-    double stage_ms[4] = {0, 0, 0, 0};
-    int64_t timed_signals = 0;
+    StageTimer timer;
+    // device memory of the plan and of everything it owns (ssq_cwt_plan_bytes)
+    int64_t bytes() const {
+        int64_t b = mem.bytes() + (int64_t)fwd.work_bytes + (blk ? blk->bytes() : 0) + (tile ? tile->bytes() : 0);
+        for (auto& kv : inv) b += (int64_t)kv.second.work_bytes;
+        for (auto& kv : adj_fwd) b += (int64_t)kv.second.work_bytes;
+        return b;
+    }
 };
 
-static int h2d(void* dst, const void* src, size_t bytes) {
-    SSQ_CHECK_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return 0;
+static void destroy_blocks(BlockPlan* b) { b->destroy(); delete b; }
+static void destroy_tiles(TilePlan* t) { t->destroy(); delete t; }
+
+// the plan's transform of `count` rows in `plans`, made at its first use, over `data` in place
+static int cwt_cached_fft(ssq_cwt_plan* pl, std::map<int64_t, FftPlan>& plans, int kind, int64_t count, double scale,
+                          void* data, hipStream_t stream) {
+    auto it = plans.find(count);
+    if (it == plans.end()) {
+        FftPlan fp;
+        int rc = fp.create(kind, pl->d.dtype, (size_t)pl->d.m, (size_t)count, scale);
+        if (rc) { fp.destroy(); return rc; }
+        it = plans.emplace(count, fp).first;
+    }
+    return it->second.execute(data, nullptr, stream);
 }
-static int dev_alloc(void** p, size_t bytes, int64_t& acc) {
-    SSQ_CHECK_HIP(hipMalloc(p, bytes ? bytes : 1));
-    acc += (int64_t)bytes;
-    return 0;
-}
+// the product workspace of the generic route and of the adjoint, made by the first call that needs it
+static int cwt_product_workspace(ssq_cwt_plan* pl) { return pl->prod ? 0 : pl->mem.alloc(&pl->prod, pl->prod_bytes); }
 
 extern "C" {
 
@@ -208,7 +259,7 @@ int ssq_cwt_plan_create(ssq_cwt_plan** out, const ssq_cwt_desc* desc) {
                     "row %lld: band [%d, +%lld) outside [0, %lld)", (long long)i, d.band_lo[i],
                     (long long)len, (long long)d.m);
     }
-    auto* pl = new ssq_cwt_plan();
+    PlanGuard<ssq_cwt_plan> pl(new ssq_cwt_plan(), ssq_cwt_plan_destroy);
     pl->d = d;
     if (pl->d.max_batch < 1) pl->d.max_batch = 1;
     pl->h_band_off.assign(d.band_off, d.band_off + d.na + 1);
@@ -216,20 +267,14 @@ int ssq_cwt_plan_create(ssq_cwt_plan** out, const ssq_cwt_desc* desc) {
     pl->d.bank = nullptr; pl->d.band_off = nullptr; pl->d.band_lo = nullptr; pl->d.row_scale = nullptr;
     const int rs = pl->rsize(), cs = pl->csize();
     const int64_t nnz = d.band_off[d.na];
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) { ssq_cwt_plan_destroy(pl); return rc; } } while (0)
-    TRY(dev_alloc(&pl->bank, (size_t)nnz * rs, pl->bytes));
-    TRY(dev_alloc((void**)&pl->band_off, (size_t)(d.na + 1) * 8, pl->bytes));
-    TRY(dev_alloc((void**)&pl->band_lo, (size_t)d.na * 4, pl->bytes));
-    TRY(h2d(pl->bank, d.bank, (size_t)nnz * rs));
-    TRY(h2d(pl->band_off, d.band_off, (size_t)(d.na + 1) * 8));
-    TRY(h2d(pl->band_lo, d.band_lo, (size_t)d.na * 4));
-    if (d.row_scale) {
-        TRY(dev_alloc(&pl->row_scale, (size_t)d.na * rs, pl->bytes));
-        TRY(h2d(pl->row_scale, d.row_scale, (size_t)d.na * rs));
-    }
-    TRY(dev_alloc(&pl->xp, (size_t)pl->d.max_batch * d.m * rs, pl->bytes));
-    TRY(dev_alloc(&pl->xh, (size_t)pl->d.max_batch * (d.m / 2 + 1) * cs, pl->bytes));
+    DeviceArena& mem = pl->mem;
+    int rc;
+    if ((rc = mem.upload(&pl->bank, d.bank, (size_t)nnz * rs))) return rc;
+    if ((rc = mem.upload(&pl->band_off, d.band_off, (size_t)(d.na + 1) * 8))) return rc;
+    if ((rc = mem.upload(&pl->band_lo, d.band_lo, (size_t)d.na * 4))) return rc;
+    if (d.row_scale && (rc = mem.upload(&pl->row_scale, d.row_scale, (size_t)d.na * rs))) return rc;
+    if ((rc = mem.alloc(&pl->xp, (size_t)pl->d.max_batch * d.m * rs))) return rc;
+    if ((rc = mem.alloc(&pl->xh, (size_t)pl->d.max_batch * (d.m / 2 + 1) * cs))) return rc;
     // product workspace: 2 planes (Wx, dWx) per row, bounded to ~2 GiB
     const size_t per_row = (size_t)2 * d.m * cs;
     const size_t budget = (size_t)2 << 30;
@@ -243,20 +288,16 @@ int ssq_cwt_plan_create(ssq_cwt_plan** out, const ssq_cwt_desc* desc) {
         const int64_t g = std::min<int64_t>(16, std::max<int64_t>(1, ((int64_t)1 << 30) / (d.na * d.n)));
         pl->group = (int)std::max<int64_t>(1, std::min<int64_t>(g, pl->d.max_batch));
     }
-    TRY(dev_alloc((void**)&pl->kidx, ((size_t)pl->group * d.na * d.n + 64) * 2, pl->bytes));
+    if ((rc = mem.alloc(&pl->kidx, ((size_t)pl->group * d.na * d.n + 64) * 2))) return rc;
     {
         std::vector<int32_t> all((size_t)d.na);
         for (int64_t i = 0; i < d.na; ++i) all[i] = (int32_t)i;
-        TRY(dev_alloc((void**)&pl->gen_rows, (size_t)d.na * 4, pl->bytes));
-        TRY(dev_alloc((void**)&pl->all_rows, (size_t)d.na * 4, pl->bytes));
-        TRY(h2d(pl->gen_rows, all.data(), (size_t)d.na * 4));
-        TRY(h2d(pl->all_rows, all.data(), (size_t)d.na * 4));
+        if ((rc = mem.upload(&pl->gen_rows, all.data(), (size_t)d.na * 4))) return rc;
+        if ((rc = mem.upload(&pl->all_rows, all.data(), (size_t)d.na * 4))) return rc;
         pl->n_gen = d.na;
     }
-    TRY(pl->fwd.create(0, d.dtype, (size_t)d.m, (size_t)pl->d.max_batch, 1.0));
-    pl->bytes += (int64_t)pl->fwd.work_bytes;
-#undef TRY
-    *out = pl;
+    if ((rc = pl->fwd.create(0, d.dtype, (size_t)d.m, (size_t)pl->d.max_batch, 1.0))) return rc;
+    *out = pl.release();
     return 0;
 }
 
@@ -265,14 +306,12 @@ void ssq_cwt_plan_destroy(ssq_cwt_plan* pl) {
     pl->fwd.destroy();
     for (auto& kv : pl->inv) kv.second.destroy();
     for (auto& kv : pl->adj_fwd) kv.second.destroy();
-    if (pl->blk) { pl->blk->destroy(); delete pl->blk; }
-    if (pl->tile) { pl->tile->destroy(); delete pl->tile; }
-    for (hipEvent_t e : pl->tev) (void)hipEventDestroy(e);
+    if (pl->blk) destroy_blocks(pl->blk);
+    if (pl->tile) destroy_tiles(pl->tile);
+    pl->timer.destroy();
     pl->weights.destroy();
     pl->order.destroy();
-    void* ptrs[] = {pl->bank, pl->band_off, pl->band_lo, pl->row_scale, pl->xp, pl->xh, pl->prod,
-                    pl->kidx, pl->gen_rows, pl->all_rows, pl->adj_spec, pl->adj_off, pl->adj_idx, pl->adj_seg};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    pl->mem.release();
     delete pl;
 }
 
@@ -280,24 +319,9 @@ int ssq_cwt_plan_set_ssq(ssq_cwt_plan* pl, int grid, const double* params, const
                          int cst_f64, int flipud, double gamma) {
     SSQ_REQUIRE(pl && params && cst, "ssq_cwt_plan_set_ssq: null pointer");
     SSQ_REQUIRE(grid >= SSQ_GRID_LOG && grid <= SSQ_GRID_LIN, "unknown grid kind %d", grid);
-    // (kernels receive SsqParams by value at launch: an execute already enqueued keeps its own;
-    // the lock orders this update against an execute being enqueued by another host thread)
     std::lock_guard<std::mutex> lock(pl->order.mu);
-    for (int t = 0; t < 5; ++t) pl->sp.p[t] = params[t];
-    pl->sp.grid = grid; pl->sp.flipud = flipud ? 1 : 0; pl->sp.gamma = gamma;
-    pl->sp.cst_f64 = (cst_f64 && pl->d.dtype == SSQ_F32) ? 1 : 0;
-    {   // the weights come from the host here: note when they are one scalar repeated
-        const bool wide = cst_f64 || pl->d.dtype == SSQ_F64;
-        bool uni = true;
-        for (int64_t i = 1; i < pl->d.na && uni; ++i)
-            uni = wide ? ((const double*)cst)[i] == ((const double*)cst)[0]
-                       : ((const float*)cst)[i] == ((const float*)cst)[0];
-        pl->sp.cst_uniform = uni ? 1 : 0;
-    }
-    finalize_params(pl->sp);
-    size_t bytes = (size_t)pl->d.na * ((cst_f64 || pl->d.dtype == SSQ_F64) ? 8 : 4);
-    pl->cst0 = (cst_f64 || pl->d.dtype == SSQ_F64) ? (float)((const double*)cst)[0] : ((const float*)cst)[0];
-    int rc = pl->weights.upload(&pl->cst, cst, bytes);
+    int rc = set_ssq_params(pl->sp, pl->weights, &pl->cst, &pl->cst0, pl->d.dtype, pl->d.na, grid, params, cst, cst_f64,
+                            flipud, gamma);
     if (rc) return rc;
     pl->have_ssq = true;
     return 0;
@@ -313,21 +337,21 @@ int ssq_cwt_plan_set_blocks(ssq_cwt_plan* pl, const ssq_cwt_blocks_desc* bd) {
         int64_t P = bd->classes[5 * c];
         SSQ_REQUIRE(P >= 4096 && (P & (P - 1)) == 0 && P <= pl->d.m, "class %d: bad block length %lld", c, (long long)P);
     }
-    auto* b = new BlockPlan();
+    PlanGuard<BlockPlan> b(new BlockPlan(), destroy_blocks);
     b->group = pl->group;
-    int rc = b->create(*bd, pl->d.dtype, pl->d.m, pl->d.n, pl->d.n1, pl->d.na, pl->d.max_batch, pl->bytes);
-    if (rc) { b->destroy(); delete b; return rc; }
-    pl->blk = b;
-    pl->n_gen = bd->n_generic;
-    if (pl->n_gen)
-        SSQ_CHECK_HIP(hipMemcpy(pl->gen_rows, bd->generic_rows, (size_t)pl->n_gen * 4, hipMemcpyHostToDevice));
-    if (pl->n_gen && pl->d.dtype == SSQ_F32) {      // four-step exact kernels: float32 only
+    int rc = b->create(*bd, pl->d.dtype, pl->d.m, pl->d.n, pl->d.n1, pl->d.na, pl->d.max_batch);
+    if (rc) return rc;
+    if (bd->n_generic && pl->d.dtype == SSQ_F32) {      // four-step exact kernels: float32 only
         std::vector<int32_t> hg(bd->generic_rows, bd->generic_rows + bd->n_generic);
         rc = b->setup_exact((const float*)pl->bank, pl->band_off, pl->band_lo, pl->gen_rows,
-                            pl->h_band_off, pl->h_band_lo, hg, pl->bytes);
+                            pl->h_band_off, pl->h_band_lo, hg);
         if (rc) return rc;
     }
+    if (bd->n_generic)
+        SSQ_CHECK_HIP(hipMemcpy(pl->gen_rows, bd->generic_rows, (size_t)bd->n_generic * 4, hipMemcpyHostToDevice));
+    pl->n_gen = bd->n_generic;
     pl->algo = !pl->n_gen ? "blockzoom" : (b->exact_ok ? "blockzoom+fourstep" : "blockzoom+rocfft");
+    pl->blk = b.release();
     return 0;
 }
 
@@ -339,29 +363,25 @@ int ssq_cwt_plan_set_tiles(ssq_cwt_plan* pl, const ssq_cwt_tiles_desc* td) {
     for (int t = 0; t < 5; ++t)
         SSQ_REQUIRE(td->n_items_tile[t] >= 0 && td->n_items_tile[t] <= pl->blk->n_items[t],
                     "tile tables: bad block item count in slot %d", t);
-    auto* tp = new TilePlan();
-    int rc = tp->create(*td, pl->d.m, pl->d.n, pl->d.n1, pl->d.na, pl->group, pl->d.dt, pl->bytes);
-    if (rc) { tp->destroy(); delete tp; return rc; }
+    PlanGuard<TilePlan> tp(new TilePlan(), destroy_tiles);
+    int rc = tp->create(*td, pl->d.m, pl->d.n, pl->d.n1, pl->d.na, pl->group, pl->d.dt);
+    if (rc) return rc;
     tp->class_need.assign((size_t)pl->blk->nc, 0);
     for (int t = 0; t < 5; ++t)
         for (int64_t q = 0; q < td->n_items_tile[t]; ++q) {
             const int c = pl->blk->h_items[t][4 * q + 3];
             if (c >= 0 && c < pl->blk->nc) tp->class_need[(size_t)c] = 1;
         }
-    pl->tile = tp;
+    pl->tile = tp.release();
     pl->algo += "+tiles";
     return 0;
 }
 
 int ssq_cwt_plan_timing(ssq_cwt_plan* pl, int enable, double* stage_ms, int64_t* signals) {
     SSQ_REQUIRE(pl, "ssq_cwt_plan_timing: null plan");
-    if (stage_ms) for (int t = 0; t < 4; ++t) stage_ms[t] = pl->stage_ms[t];
-    if (signals) *signals = pl->timed_signals;
-    if (enable >= 0) {
-        pl->timing = enable != 0;
-        for (int t = 0; t < 4; ++t) pl->stage_ms[t] = 0;
-        pl->timed_signals = 0;
-    }
+    if (stage_ms) for (int t = 0; t < 4; ++t) stage_ms[t] = pl->timer.stage_ms[t];
+    if (signals) *signals = pl->timer.signals;
+    if (enable >= 0) pl->timer.reset(enable != 0);
     return 0;
 }
 
@@ -388,203 +408,187 @@ int ssq_cwt_plan_tile_counters(ssq_cwt_plan* pl, unsigned long long* out, int n,
     return 0;
 }
 int ssq_cwt_plan_tile_kernel(const ssq_cwt_plan* pl) { return (pl && pl->tile) ? pl->tile->tile_kernel() : 0; }
-int64_t ssq_cwt_plan_bytes(const ssq_cwt_plan* pl) { return pl ? pl->bytes : 0; }
+int64_t ssq_cwt_plan_bytes(const ssq_cwt_plan* pl) { return pl ? pl->bytes() : 0; }
 const char* ssq_cwt_plan_algo(const ssq_cwt_plan* pl) { return pl ? pl->algo.c_str() : ""; }
 
 }  // extern "C"
 
-template <typename T>
-static int cwt_execute_t(ssq_cwt_plan* pl, const void* x, int64_t batch, void* Wx, void* dWx,
-                         void* Tx, void* w, int rpadded, hipStream_t stream) {
+// ---- one execute: its arguments, what it decides before any row is routed, and its stages ---------------------------
+struct CwtCall {
+    ssq_cwt_plan* pl;
+    const void* x; int64_t batch;
+    void* Wx; void* dWx; void* Tx; void* w;
+    int rpadded;
+    hipStream_t stream;
+    bool use_blocks = false;      // the block (+ exact) kernels take the rows they can
+    bool use_tiles = false;       // fused ssq form on the column-tile path: block / exact kernels only for the rows the
+                                  // tile kernel reads back, no separate reassignment launch
+    bool side = false;            // ... with the decimated samples on the tile plan's side stream
+    int64_t n_gen = 0;            // rows of the exact / generic route
+    unsigned short* kidx = nullptr;   // the bin map, where the reassignment reads one
+    int64_t out_cols() const { return rpadded ? pl->d.m : pl->d.n; }
+    int nplanes() const { return (dWx || Tx || w) ? 2 : 1; }
+};
+
+// pad (or copy) the whole batch, forward FFT of all signals at once
+// (a smaller batch than planned runs the planned batch over the valid prefix; rows past `batch` hold stale but finite
+// data and are ignored)
+static int cwt_pad_fft(const CwtCall& c) {
+    ssq_cwt_plan* pl = c.pl;
     const ssq_cwt_desc& d = pl->d;
-    const int64_t M = d.m, N = d.n, na = d.na;
-    const int64_t out_cols = rpadded ? M : N;
-    const bool deriv = dWx || Tx || w;
-    const int nplanes = deriv ? 2 : 1;
+    if (d.padtype != SSQ_PAD_NONE) {
+        int rc = ssq_pad_signal(d.dtype, c.x, pl->xp, c.batch, d.n, d.n1, d.m - d.n - d.n1, d.padtype, c.stream);
+        if (rc) return rc;
+    } else
+        SSQ_CHECK_HIP(hipMemcpyAsync(pl->xp, c.x, (size_t)c.batch * d.m * pl->rsize(), hipMemcpyDeviceToDevice, c.stream));
+    return pl->fwd.execute(pl->xp, pl->xh, c.stream);
+}
+
+// Decimated samples of the interpolated rows of signals b0 .. b0 + ng - 1 (tile path). With the side stream: forked
+// from the execute's stream -- which also orders this group's samples behind the previous group's tile kernel -- and
+// left to be joined by cwt_reassign; when timing stage by stage they run in line.
+static int cwt_tile_samples(const CwtCall& c, int64_t b0, int ng) {
+    TilePlan* t = c.pl->tile;
+    hipStream_t ss = c.side ? t->side : c.stream;
+    if (c.side) {
+        SSQ_CHECK_HIP(hipEventRecord(t->ev_fork, c.stream));
+        SSQ_CHECK_HIP(hipStreamWaitEvent(ss, t->ev_fork, 0));
+    }
+    int rc = t->spectra((int)b0, ng, c.pl->xh, ss);
+    if (rc) return rc;
+    if (c.side) SSQ_CHECK_HIP(hipEventRecord(t->ev_join, ss));
+    return 0;
+}
+
+template <typename T>
+static int cwt_block_rows(const CwtCall& c, int64_t b0, int ng) {
+    ssq_cwt_plan* pl = c.pl;
+    if constexpr (sizeof(T) == 4)
+        return pl->blk->run((int)b0, ng, (float*)c.Wx, (float*)c.dWx, (float*)c.w, c.kidx, (const float*)pl->row_scale,
+                            pl->d.dt, pl->sp, c.stream, c.use_tiles ? pl->tile->n_items_tile : nullptr);
+    else
+        return pl->blk->run64((int)b0, ng, (double*)c.Wx, (double*)c.dWx, (double*)c.w, c.kidx,
+                              (const double*)pl->row_scale, pl->d.dt, pl->sp, c.stream);
+}
+
+// the rows whose band is cut by the Nyquist bin, four-step full-length FFT (float32), the whole group in one launch
+// (sub-groups of n signals, so that the four-step intermediate Z -- 4 MB per row and signal -- could stay
+// in the 256 MiB Infinity Cache between the two passes, were measured on the MI355X at config 2: 16 signals
+// at once 68.9 us per transform, 4: 76.2, 2: 73.7, 1: 85.3 -- the cache does not pay for the smaller launches)
+static int cwt_exact_rows(const CwtCall& c, int64_t b0, int ng) {
+    ssq_cwt_plan* pl = c.pl;
+    return pl->blk->run_exact((int)b0, ng, pl->xh, (float*)c.Wx, (float*)c.dWx, (float*)c.w, c.kidx,
+                              (const float*)pl->row_scale, pl->d.dt, pl->sp, c.stream);
+}
+
+// generic route, signal by signal in row chunks: banded product, rocFFT inverse (the plans cached by their transform
+// count), epilogue; the product workspace exists from the first execute that sends rows here
+template <typename T>
+static int cwt_generic_rows(const CwtCall& c, int64_t b0, int ng) {
+    ssq_cwt_plan* pl = c.pl;
+    const ssq_cwt_desc& d = pl->d;
+    const int64_t M = d.m, N = d.n, na = d.na, out_cols = c.out_cols(), n_gen = c.n_gen;
+    const int nplanes = c.nplanes();
     const double h = (2.0 * 3.141592653589793) / (double)M;
     const T inv_dt = T(1) / (T)d.dt;
-    if (pl->timing && pl->tev.size() < 2) {
-        for (int t = 0; t < 2; ++t) { hipEvent_t e; SSQ_CHECK_HIP(hipEventCreate(&e)); pl->tev.push_back(e); }
-    }
-    if (pl->timing) (void)hipEventRecord(pl->tev[0], stream);
-
-    // pad (or copy) the whole batch, forward FFT of all signals at once
-    const T* xsrc = (const T*)x;
-    if (d.padtype != SSQ_PAD_NONE) {
-        int rc = ssq_pad_signal(d.dtype, x, pl->xp, batch, N, d.n1, M - N - d.n1, d.padtype, stream);
-        if (rc) return rc;
-        xsrc = (const T*)pl->xp;
-    } else {
-        SSQ_CHECK_HIP(hipMemcpyAsync(pl->xp, x, (size_t)batch * M * sizeof(T), hipMemcpyDeviceToDevice, stream));
-        xsrc = (const T*)pl->xp;
-    }
-    if (batch == d.max_batch) {
-        int rc = pl->fwd.execute((void*)xsrc, pl->xh, stream);
-        if (rc) return rc;
-    } else {
-        // smaller batch than planned: run the planned batch over the (valid) prefix;
-        // rows past `batch` hold stale but finite data and are ignored
-        int rc = pl->fwd.execute((void*)xsrc, pl->xh, stream);
+    const int32_t* rowlist = pl->gen_rows_for(c.use_blocks);
+    if (n_gen > 0) {
+        int rc = cwt_product_workspace(pl);
         if (rc) return rc;
     }
-
-    pl->executed = true;
-    const bool tm = pl->timing;
-    if (tm && pl->tev.size() < (size_t)(2 + 6 * batch)) {
-        size_t need = (size_t)(2 + 6 * batch);
-        while (pl->tev.size() < need) {
-            hipEvent_t e; SSQ_CHECK_HIP(hipEventCreate(&e)); pl->tev.push_back(e);
-        }
-    }
-    auto mark = [&](size_t idx) { if (tm) (void)hipEventRecord(pl->tev[idx], stream); };
-    const bool use_blocks = pl->blk && !rpadded;
-    const int64_t n_gen = use_blocks ? pl->n_gen : na;
-    // fused ssq form on the column-tile path: block / exact kernels only for the rows the
-    // tile kernel reads back, no separate reassignment launch
-    // (a tile plan the selected kernel cannot run -- more rows than the ordered kernel's tile holds -- is decided
-    // HERE, before any row is routed: those calls take the block kernels + the separate reassignment)
-    const bool use_tiles = use_blocks && pl->tile && pl->tile->usable() && Tx && !w && sizeof(T) == 4;
-    // The first launch group's decimated samples need the spectra xh and nothing else: their kernels go to the side stream
-    // HERE, beside the analytic signal and the block spectra, not only beside the block rows (a short signal's ssq_cwt:
-    // their three launches are the longer branch).
-    const bool early = use_tiles && pl->tile->side && !tm;
-    if (early) {
-        SSQ_CHECK_HIP(hipEventRecord(pl->tile->ev_fork, stream));
-        SSQ_CHECK_HIP(hipStreamWaitEvent(pl->tile->side, pl->tile->ev_fork, 0));
-        int rc2 = pl->tile->spectra(0, (int)std::min<int64_t>(pl->group, batch), pl->xh, pl->tile->side);
-        if (rc2) return rc2;
-        SSQ_CHECK_HIP(hipEventRecord(pl->tile->ev_join, pl->tile->side));
-    }
-    if (use_blocks) {
-        int rc = pl->blk->spectra(pl->xp, pl->xh, batch, stream, use_tiles ? pl->tile->class_need.data() : nullptr);
-        if (rc) return rc;
-    }
-    mark(1);
-    int64_t slot = 0;                                   // timing slot = launch group
-    for (int64_t b0 = 0; b0 < batch; b0 += pl->group, ++slot) {
-        const int ng = (int)std::min<int64_t>(pl->group, batch - b0);
-        const bool fork = use_tiles && pl->tile->side && !tm;
-        if (use_tiles && !(early && b0 == 0)) {   // decimated samples of the interpolated rows: counted with stage 0
-            mark(2 + 4 * batch + 2 * slot);
-            // (beside the block / exact kernels when not timing stage by stage; the fork also
-            // orders this group's samples behind the previous group's tile kernel)
-            hipStream_t ss = fork ? pl->tile->side : stream;
-            if (fork) {
-                SSQ_CHECK_HIP(hipEventRecord(pl->tile->ev_fork, stream));
-                SSQ_CHECK_HIP(hipStreamWaitEvent(ss, pl->tile->ev_fork, 0));
-            }
-            int rc2 = pl->tile->spectra((int)b0, ng, pl->xh, ss);
-            if (rc2) return rc2;
-            if (fork) SSQ_CHECK_HIP(hipEventRecord(pl->tile->ev_join, ss));
-            mark(2 + 4 * batch + 2 * slot + 1);
-        }
-        mark(2 + 4 * slot);
-        unsigned short* kidx = (Tx && !w) ? pl->kidx : nullptr;
-        if (use_blocks) {
-            if constexpr (sizeof(T) == 4) {
-                int rc = pl->blk->run((int)b0, ng, (float*)Wx, (float*)dWx, (float*)w, kidx,
-                                      (const float*)pl->row_scale, d.dt, pl->sp, stream,
-                                      use_tiles ? pl->tile->n_items_tile : nullptr);
-                if (rc) return rc;
-            } else {
-                int rc = pl->blk->run64((int)b0, ng, (double*)Wx, (double*)dWx, (double*)w, kidx,
-                                        (const double*)pl->row_scale, d.dt, pl->sp, stream);
-                if (rc) return rc;
-            }
-        }
-        mark(2 + 4 * slot + 1);
-        if (use_blocks && pl->blk->exact_ok && n_gen > 0) {
-            if constexpr (sizeof(T) == 4) {
-                // (sub-groups of n signals, so that the four-step intermediate Z -- 4 MB per row and signal -- could stay
-                // in the 256 MiB Infinity Cache between the two passes, were measured on the MI355X at config 2: 16 signals
-                // at once 68.9 us per transform, 4: 76.2, 2: 73.7, 1: 85.3 -- the cache does not pay for the smaller launches)
-                const int eg = ng;
-                for (int s0 = 0; s0 < ng; s0 += eg) {
-                    const int ns = std::min(eg, ng - s0);
-                    int rc = pl->blk->run_exact((int)b0 + s0, ns, pl->xh, (float*)Wx, (float*)dWx, (float*)w,
-                                                kidx ? kidx + (size_t)s0 * na * N : nullptr,
-                                                (const float*)pl->row_scale, d.dt, pl->sp, stream);
-                    if (rc) return rc;
-                }
-            }
-        } else
-        for (int64_t b = b0; b < b0 + ng; ++b) {
+    for (int64_t b = b0; b < b0 + ng; ++b) {
         const T* xh = (const T*)pl->xh + (size_t)b * (M / 2 + 1) * 2;
-        T* Wx_b = Wx ? (T*)Wx + (size_t)b * na * out_cols * 2 : nullptr;
-        T* dWx_b = dWx ? (T*)dWx + (size_t)b * na * out_cols * 2 : nullptr;
-        T* w_b = w ? (T*)w + (size_t)b * na * out_cols : nullptr;
-        if (n_gen > 0 && !pl->prod) {
-            SSQ_CHECK_HIP(hipMalloc(&pl->prod, pl->prod_bytes ? pl->prod_bytes : 1));
-            pl->bytes += (int64_t)pl->prod_bytes;
-        }
         for (int64_t row0 = 0; row0 < n_gen; row0 += pl->rows_chunk) {
             const int64_t rows = std::min(pl->rows_chunk, n_gen - row0);
             unsigned gx = (unsigned)std::min<int64_t>((M + 255) / 256, 4096);
-            hipLaunchKernelGGL((bank_multiply_kernel<T>), dim3(gx, (unsigned)rows), dim3(256), 0, stream,
+            hipLaunchKernelGGL((bank_multiply_kernel<T>), dim3(gx, (unsigned)rows), dim3(256), 0, c.stream,
                                xh, (const T*)pl->bank, pl->band_off, pl->band_lo, (T*)pl->prod, M,
-                               pl->gen_rows_for(use_blocks), row0, nplanes, h, inv_dt);
+                               rowlist, row0, nplanes, h, inv_dt);
             SSQ_LAUNCH_CHECK();
-            const int64_t ntrans = rows * nplanes;
-            auto it = pl->inv.find(ntrans);
-            if (it == pl->inv.end()) {
-                FftPlan fp;
-                int rc = fp.create(1, d.dtype, (size_t)M, (size_t)ntrans, 1.0 / (double)M);
-                if (rc) return rc;
-                pl->bytes += (int64_t)fp.work_bytes;
-                it = pl->inv.emplace(ntrans, fp).first;
-            }
-            int rc = it->second.execute(pl->prod, nullptr, stream);
+            int rc = cwt_cached_fft(pl, pl->inv, 1, rows * nplanes, 1.0 / (double)M, pl->prod, c.stream);
             if (rc) return rc;
             EpilogueArgs ea;
-            ea.Wx = Wx_b; ea.dWx = dWx_b; ea.w = w_b;
-            ea.kidx = kidx ? kidx + (size_t)(b - b0) * na * N : nullptr;
-            ea.out_cols = out_cols; ea.col0 = rpadded ? 0 : d.n1; ea.row0 = row0;
-            ea.rowlist = pl->gen_rows_for(use_blocks);
+            ea.Wx = c.Wx ? (T*)c.Wx + (size_t)b * na * out_cols * 2 : nullptr;
+            ea.dWx = c.dWx ? (T*)c.dWx + (size_t)b * na * out_cols * 2 : nullptr;
+            ea.w = c.w ? (T*)c.w + (size_t)b * na * out_cols : nullptr;
+            ea.kidx = c.kidx ? c.kidx + (size_t)(b - b0) * na * N : nullptr;
+            ea.out_cols = out_cols; ea.col0 = c.rpadded ? 0 : d.n1; ea.row0 = row0;
+            ea.rowlist = rowlist;
             ea.row_scale = pl->row_scale; ea.gamma = pl->sp.gamma; ea.have_ssq = pl->have_ssq;
             unsigned ex = (unsigned)std::min<int64_t>((out_cols + 255) / 256, 4096);
-            hipLaunchKernelGGL((cwt_epilogue_kernel<T>), dim3(ex, (unsigned)rows), dim3(256), 0, stream,
+            hipLaunchKernelGGL((cwt_epilogue_kernel<T>), dim3(ex, (unsigned)rows), dim3(256), 0, c.stream,
                                (const T*)pl->prod, M, nplanes, na, ea, pl->sp);
             SSQ_LAUNCH_CHECK();
         }
-        }
-        mark(2 + 4 * slot + 2);
-        if (use_tiles) {
-            if (fork) SSQ_CHECK_HIP(hipStreamWaitEvent(stream, pl->tile->ev_join, 0));
-            int rc2 = pl->tile->run((int)b0, ng, (float*)Wx, (float*)dWx, (float*)Tx, pl->kidx, pl->cst, pl->cst0, pl->sp, stream,
-                                    pl->kdump);
-            if (rc2) return rc2;
-        } else if (Tx) {
-            // (diagnostic: the map the separate reassignment is about to consume)
-            if (pl->kdump && !w)
-                SSQ_CHECK_HIP(hipMemcpyAsync(pl->kdump + (size_t)b0 * na * N, pl->kidx, (size_t)ng * na * N * 2,
-                                             hipMemcpyDeviceToDevice, stream));
-            T* Wx_g = (T*)Wx + (size_t)b0 * na * out_cols * 2;
-            T* w_g = w ? (T*)w + (size_t)b0 * na * out_cols : nullptr;
-            T* Tx_g = (T*)Tx + (size_t)b0 * na * out_cols * 2;
-            int rc2 = launch_accumulate(d.dtype, w ? BIN_FROM_W : BIN_FROM_KIDX, Wx_g,
-                                        w ? (const void*)w_g : (const void*)pl->kidx, nullptr, Tx_g,
-                                        pl->cst, pl->sp, ng, na, N, nullptr, stream);
-            if (rc2) return rc2;
-        }
-        mark(2 + 4 * slot + 3);
-    }
-    const int64_t nslots = slot;
-    if (tm) {
-        SSQ_CHECK_HIP(hipEventSynchronize(pl->tev[2 + 4 * (nslots - 1) + 3]));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, pl->tev[0], pl->tev[1]); pl->stage_ms[0] += ms;
-        for (int64_t b = 0; use_tiles && b < nslots; ++b) {
-            (void)hipEventElapsedTime(&ms, pl->tev[2 + 4 * batch + 2 * b], pl->tev[2 + 4 * batch + 2 * b + 1]);
-            pl->stage_ms[0] += ms;
-        }
-        for (int64_t b = 0; b < nslots; ++b)
-            for (int st = 0; st < 3; ++st) {
-                (void)hipEventElapsedTime(&ms, pl->tev[2 + 4 * b + st], pl->tev[2 + 4 * b + st + 1]);
-                pl->stage_ms[1 + st] += ms;
-            }
-        pl->timed_signals += batch;
     }
     return 0;
+}
+
+// Tx of the group: the tile kernel (joins the side stream first; also writes Wx of the interpolated rows), or the
+// separate reassignment from the bin map / w
+template <typename T>
+static int cwt_reassign(const CwtCall& c, int64_t b0, int ng) {
+    ssq_cwt_plan* pl = c.pl;
+    const int64_t N = pl->d.n, na = pl->d.na, out_cols = c.out_cols();
+    if (c.use_tiles) {
+        if (c.side) SSQ_CHECK_HIP(hipStreamWaitEvent(c.stream, pl->tile->ev_join, 0));
+        return pl->tile->run((int)b0, ng, (float*)c.Wx, (float*)c.dWx, (float*)c.Tx, pl->kidx, pl->cst, pl->cst0, pl->sp,
+                             c.stream, pl->kdump);
+    }
+    if (!c.Tx) return 0;
+    // (diagnostic: the map the separate reassignment is about to consume)
+    if (pl->kdump && !c.w)
+        SSQ_CHECK_HIP(hipMemcpyAsync(pl->kdump + (size_t)b0 * na * N, pl->kidx, (size_t)ng * na * N * 2,
+                                     hipMemcpyDeviceToDevice, c.stream));
+    T* Wx_g = (T*)c.Wx + (size_t)b0 * na * out_cols * 2;
+    T* w_g = c.w ? (T*)c.w + (size_t)b0 * na * out_cols : nullptr;
+    T* Tx_g = (T*)c.Tx + (size_t)b0 * na * out_cols * 2;
+    return launch_accumulate(pl->d.dtype, c.w ? BIN_FROM_W : BIN_FROM_KIDX, Wx_g,
+                             c.w ? (const void*)w_g : (const void*)pl->kidx, nullptr, Tx_g,
+                             pl->cst, pl->sp, ng, na, N, nullptr, c.stream);
+}
+
+template <typename T>
+static int cwt_execute_t(CwtCall& c) {
+    ssq_cwt_plan* pl = c.pl;
+    StageTimer& tm = pl->timer;
+    const int64_t batch = c.batch;
+    int rc = tm.begin((batch + pl->group - 1) / pl->group, c.stream);
+    if (rc) return rc;
+    if ((rc = cwt_pad_fft(c))) return rc;
+    pl->executed = true;
+    c.use_blocks = pl->blk && !c.rpadded;
+    c.n_gen = c.use_blocks ? pl->n_gen : pl->d.na;
+    // (a tile plan the selected kernel cannot run -- more rows than the ordered kernel's tile holds -- is decided
+    // HERE, before any row is routed: those calls take the block kernels + the separate reassignment)
+    c.use_tiles = c.use_blocks && pl->tile && pl->tile->usable() && c.Tx && !c.w && sizeof(T) == 4;
+    c.side = c.use_tiles && pl->tile->side && !tm.on;
+    c.kidx = (c.Tx && !c.w) ? pl->kidx : nullptr;
+    // The first launch group's decimated samples need the spectra xh and nothing else: their kernels go to the side stream
+    // HERE, beside the analytic signal and the block spectra, not only beside the block rows (a short signal's ssq_cwt:
+    // their three launches are the longer branch).
+    if (c.side && (rc = cwt_tile_samples(c, 0, (int)std::min<int64_t>(pl->group, batch)))) return rc;
+    if (c.use_blocks && (rc = pl->blk->spectra(pl->xp, pl->xh, batch, c.stream, c.use_tiles ? pl->tile->class_need.data() : nullptr)))
+        return rc;
+    tm.front_done();
+    int64_t g = 0;                                      // launch group = timing slot
+    for (int64_t b0 = 0; b0 < batch; b0 += pl->group, ++g) {
+        const int ng = (int)std::min<int64_t>(pl->group, batch - b0);
+        if (c.use_tiles && !(c.side && b0 == 0)) {      // counted with stage 0
+            tm.mark(g, StageTimer::SAMPLES);
+            if ((rc = cwt_tile_samples(c, b0, ng))) return rc;
+            tm.mark(g, StageTimer::SAMPLES_END);
+        }
+        tm.mark(g, StageTimer::ROWS);
+        if (c.use_blocks && (rc = cwt_block_rows<T>(c, b0, ng))) return rc;
+        tm.mark(g, StageTimer::OTHER_ROWS);
+        const bool exact = c.use_blocks && pl->blk->exact_ok && c.n_gen > 0;      // (exact_ok: float32 plans only)
+        if ((rc = exact ? cwt_exact_rows(c, b0, ng) : cwt_generic_rows<T>(c, b0, ng))) return rc;
+        tm.mark(g, StageTimer::REASSIGN);
+        if ((rc = cwt_reassign<T>(c, b0, ng))) return rc;
+        tm.mark(g, StageTimer::GROUP_END);
+    }
+    return tm.finish(g, c.use_tiles, batch);
 }
 
 extern "C" {
@@ -604,9 +608,8 @@ int ssq_cwt_execute(ssq_cwt_plan* pl, const void* x, int64_t batch, void* Wx, vo
     // (replaying the launches of small transforms from a hipGraph was built in round 2 and
     // measured slower than the eager launches on ROCm 7.2 -- config 1: 0.298 vs 0.126 ms -- so it
     // is gone; what helps small transforms is fewer launches)
-    const int rc = dispatch_dtype(pl->d.dtype, [&](auto t) {
-        return cwt_execute_t<decltype(t)>(pl, x, batch, Wx, dWx, Tx, w, rpadded, st);
-    });
+    CwtCall c{pl, x, batch, Wx, dWx, Tx, w, rpadded, st};
+    const int rc = dispatch_dtype(pl->d.dtype, [&](auto t) { return cwt_execute_t<decltype(t)>(c); });
     pl->order.leave(st);
     return rc;
 }
@@ -742,27 +745,12 @@ static int cwt_adjoint_setup(ssq_cwt_plan* pl) {
             else { e[0] = std::min(e[0], (int32_t)a); e[1] = std::max(e[1], (int32_t)a + 1); }
         }
     }
-    int rc = dev_alloc((void**)&pl->adj_off, off.size() * 4, pl->bytes);
-    if (!rc) rc = dev_alloc((void**)&pl->adj_idx, idx.size() * 4, pl->bytes);
-    if (!rc) rc = dev_alloc((void**)&pl->adj_seg, seg.size() * 4, pl->bytes);
-    if (!rc) rc = h2d(pl->adj_off, off.data(), off.size() * 4);
-    if (!rc && !idx.empty()) rc = h2d(pl->adj_idx, idx.data(), idx.size() * 4);
-    if (!rc) rc = h2d(pl->adj_seg, seg.data(), seg.size() * 4);
-    if (!rc) rc = dev_alloc(&pl->adj_spec, (size_t)d.max_batch * d.m * pl->csize(), pl->bytes);
+    // (a failure part-way is undone by ssq_cwt_adjoint, with whatever else its first call allocated)
+    int rc = pl->mem.upload(&pl->adj_off, off.data(), off.size() * 4);
+    if (!rc) rc = pl->mem.upload(&pl->adj_idx, idx.data(), idx.size() * 4);
+    if (!rc) rc = pl->mem.upload(&pl->adj_seg, seg.data(), seg.size() * 4);
+    if (!rc) rc = pl->mem.alloc(&pl->adj_spec, (size_t)d.max_batch * d.m * pl->csize());
     return rc;
-}
-
-static int cwt_adjoint_fft(ssq_cwt_plan* pl, std::map<int64_t, FftPlan>& plans, int kind, int64_t count, double scale,
-                           void* data, hipStream_t stream) {
-    auto it = plans.find(count);
-    if (it == plans.end()) {
-        FftPlan fp;
-        int rc = fp.create(kind, pl->d.dtype, (size_t)pl->d.m, (size_t)count, scale);
-        if (rc) return rc;
-        pl->bytes += (int64_t)fp.work_bytes;
-        it = plans.emplace(count, fp).first;
-    }
-    return it->second.execute(data, nullptr, stream);
 }
 
 template <typename T, int V>
@@ -774,10 +762,8 @@ static int cwt_adjoint_t(ssq_cwt_plan* pl, const void* gWx, const void* gdWx, vo
     const int nplanes = (gWx ? 1 : 0) + (gdWx ? 1 : 0);
     const double h = (2.0 * 3.141592653589793) / (double)M;
     const T inv_dt = T(1) / (T)d.dt;
-    if (!pl->prod) {
-        SSQ_CHECK_HIP(hipMalloc(&pl->prod, pl->prod_bytes ? pl->prod_bytes : 1));
-        pl->bytes += (int64_t)pl->prod_bytes;
-    }
+    int rc = cwt_product_workspace(pl);
+    if (rc) return rc;
     T* ws = (T*)pl->prod;
     // rows per pass: the forward's chunk, cut to ADJ_PASS_BYTES of rows (two planes each) -- rocFFT's own work area
     // is as large as what it transforms in one call, and a pass of this size is still in the Infinity Cache when the
@@ -799,7 +785,7 @@ static int cwt_adjoint_t(ssq_cwt_plan* pl, const void* gWx, const void* gdWx, vo
             hipLaunchKernelGGL((cwt_adjoint_stage_kernel<T, V>), dim3(sx, (unsigned)rows, (unsigned)nplanes), dim3(256), 0,
                                stream, g0, g1, ws, M, cols, col0, row0, nplanes);
             SSQ_LAUNCH_CHECK();
-            int rc = cwt_adjoint_fft(pl, pl->adj_fwd, 2, rows * nplanes, 1.0, ws, stream);
+            rc = cwt_cached_fft(pl, pl->adj_fwd, 2, rows * nplanes, 1.0, ws, stream);
             if (rc) return rc;
 #define SSQ_MAC(F, G) hipLaunchKernelGGL((cwt_adjoint_mac_kernel<T, V, F, G>), dim3(mx), dim3(256), 0, stream,           \
                                          (const T*)ws, (const T*)pl->bank, pl->band_off, pl->band_lo,                      \
@@ -811,7 +797,7 @@ static int cwt_adjoint_t(ssq_cwt_plan* pl, const void* gWx, const void* gdWx, vo
             SSQ_LAUNCH_CHECK();
         }
     }
-    int rc = cwt_adjoint_fft(pl, pl->inv, 1, batch, 1.0 / (double)M, pl->adj_spec, stream);
+    rc = cwt_cached_fft(pl, pl->inv, 1, batch, 1.0 / (double)M, pl->adj_spec, stream);
     if (rc) return rc;
     hipLaunchKernelGGL((cwt_adjoint_unpad_kernel<T>), dim3((unsigned)((N + 255) / 256), (unsigned)batch), dim3(256), 0,
                        stream, (const T*)pl->adj_spec, (T*)gx, (const int32_t*)pl->adj_off, (const int32_t*)pl->adj_idx,
@@ -829,11 +815,18 @@ extern "C" int ssq_cwt_adjoint(ssq_cwt_plan* pl, const void* gWx, const void* gd
     SSQ_REQUIRE(batch <= 65535, "ssq_cwt_adjoint: batch %lld > 65535", (long long)batch);
     hipStream_t st = as_stream(stream);
     pl->order.enter(st);
+    const bool first = !pl->adj_spec, had_prod = pl->prod != nullptr;
+    const size_t before = pl->mem.count();
     int rc = cwt_adjoint_setup(pl);
     if (!rc) {
         if (pl->d.dtype == SSQ_F64) rc = cwt_adjoint_t<double, 1>(pl, gWx, gdWx, gx, batch, rpadded, st);
         else if (pl->d.m % 2 == 0) rc = cwt_adjoint_t<float, 2>(pl, gWx, gdWx, gx, batch, rpadded, st);
         else rc = cwt_adjoint_t<float, 1>(pl, gWx, gdWx, gx, batch, rpadded, st);
+    }
+    if (rc && first) {       // a first call that fails leaves the plan as it found it: the next one starts over
+        pl->mem.release(before);
+        pl->adj_off = pl->adj_idx = pl->adj_seg = nullptr; pl->adj_spec = nullptr;
+        if (!had_prod) pl->prod = nullptr;
     }
     pl->order.leave(st);
     return rc;

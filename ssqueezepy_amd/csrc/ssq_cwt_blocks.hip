@@ -982,7 +982,7 @@ static int launch_zoom(const BlockArgs& A, const SsqParams& sp, int nsig, hipStr
 }
 
 int BlockPlan::create(const ssq_cwt_blocks_desc& d, int dtype_, int64_t M_, int64_t N_, int64_t n1_,
-                      int64_t na_, int64_t max_batch_, int64_t& bytes) {
+                      int64_t na_, int64_t max_batch_) {
     M = M_; N = N_; n1 = n1_; na = na_; max_batch = max_batch_; dtype = dtype_;
     const size_t rs = dtype == SSQ_F32 ? 4 : 8;
     nc = d.n_classes;
@@ -1002,28 +1002,22 @@ int BlockPlan::create(const ssq_cwt_blocks_desc& d, int dtype_, int64_t M_, int6
         if (!k.analytic) blk_max += max_batch * k.nb * k.P;
         n_analytic += (int)k.analytic;
     }
-    auto up = [&](void** dst, const void* src, size_t nbytes) -> int {
-        SSQ_CHECK_HIP(hipMalloc(dst, nbytes ? nbytes : 1));
-        if (nbytes) SSQ_CHECK_HIP(hipMemcpy(*dst, src, nbytes, hipMemcpyHostToDevice));
-        bytes += (int64_t)nbytes;
-        return 0;
-    };
     int rc;
-    if ((rc = up((void**)&classes, hcls.data(), sizeof(BlockClassDev) * nc))) return rc;
+    if ((rc = mem.upload(&classes, hcls.data(), sizeof(BlockClassDev) * nc))) return rc;
     static_assert(sizeof(BlockRowDev) == 6 * sizeof(int32_t), "row table layout");
-    if ((rc = up((void**)&rows, d.rows, sizeof(BlockRowDev) * na))) return rc;
-    if ((rc = up((void**)&pbank, d.pbank, rs * d.n_pbank))) return rc;
-    if ((rc = up((void**)&pxi, d.pxi, rs * d.n_pbank))) return rc;
-    if ((rc = up((void**)&ctw, d.ctw, 2 * rs * (size_t)d.ctw_off[nc]))) return rc;
-    if ((rc = up((void**)&ftw, d.ftw, 2 * rs * (size_t)d.n_ftw))) return rc;
+    if ((rc = mem.upload(&rows, d.rows, sizeof(BlockRowDev) * na))) return rc;
+    if ((rc = mem.upload(&pbank, d.pbank, rs * d.n_pbank))) return rc;
+    if ((rc = mem.upload(&pxi, d.pxi, rs * d.n_pbank))) return rc;
+    if ((rc = mem.upload(&ctw, d.ctw, 2 * rs * (size_t)d.ctw_off[nc]))) return rc;
+    if ((rc = mem.upload(&ftw, d.ftw, 2 * rs * (size_t)d.n_ftw))) return rc;
     for (int s = 0; s < 5; ++s) {
         n_items[s] = d.n_items[s];
         ftw_off[s] = d.ftw_off[s];
-        if ((rc = up((void**)&items[s], d.items[s], sizeof(int4) * (size_t)d.n_items[s]))) return rc;
+        if ((rc = mem.upload(&items[s], d.items[s], sizeof(int4) * (size_t)d.n_items[s]))) return rc;
         if (d.n_items[s]) h_items[s].assign(d.items[s], d.items[s] + 4 * d.n_items[s]);
     }
-    SSQ_CHECK_HIP(hipMalloc((void**)&xb, 2 * rs * (size_t)xb_total)); bytes += 2 * rs * xb_total;
-    SSQ_CHECK_HIP(hipMalloc((void**)&blocks, rs * (size_t)blk_max)); bytes += rs * blk_max;
+    if ((rc = mem.alloc(&xb, 2 * rs * (size_t)xb_total))) return rc;
+    if ((rc = mem.alloc(&blocks, rs * (size_t)blk_max))) return rc;
     // classes of equal block length and kind are contiguous in `blocks` and `xb`: one batched
     // real-to-complex transform per length (complex, in place in `xb`, for the analytic classes)
     for (int c = 0; c < nc;) {
@@ -1033,20 +1027,18 @@ int BlockPlan::create(const ssq_cwt_blocks_desc& d, int dtype_, int64_t M_, int6
             nblocks += max_batch * hcls[e++].nb;
         FftPlan fp;
         rc = fp.create(hcls[c].analytic ? 2 : 0, dtype, (size_t)hcls[c].P, (size_t)nblocks, 1.0);
-        if (rc) return rc;
-        bytes += (int64_t)fp.work_bytes;
+        if (rc) { fp.destroy(); return rc; }
         ffts.push_back(fp); fft_first.push_back(c);
         c = e;
     }
     if (n_analytic) {
-        SSQ_CHECK_HIP(hipMalloc(&xa, 2 * rs * (size_t)(max_batch * M))); bytes += 2 * rs * max_batch * M;
+        if ((rc = mem.alloc(&xa, 2 * rs * (size_t)(max_batch * M)))) return rc;
         if (AnalyticFft::supports(dtype, M)) {
             ana = new AnalyticFft();
-            if ((rc = ana->create(M, max_batch, bytes))) return rc;
+            if ((rc = ana->create(M, max_batch))) return rc;
         } else {
             rc = inv_m.create(1, dtype, (size_t)M, (size_t)max_batch, 1.0 / (double)M);
             if (rc) return rc;
-            bytes += (int64_t)inv_m.work_bytes;
         }
     }
     n_generic = d.n_generic;
@@ -1070,9 +1062,13 @@ void BlockPlan::destroy() {
     for (auto& f : ffts) f.destroy();
     inv_m.destroy();
     if (ana) { ana->destroy(); delete ana; ana = nullptr; }
-    void* ptrs[] = {xa, twM, zbuf, classes, rows, pbank, pxi, ctw, ftw, xb, blocks, items[0], items[1], items[2],
-                    items[3], items[4]};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    mem.release();
+}
+
+int64_t BlockPlan::bytes() const {
+    int64_t b = mem.bytes() + (int64_t)inv_m.work_bytes + (ana ? ana->mem.bytes() : 0);
+    for (const FftPlan& f : ffts) b += (int64_t)f.work_bytes;
+    return b;
 }
 
 int BlockPlan::spectra(const void* xp, const void* xh, int64_t batch, hipStream_t stream,
@@ -1258,8 +1254,7 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
 // ---- exact rows: host side
 int BlockPlan::setup_exact(const float* bank_dev, const int64_t* band_off_dev, const int32_t* band_lo_dev,
                            const int32_t* gen_rows_dev, const std::vector<int64_t>& h_off,
-                           const std::vector<int32_t>& h_lo, const std::vector<int32_t>& h_gen,
-                           int64_t& bytes) {
+                           const std::vector<int32_t>& h_lo, const std::vector<int32_t>& h_gen) {
     exact_ok = false;
     if (h_gen.empty()) return 0;
     const int lm = fft_slot(M, 1);                  // (log2 M when M is a power of two)
@@ -1276,9 +1271,9 @@ int BlockPlan::setup_exact(const float* bank_dev, const int64_t* band_off_dev, c
         double ang = 2.0 * 3.14159265358979323846 * (double)q / (double)M;
         tw[2 * q] = (float)(cos(ang) / (double)M); tw[2 * q + 1] = (float)(sin(ang) / (double)M);
     }
-    SSQ_CHECK_HIP(hipMalloc(&twM, 8 * (size_t)M)); bytes += 8 * M;
-    SSQ_CHECK_HIP(hipMemcpy(twM, tw.data(), 8 * (size_t)M, hipMemcpyHostToDevice));
-    SSQ_CHECK_HIP(hipMalloc(&zbuf, (size_t)group * n_exact * 2 * M * 8)); bytes += (int64_t)group * n_exact * 2 * M * 8;
+    int rc;
+    if ((rc = mem.upload(&twM, tw.data(), 8 * (size_t)M))) return rc;
+    if ((rc = mem.alloc(&zbuf, (size_t)group * n_exact * 2 * M * 8))) return rc;
     exact_ok = true;
     return 0;
 }

@@ -191,7 +191,7 @@ static bool deal_item_lists(const ItemTable& t, int nw, float rb_cost, float chg
 }
 
 int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_t n1_, int64_t na_, int group_,
-                     double dt_, int64_t& bytes) {
+                     double dt_) {
     M = M_; N = N_; n1 = n1_; na = na_; group = group_; dt = dt_;
     nsegs = d.n_segs; nsteps = d.n_steps; n_irows = d.n_irows; u_total = d.u_total;
     SSQ_REQUIRE(nsegs >= 1 && nsteps >= 1 && n_irows >= 1 && d.n_classes >= 1, "empty tile tables");
@@ -215,12 +215,6 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
     // (and the centre bin, < M / 2, shares a word with the row: 22 bits)
     SSQ_REQUIRE(M <= ((int64_t)1 << 23), "the tile path needs a padded length <= 2^23");
     SSQ_REQUIRE((int64_t)group * u_total < ((int64_t)1 << 31), "tile intermediates exceed 2^31 entries");
-    auto up = [&](void** dst, const void* src, size_t nbytes) -> int {
-        SSQ_CHECK_HIP(hipMalloc(dst, nbytes ? nbytes : 1));
-        if (nbytes) SSQ_CHECK_HIP(hipMemcpy(*dst, src, nbytes, hipMemcpyHostToDevice));
-        bytes += (int64_t)nbytes;
-        return 0;
-    };
     int rc;
     static_assert(sizeof(TileSeg) == 32 && sizeof(TileRow) == 16 && sizeof(TileIRow) == 32, "table layout");
     {   // one packed record per step (a wavefront's consecutive steps are usually of different
@@ -243,7 +237,7 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
             covered += sg[i].nsteps;
         }
         SSQ_REQUIRE(covered == nsteps, "tile segments cover %lld of %d steps", (long long)covered, nsteps);
-        if ((rc = up((void**)&steps, hs.data(), hs.size() * 4))) return rc;
+        if ((rc = mem.upload(&steps, hs.data(), hs.size() * 4))) return rc;
     }
     {   // row records as the kernel reads them: row | padding << 9 | centre bin << 10, offset of the
         // row's samples inside its class
@@ -255,7 +249,7 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
             hp[2 * i] = row | (rw[i].row < 0 ? 0x200 : 0) | (int32_t)((uint32_t)rw[i].kc << 10);
             hp[2 * i + 1] = rw[i].ubase;
         }
-        if ((rc = up((void**)&rows, hp.data(), hp.size() * 4))) return rc;
+        if ((rc = mem.upload(&rows, hp.data(), hp.size() * 4))) return rc;
     }
     {   // the default kernels' items (see pack_items) and the wavefronts' shares of them
         const TileRow* rw = reinterpret_cast<const TileRow*>(d.rows);
@@ -270,8 +264,8 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
         ItemTable t2 = pack_items(sg, nsegs, rw, nsteps, M, N, 64 / cols2, false);
         tile2_ok = cut_item_blocks(t2, TILE2_NW, 0.7f, waves);
         n_items2 = t2.n;
-        if ((rc = up(&items2, t2.rec.data(), t2.rec.size() * 4))) return rc;
-        if ((rc = up((void**)&wave_first2, waves.data(), waves.size() * 4))) return rc;
+        if ((rc = mem.upload(&items2, t2.rec.data(), t2.rec.size() * 4))) return rc;
+        if ((rc = mem.upload(&wave_first2, waves.data(), waves.size() * 4))) return rc;
         tile3_ok = false;
         if (cols2 == 32) {
             // tile3_kernel: 4 rows x 32 columns, two columns per lane. (Measured with shader-clock stamps, round 6: an
@@ -280,8 +274,8 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
             std::vector<int32_t> dealt;
             tile3_ok = deal_item_lists(t3, TILE3_NW, 0.45f, 0.65f, dealt, waves);
             n_items3 = t3.n;
-            if ((rc = up(&items3, dealt.data(), dealt.size() * 4))) return rc;
-            if ((rc = up((void**)&wave_first3, waves.data(), waves.size() * 4))) return rc;
+            if ((rc = mem.upload(&items3, dealt.data(), dealt.size() * 4))) return rc;
+            if ((rc = mem.upload(&wave_first3, waves.data(), waves.size() * 4))) return rc;
             // (the 16 lanes of a sub-row hold the sample window of the tile's 32 columns: (31 >> lgR) + 8 + 1 <= 16 needs
             // a decimation of 4 or more -- R_MIN of _tiles.py; plans with a smaller one go to tile2_kernel)
             for (int i = 0; i < nsegs; ++i) if (sg[i].kind && sg[i].lgR < 2) tile3_ok = false;
@@ -303,9 +297,9 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
                     for (int k = 0; k < 4; ++k)
                         w[(size_t)(16 * o + (t * R + ph) * 4 + k)] = src[(size_t)(16 * (o + ph) + 4 * t + k)];
         }
-        if ((rc = up(&wtab, w.data(), (size_t)64 * d.n_phases))) return rc;
+        if ((rc = mem.upload(&wtab, w.data(), (size_t)64 * d.n_phases))) return rc;
     }
-    if ((rc = up(&tbank, d.tbank, (size_t)4 * d.n_tbank))) return rc;
+    if ((rc = mem.upload(&tbank, d.tbank, (size_t)4 * d.n_tbank))) return rc;
     cls.resize(d.n_classes);
     // classes of 2^14 entries and more: four-step kernels, L = A B with A <= B, both 128 .. 2048
     // (SSQ_DEBUG_TILE_FFT=rocfft keeps every class on rocFFT)
@@ -345,28 +339,27 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
             if (pass == 1) n_irows_fft += (int)cls[c].nrows;
         }
     SSQ_REQUIRE((int)hi.size() == n_irows, "tile rows of unknown classes");
-    if ((rc = up((void**)&irows, hi.data(), sizeof(TileIRow) * n_irows))) return rc;
+    if ((rc = mem.upload(&irows, hi.data(), sizeof(TileIRow) * n_irows))) return rc;
     if (own_fft) {
-        SSQ_CHECK_HIP(hipMalloc(&Y, (size_t)8 * std::max<int64_t>(y_entries, 1))); bytes += 8 * y_entries;
+        if ((rc = mem.alloc(&Y, (size_t)8 * y_entries))) return rc;
         std::vector<float> tw;
         for (int s = 0; s < 7; ++s) {
             const int Lp = 64 << s;
             ftw_off[s] = (int64_t)tw.size() / 2;
             fft_twiddles(Lp, tw);
         }
-        if ((rc = up(&ftw, tw.data(), tw.size() * 4))) return rc;
+        if ((rc = mem.upload(&ftw, tw.data(), tw.size() * 4))) return rc;
     }
     // (+ 4 rows of slack: tile2_kernel's padded sub-rows read, and discard, the rows behind a class's last)
-    SSQ_CHECK_HIP(hipMalloc(&U, (size_t)8 * (group * u_total + 4 * lmax))); bytes += 8 * (group * u_total + 4 * lmax);
+    if ((rc = mem.alloc(&U, (size_t)8 * (group * u_total + 4 * lmax)))) return rc;
     SSQ_CHECK_HIP(hipMemset(U, 0, (size_t)8 * (group * u_total + 4 * lmax)));
-    SSQ_CHECK_HIP(hipMalloc((void**)&counters, 4096));       // [0]: tiles done
+    if ((rc = mem.alloc(&counters, 4096))) return rc;        // [0]: tiles done
     SSQ_CHECK_HIP(hipMemset(counters, 0, 4096));
     for (size_t c = 0; c < cls.size(); ++c) {
         FftPlan fp;
         if (!cls[c].A && !cls[c].B) {
             rc = fp.create(1, SSQ_F32, (size_t)cls[c].L, (size_t)(group * cls[c].nrows), 1.0);
-            if (rc) return rc;
-            bytes += (int64_t)fp.work_bytes;
+            if (rc) { fp.destroy(); return rc; }
         }
         ffts.push_back(fp);
     }
@@ -384,11 +377,13 @@ void TilePlan::destroy() {
     ev_fork = ev_join = nullptr;
     for (auto& f : ffts) f.destroy();
     ffts.clear();
-    void* ptrs[] = {steps, rows, irows, wtab, tbank, U, counters, Y, ftw, items2, wave_first2, items3, wave_first3};
-    items2 = nullptr; wave_first2 = nullptr; items3 = nullptr; wave_first3 = nullptr;
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    steps = nullptr; rows = nullptr; irows = nullptr; wtab = tbank = U = Y = ftw = nullptr;
-    counters = nullptr;
+    mem.release();
+}
+
+int64_t TilePlan::bytes() const {
+    int64_t b = mem.bytes();
+    for (const FftPlan& f : ffts) b += (int64_t)f.work_bytes;
+    return b;
 }
 
 // SSQ_TILE_ORDER = ordered: the ticketed kernel (float32 sums in the reference's order, bit for bit; na <=

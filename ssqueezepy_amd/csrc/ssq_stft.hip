@@ -468,6 +468,7 @@ struct ssq_stft_plan {
     ssq_stft_desc d;
     int64_t padlen = 0, n1 = 0, n2 = 0, rows = 0, n_hops = 0;
     int rsize() const { return d.dtype == SSQ_F32 ? 4 : 8; }
+    DeviceArena mem;                              // every device pointer below but the weight versions
     void* window = nullptr; void* diff_window = nullptr;
     void* xp = nullptr; void* frames = nullptr; void* dframes = nullptr; void* dSx_ws = nullptr;
     FftPlan fft;                                  // R2C, transposed output: transform c writes bin f at Sx[f * n_hops + c]
@@ -493,7 +494,7 @@ int ssq_stft_plan_create(ssq_stft_plan** out, const ssq_stft_desc* desc) {
                 (long long)d.n, (long long)d.n_fft, (long long)d.hop_len);
     SSQ_REQUIRE(d.window, "window must not be null");
     SSQ_REQUIRE(d.padtype >= SSQ_PAD_ZERO && d.padtype <= SSQ_PAD_WRAP, "bad padtype %d", d.padtype);
-    auto* pl = new ssq_stft_plan();
+    PlanGuard<ssq_stft_plan> pl(new ssq_stft_plan(), ssq_stft_plan_destroy);
     pl->d = d;
     if (pl->d.max_batch < 1) pl->d.max_batch = 1;
     // padsignal(x, padlength = N + n_fft - 1): even total -> split evenly, odd -> left
@@ -505,58 +506,39 @@ int ssq_stft_plan_create(ssq_stft_plan** out, const ssq_stft_desc* desc) {
     pl->rows = d.n_fft / 2 + 1;
     pl->n_hops = (pl->padlen - d.n_fft) / d.hop_len + 1;
     const int rs = pl->rsize();
-    int rc = 0;
-#define TRYA(p, bytes) do { if (hipMalloc((void**)&(p), (bytes)) != hipSuccess) { set_error("hipMalloc failed (stft plan)"); ssq_stft_plan_destroy(pl); return -2; } } while (0)
-    TRYA(pl->window, (size_t)d.n_fft * rs);
-    SSQ_CHECK_HIP(hipMemcpy(pl->window, d.window, (size_t)d.n_fft * rs, hipMemcpyHostToDevice));
-    if (d.diff_window) {
-        TRYA(pl->diff_window, (size_t)d.n_fft * rs);
-        SSQ_CHECK_HIP(hipMemcpy(pl->diff_window, d.diff_window, (size_t)d.n_fft * rs, hipMemcpyHostToDevice));
-    }
-    TRYA(pl->xp, (size_t)pl->d.max_batch * pl->padlen * rs);
-#undef TRYA
+    DeviceArena& mem = pl->mem;
+    int rc;
+    if ((rc = mem.upload(&pl->window, d.window, (size_t)d.n_fft * rs))) return rc;
+    if (d.diff_window && (rc = mem.upload(&pl->diff_window, d.diff_window, (size_t)d.n_fft * rs))) return rc;
+    if ((rc = mem.alloc(&pl->xp, (size_t)pl->d.max_batch * pl->padlen * rs))) return rc;
+    const bool own = d.dtype == SSQ_F32 && !getenv("SSQ_DEBUG_STFT_GENERIC");
     const bool pow2 = (d.n_fft & (d.n_fft - 1)) == 0;
-    if (d.dtype == SSQ_F32 && pow2 && d.n_fft >= 128 && d.n_fft <= 2048 && !getenv("SSQ_DEBUG_STFT_GENERIC")) {
-        std::vector<float> tw((size_t)2 * d.n_fft);
+    pl->fused = own && pow2 && d.n_fft >= 128 && d.n_fft <= 2048;
+    pl->generic_fused = own && !pl->fused && stft_generic_plan(d.n_fft, pl->gen_radix, &pl->gen_npass, &pl->gen_G);
+    if (pl->fused || pl->generic_fused) {
+        std::vector<float> tw;
+        fft_twiddles((int)d.n_fft, tw);
+        if ((rc = mem.upload(&pl->ftw, tw.data(), tw.size() * 4))) return rc;
+    }
+    if (pl->fused && d.diff_window) {
+        std::vector<float> wd((size_t)2 * d.n_fft);
         for (int64_t q = 0; q < d.n_fft; ++q) {
-            double ang = 2.0 * 3.14159265358979323846 * (double)q / (double)d.n_fft;
-            tw[2 * q] = (float)cos(ang); tw[2 * q + 1] = (float)sin(ang);
+            wd[2 * q] = ((const float*)d.window)[q]; wd[2 * q + 1] = ((const float*)d.diff_window)[q];
         }
-        if (hipMalloc(&pl->ftw, tw.size() * 4) != hipSuccess) { set_error("hipMalloc failed (stft plan)"); ssq_stft_plan_destroy(pl); return -2; }
-        SSQ_CHECK_HIP(hipMemcpy(pl->ftw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
-        if (d.diff_window) {
-            std::vector<float> wd((size_t)2 * d.n_fft);
-            for (int64_t q = 0; q < d.n_fft; ++q) {
-                wd[2 * q] = ((const float*)d.window)[q]; wd[2 * q + 1] = ((const float*)d.diff_window)[q];
-            }
-            if (hipMalloc(&pl->wd, wd.size() * 4) != hipSuccess) { set_error("hipMalloc failed (stft plan)"); ssq_stft_plan_destroy(pl); return -2; }
-            SSQ_CHECK_HIP(hipMemcpy(pl->wd, wd.data(), wd.size() * 4, hipMemcpyHostToDevice));
-        }
-        pl->fused = true;
-    } else if (d.dtype == SSQ_F32 && !getenv("SSQ_DEBUG_STFT_GENERIC")
-               && stft_generic_plan(d.n_fft, pl->gen_radix, &pl->gen_npass, &pl->gen_G)) {
-        std::vector<float> tw((size_t)2 * d.n_fft);
-        for (int64_t q = 0; q < d.n_fft; ++q) {
-            double ang = 2.0 * 3.14159265358979323846 * (double)q / (double)d.n_fft;
-            tw[2 * q] = (float)cos(ang); tw[2 * q + 1] = (float)sin(ang);
-        }
-        if (hipMalloc(&pl->ftw, tw.size() * 4) != hipSuccess) { set_error("hipMalloc failed (stft plan)"); ssq_stft_plan_destroy(pl); return -2; }
-        SSQ_CHECK_HIP(hipMemcpy(pl->ftw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
-        pl->generic_fused = true;
+        if ((rc = mem.upload(&pl->wd, wd.data(), wd.size() * 4))) return rc;
     }
     // The framing workspace (two n_fft x n_hops arrays) and the rocFFT plan belong to the unfused route only: a fused
     // plan does without them (at the reference's hop-1 benchmark shape they would be 2 x 383 MB). The derivative's
     // workspace (dSx not returned, and no bin map in its place) is allocated at the first execute that needs it.
     if (!pl->fused && !pl->generic_fused) {
         const size_t fb = (size_t)d.n_fft * pl->n_hops * rs;
-        if (hipMalloc(&pl->frames, fb) != hipSuccess || hipMalloc(&pl->dframes, fb) != hipSuccess) {
-            set_error("hipMalloc failed (stft plan)"); ssq_stft_plan_destroy(pl); return -2;
-        }
+        if ((rc = mem.alloc(&pl->frames, fb))) return rc;
+        if ((rc = mem.alloc(&pl->dframes, fb))) return rc;
         rc = pl->fft.create(0, d.dtype, (size_t)d.n_fft, (size_t)pl->n_hops, 1.0, (size_t)d.n_fft, 1, (size_t)pl->n_hops);
-        if (rc) { ssq_stft_plan_destroy(pl); return rc; }
+        if (rc) return rc;
     }
     pl->d.window = nullptr; pl->d.diff_window = nullptr;
-    *out = pl;
+    *out = pl.release();
     return 0;
 }
 
@@ -564,9 +546,7 @@ void ssq_stft_plan_destroy(ssq_stft_plan* pl) {
     if (!pl) return;
     pl->fft.destroy();
     pl->weights.destroy(); pl->freqs.destroy(); pl->order.destroy();
-    void* ptrs[] = {pl->window, pl->diff_window, pl->xp, pl->frames, pl->dframes, pl->dSx_ws,
-                    pl->ftw, pl->kidx, pl->wd, pl->adj_off, pl->adj_idx};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    pl->mem.release();
     delete pl;
 }
 
@@ -574,23 +554,12 @@ int ssq_stft_plan_set_ssq(ssq_stft_plan* pl, const void* Sfs, int grid, const do
                           const void* cst, int cst_f64, int flipud, double gamma) {
     SSQ_REQUIRE(pl && Sfs && params && cst, "ssq_stft_plan_set_ssq: null pointer");
     SSQ_REQUIRE(grid >= SSQ_GRID_LOG && grid <= SSQ_GRID_LIN, "unknown grid kind %d", grid);
-    for (int t = 0; t < 5; ++t) pl->sp.p[t] = params[t];
-    pl->sp.grid = grid; pl->sp.flipud = flipud ? 1 : 0; pl->sp.gamma = gamma;
-    pl->sp.cst_f64 = (cst_f64 && pl->d.dtype == SSQ_F32) ? 1 : 0;
-    {
-        const bool wide = cst_f64 || pl->d.dtype == SSQ_F64;
-        bool uni = true;
-        for (int64_t i = 1; i < pl->rows && uni; ++i)
-            uni = wide ? ((const double*)cst)[i] == ((const double*)cst)[0]
-                       : ((const float*)cst)[i] == ((const float*)cst)[0];
-        pl->sp.cst_uniform = uni ? 1 : 0;
-    }
-    finalize_params(pl->sp);
-    const int rs = pl->rsize();
     std::lock_guard<std::mutex> lock(pl->order.mu);
-    int rc = pl->weights.upload(&pl->cst, cst, (size_t)pl->rows * ((cst_f64 || rs == 8) ? 8 : 4));
+    float cst0;                                            // (the STFT kernels read the weights' table)
+    int rc = set_ssq_params(pl->sp, pl->weights, &pl->cst, &cst0, pl->d.dtype, pl->rows, grid, params, cst, cst_f64, flipud,
+                            gamma);
     if (rc) return rc;
-    rc = pl->freqs.upload(&pl->Sfs, Sfs, (size_t)pl->rows * rs);
+    rc = pl->freqs.upload(&pl->Sfs, Sfs, (size_t)pl->rows * pl->rsize());
     if (rc) return rc;
     pl->have_ssq = true;
     return 0;
@@ -622,13 +591,6 @@ static int stft_execute_t(ssq_stft_plan* pl, const void* x, int64_t batch, void*
     if (!pad_in_kernel) rc = ssq_pad_signal(d.dtype, x, pl->xp, batch, d.n, pl->n1, pl->n2, d.padtype, stream);
     if (rc) return rc;
     const int64_t s20 = (n_fft + 1) / 2, s21 = (n_fft % 2 == 1) ? s20 - 1 : s20;
-    // (decided below: whether the derivative is stored at all; its workspace exists from the first call that needs one)
-    auto dsx_workspace = [&]() -> void* {
-        if (!pl->dSx_ws) {
-            if (hipMalloc(&pl->dSx_ws, (size_t)pl->d.max_batch * rows * n_hops * sizeof(T) * 2) != hipSuccess) return nullptr;
-        }
-        return pl->dSx_ws;
-    };
     T* dS = (T*)dSx;
     // fused ssq_stft form: Tx wanted, neither dSx nor w -> the kernel emits 2-byte bins
     // instead of the 8-byte derivative (the reassignment then reads 10 instead of 16 B/pt)
@@ -643,61 +605,55 @@ static int stft_execute_t(ssq_stft_plan* pl, const void* x, int64_t batch, void*
             const char* fe = getenv("SSQ_DEBUG_STFT_FUSED_TX");        // (read at every call, like SSQ_TILE_ORDER: tests switch it)
             const int force = (fe && *fe) ? atoi(fe) : -1;
             fused_tx = !reassign_ordered() && rows == n_fft / 2 + 1 && force != 0;
-            if (!fused_tx && !pl->kidx)
-                SSQ_CHECK_HIP(hipMalloc((void**)&pl->kidx, (size_t)pl->d.max_batch * rows * n_hops * 2));
+            if (!fused_tx && !pl->kidx && (rc = pl->mem.alloc(&pl->kidx, (size_t)pl->d.max_batch * rows * n_hops * 2)))
+                return rc;
         }
     }
-    if (deriv && !dSx && !use_kidx) {              // the derivative is needed (phase transform / bins) but not returned
-        dS = (T*)dsx_workspace();
-        SSQ_REQUIRE(dS, "hipMalloc failed (stft derivative workspace)");
+    // the derivative is needed (phase transform / bins) but not returned: its workspace exists from the first such call
+    if (deriv && !dSx && !use_kidx) {
+        if (!pl->dSx_ws && (rc = pl->mem.alloc(&pl->dSx_ws, (size_t)pl->d.max_batch * rows * n_hops * sizeof(T) * 2)))
+            return rc;
+        dS = (T*)pl->dSx_ws;
     }
     if constexpr (sizeof(T) == 4) {
-        if (pl->fused) {
+        if (pl->fused || pl->generic_fused) {
             StftFusedArgs A;
             A.xp = (const float*)pl->xp; A.window = (const float*)pl->window;
-            A.diff_window = (const float*)pl->diff_window; A.ftw = (const c32*)pl->ftw;
+            A.diff_window = (const float*)pl->diff_window;
             A.Sx = (float2*)Sx; A.dSx = (deriv && !use_kidx) ? (float2*)dS : nullptr;
             A.kidx = (use_kidx && !fused_tx) ? pl->kidx : nullptr; A.Sfs = (const float*)pl->Sfs; A.gamma = pl->sp.gamma;
             A.Tx = fused_tx ? (float2*)Tx : nullptr; A.cst = pl->cst; A.cst_uniform = pl->sp.cst_uniform;
             A.padlen = pl->padlen; A.n_hops = n_hops; A.rows = rows;
             A.hop = (int)d.hop_len; A.s20 = (int)s20; A.s21 = (int)s21; A.modulated = d.modulated;
-            A.x = pad_in_kernel ? (const float*)x : nullptr; A.n = (int)d.n; A.n1 = (int)pl->n1; A.padtype = d.padtype;
-            A.wd = (const float2*)pl->wd;
-            rc = fft_dispatch<128, 2048>(n_fft, [&](auto len) { return launch_stft_fused<decltype(len)::value>(A, pl->sp, batch, stream); });
+            A.n = (int)d.n; A.n1 = (int)pl->n1; A.padtype = d.padtype;
+            if (pl->fused) {                              // (its launch sets xcd and batch)
+                A.ftw = (const c32*)pl->ftw; A.x = pad_in_kernel ? (const float*)x : nullptr; A.wd = (const float2*)pl->wd;
+                rc = fft_dispatch<128, 2048>(n_fft, [&](auto len) { return launch_stft_fused<decltype(len)::value>(A, pl->sp, batch, stream); });
+            } else {                                      // (the twiddles are an argument of its own)
+                A.ftw = nullptr; A.x = nullptr; A.wd = nullptr; A.xcd = 0; A.batch = (int)batch;
+                rc = launch_stft_generic(A, pl->sp, (const c32*)pl->ftw, (int)n_fft, pl->gen_radix, pl->gen_npass, pl->gen_G,
+                                         batch, stream);
+            }
             if (rc) return rc;
         }
     }
-    if constexpr (sizeof(T) == 4) {
-        if (pl->generic_fused) {
-            StftFusedArgs A;
-            A.xp = (const float*)pl->xp; A.window = (const float*)pl->window;
-            A.diff_window = (const float*)pl->diff_window; A.ftw = nullptr;
-            A.Sx = (float2*)Sx; A.dSx = (deriv && !use_kidx) ? (float2*)dS : nullptr;
-            A.kidx = (use_kidx && !fused_tx) ? pl->kidx : nullptr; A.Sfs = (const float*)pl->Sfs; A.gamma = pl->sp.gamma;
-            A.Tx = fused_tx ? (float2*)Tx : nullptr; A.cst = pl->cst; A.cst_uniform = pl->sp.cst_uniform;
-            A.padlen = pl->padlen; A.n_hops = n_hops; A.rows = rows;
-            A.hop = (int)d.hop_len; A.s20 = (int)s20; A.s21 = (int)s21; A.modulated = d.modulated; A.xcd = 0;
-            A.x = nullptr; A.n = (int)d.n; A.n1 = (int)pl->n1; A.padtype = d.padtype; A.wd = nullptr; A.batch = (int)batch;
-            rc = launch_stft_generic(A, pl->sp, (const c32*)pl->ftw, (int)n_fft, pl->gen_radix, pl->gen_npass, pl->gen_G,
-                                     batch, stream);
+    if (!pl->fused && !pl->generic_fused) {               // rocFFT route: frames, then one transform per plane and signal
+        for (int64_t b = 0; b < batch; ++b) {
+            const T* xp = (const T*)pl->xp + (size_t)b * pl->padlen;
+            int64_t total = n_fft * n_hops;
+            unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
+            hipLaunchKernelGGL((frame_window_kernel<T>), dim3(g), dim3(256), 0, stream, xp,
+                               (const T*)pl->window, (const T*)pl->diff_window, (T*)pl->frames,
+                               deriv ? (T*)pl->dframes : (T*)nullptr, n_fft, n_hops, d.hop_len, s20, s21,
+                               d.modulated);
+            SSQ_LAUNCH_CHECK();
+            T* Sx_b = (T*)Sx + (size_t)b * rows * n_hops * 2;
+            rc = pl->fft.execute(pl->frames, Sx_b, stream);
             if (rc) return rc;
-        }
-    }
-    for (int64_t b = 0; b < ((pl->fused || pl->generic_fused) ? 0 : batch); ++b) {
-        const T* xp = (const T*)pl->xp + (size_t)b * pl->padlen;
-        int64_t total = n_fft * n_hops;
-        unsigned g = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-        hipLaunchKernelGGL((frame_window_kernel<T>), dim3(g), dim3(256), 0, stream, xp,
-                           (const T*)pl->window, (const T*)pl->diff_window, (T*)pl->frames,
-                           deriv ? (T*)pl->dframes : (T*)nullptr, n_fft, n_hops, d.hop_len, s20, s21,
-                           d.modulated);
-        SSQ_LAUNCH_CHECK();
-        T* Sx_b = (T*)Sx + (size_t)b * rows * n_hops * 2;
-        rc = pl->fft.execute(pl->frames, Sx_b, stream);
-        if (rc) return rc;
-        if (deriv) {
-            rc = pl->fft.execute(pl->dframes, dS + (size_t)b * rows * n_hops * 2, stream);
-            if (rc) return rc;
+            if (deriv) {
+                rc = pl->fft.execute(pl->dframes, dS + (size_t)b * rows * n_hops * 2, stream);
+                if (rc) return rc;
+            }
         }
     }
     if (w) {
@@ -742,13 +698,11 @@ static int stft_adjoint_pad_table(ssq_stft_plan* pl) {
     SSQ_REQUIRE(m < ((int64_t)1 << 31), "stft adjoint: padded length %lld", (long long)m);
     std::vector<int32_t> off, idx;                         // (the rule of pad_kernel / stft_pad_source)
     inverse_pad_table(n, m, n1, pl->d.padtype, off, idx);
-    SSQ_CHECK_HIP(hipMalloc((void**)&pl->adj_idx, idx.size() * 4 + 4));
-    SSQ_CHECK_HIP(hipMemcpy(pl->adj_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-    int32_t* o = nullptr;
-    SSQ_CHECK_HIP(hipMalloc((void**)&o, off.size() * 4));
-    SSQ_CHECK_HIP(hipMemcpy(o, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    pl->adj_off = o;
-    return 0;
+    // (a failure part-way is undone by ssq_stft_adjoint)
+    idx.push_back(0);                                      // (one entry of slack, as the table always had)
+    int rc = pl->mem.upload(&pl->adj_idx, idx.data(), idx.size() * 4);
+    if (!rc) rc = pl->mem.upload(&pl->adj_off, off.data(), off.size() * 4);
+    return rc;
 }
 
 template <typename T>
@@ -812,6 +766,8 @@ extern "C" int ssq_stft_adjoint(ssq_stft_plan* pl, const void* gSx, const void* 
     SSQ_REQUIRE(!gdSx || pl->diff_window, "the gradient of dSx needs a diff_window");
     hipStream_t st = as_stream(stream);
     pl->order.enter(st);
+    const bool first = !pl->adj_off;
+    const size_t before = pl->mem.count();
     int rc = stft_adjoint_pad_table(pl);
     if (!rc) {
         const ssq_stft_desc& d = pl->d;
@@ -826,6 +782,10 @@ extern "C" int ssq_stft_adjoint(ssq_stft_plan* pl, const void* gSx, const void* 
                 return stft_adjoint_unpad<decltype(t)>(pl, pl->xp, gx, batch, 1, pl->padlen, pl->padlen, pl->padlen, st);
             });
         }
+    }
+    if (rc && first) {       // a first call that fails leaves the plan as it found it: the next one starts over
+        pl->mem.release(before);
+        pl->adj_off = pl->adj_idx = nullptr;
     }
     pl->order.leave(st);
     return rc;

@@ -337,17 +337,11 @@ bool AnalyticFft::supports(int dtype, int64_t M) {
     if (getenv("SSQ_DEBUG_TILE_FFT") && !strcmp(getenv("SSQ_DEBUG_TILE_FFT"), "rocfft")) return false;
     return M >= ((int64_t)1 << 13) && M <= ((int64_t)1 << 22);
 }
-int AnalyticFft::create(int64_t M_, int64_t max_batch_, int64_t& bytes) {
+int AnalyticFft::create(int64_t M_, int64_t max_batch_) {
     M = M_; max_batch = max_batch_;
     int lg = 0;
     while (((int64_t)1 << lg) < M) ++lg;
     B = 1 << ((lg + 1) / 2); A = 1 << (lg / 2);
-    auto up = [&](void** dst, const void* src, size_t nbytes) -> int {
-        SSQ_CHECK_HIP(hipMalloc(dst, nbytes));
-        SSQ_CHECK_HIP(hipMemcpy(*dst, src, nbytes, hipMemcpyHostToDevice));
-        bytes += (int64_t)nbytes;
-        return 0;
-    };
     int rc;
     std::vector<float> tw;
     for (int which = 0; which < 2; ++which) {
@@ -355,20 +349,14 @@ int AnalyticFft::create(int64_t M_, int64_t max_batch_, int64_t& bytes) {
         (which ? off_b : off_a) = (int64_t)tw.size() / 2;
         fft_twiddles(Lp, tw);
     }
-    if ((rc = up(&ftw, tw.data(), tw.size() * 4))) return rc;
+    if ((rc = mem.upload(&ftw, tw.data(), tw.size() * 4))) return rc;
     // weights: 1 / M on bins [0, M / 2), half of it at the Nyquist bin (both exact: M is a power of two)
     std::vector<float> w((size_t)(M / 2 + 1), 1.0f / (float)M);
     w[(size_t)(M / 2)] = 0.5f / (float)M;
-    if ((rc = up(&tb, w.data(), w.size() * 4))) return rc;
+    if ((rc = mem.upload(&tb, w.data(), w.size() * 4))) return rc;
     const TileIRow r = {0, 0, (int32_t)(M / 2 + 1), 0, (int32_t)M, 0, 0, (int32_t)M};
-    if ((rc = up((void**)&irow, &r, sizeof(r)))) return rc;
-    SSQ_CHECK_HIP(hipMalloc(&Y, (size_t)8 * max_batch * M)); bytes += 8 * max_batch * M;
-    return 0;
-}
-void AnalyticFft::destroy() {
-    void* ptrs[] = {Y, ftw, tb, irow};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    Y = ftw = tb = nullptr; irow = nullptr;
+    if ((rc = mem.upload(&irow, &r, sizeof(r)))) return rc;
+    return mem.alloc(&Y, (size_t)8 * max_batch * M);
 }
 int AnalyticFft::run(const void* xh_all, void* xa, int64_t batch, hipStream_t stream) {
     TileFourArgs F;

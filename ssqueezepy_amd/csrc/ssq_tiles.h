@@ -40,11 +40,12 @@ struct TileIRow {
 struct AnalyticFft {
     int64_t M = 0, max_batch = 0;
     int A = 0, B = 0;
+    DeviceArena mem;
     void* Y = nullptr; void* ftw = nullptr; void* tb = nullptr; TileIRow* irow = nullptr;
     int64_t off_a = 0, off_b = 0;           // twiddle tables e^{2 pi i q / A}, e^{2 pi i q / B} inside ftw
     static bool supports(int dtype, int64_t M);
-    int create(int64_t M, int64_t max_batch, int64_t& bytes);
-    void destroy();
+    int create(int64_t M, int64_t max_batch);
+    void destroy() { mem.release(); }
     int run(const void* xh_all, void* xa, int64_t batch, hipStream_t stream);
 };
 
@@ -89,6 +90,7 @@ struct TilePlan {
     int nsegs = 0, nsteps = 0, n_irows = 0;
     int64_t u_total = 0, lmax = 0;
     int ncu = 0;                            // persistent workgroups of the tile kernel (one per CU)
+    DeviceArena mem;                        // every device pointer below
     int4* steps = nullptr;                  // packed step records: kind | lgR << 1 | weights' offset << 8, L - 1,
                                             // entries between two signals' rows of the class, entries before it
     int2* rows = nullptr;                   // packed row records (TILE_G per step): row | pad << 9 | kc << 10, ubase
@@ -135,8 +137,9 @@ struct TilePlan {
     hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
     int create(const ssq_cwt_tiles_desc& d, int64_t M, int64_t N, int64_t n1, int64_t na, int group,
-               double dt, int64_t& bytes);
+               double dt);
     void destroy();
+    int64_t bytes() const;                  // device memory of the tables, workspaces and transforms
     // intermediates of signals sig .. sig+nsig-1 (nsig <= group) from the spectra of the batch
     int spectra(int sig, int nsig, const void* xh_all, hipStream_t stream);
     // Wx of the interpolated rows, Tx of all rows (the other rows' Wx and bin map must be in place)

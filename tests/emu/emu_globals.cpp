@@ -11,3 +11,9 @@ namespace ssq {
 alignas(64) thread_local unsigned char lds_raw[160 * 1024];
 alignas(64) thread_local unsigned char smem[160 * 1024];
 }
+
+// the allocation counter and the failure switch of hip/hip_runtime.h, for ctypes
+extern "C" {
+long ssq_emu_live_allocations() { return emu::live_allocs.load(); }
+long ssq_emu_fail_malloc(long k) { return emu::fail_malloc_in.exchange(k); }    // returns what was left of the last one
+}

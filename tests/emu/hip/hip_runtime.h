@@ -17,6 +17,7 @@
 #include <functional>
 #include <thread>
 #include <vector>
+#include <dlfcn.h>
 #include <sys/mman.h>
 #include <ucontext.h>
 
@@ -106,21 +107,43 @@ inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
     p->multiProcessorCount = 3; p->totalGlobalMem = 0; p->maxSharedMemoryPerMultiProcessor = 160 * 1024;
     return hipSuccess;
 }
-inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : 2; }
+namespace emu {
+// for the tests of the plans' failure paths (emu_globals.cpp exports a getter and a setter): allocations not yet freed,
+// and "the k-th hipMalloc from now fails" (0: none does)
+inline std::atomic<long> live_allocs{0}, fail_malloc_in{0};
+// SSQ_EMU_LAUNCH_LOG=<file>: one line per kernel launch (name, grid, block, dynamic LDS bytes, stream) and per event
+// record, stream wait and transform, appended to the file -- two builds of the host code compare their logs with diff.
+// Streams and events are told apart by a number each while the log is on (without it they stay the no-ops they were).
+inline FILE* launch_log() {
+    static FILE* f = [] { const char* e = getenv("SSQ_EMU_LAUNCH_LOG"); return (e && *e) ? fopen(e, "a") : (FILE*)nullptr; }();
+    return f;
+}
+inline void* log_handle(void* otherwise) {
+    static std::atomic<uintptr_t> next{0x100};
+    return launch_log() ? (void*)(next += 0x10) : otherwise;
+}
+#define EMU_LOG(...) do { if (FILE* f_ = emu::launch_log()) { fprintf(f_, __VA_ARGS__); fflush(f_); } } while (0)
+}  // namespace emu
+inline hipError_t hipMalloc(void** p, size_t n) {
+    if (emu::fail_malloc_in > 0 && --emu::fail_malloc_in == 0) { *p = nullptr; return 2; }
+    *p = malloc(n ? n : 1);
+    if (*p) ++emu::live_allocs;
+    return *p ? hipSuccess : 2;
+}
 template <typename P> hipError_t hipMalloc(P** p, size_t n) { return hipMalloc((void**)p, n); }
 inline hipError_t hipMallocAsync(void** p, size_t n, hipStream_t) { return hipMalloc(p, n); }
 template <typename P> hipError_t hipMallocAsync(P** p, size_t n, hipStream_t) { return hipMalloc((void**)p, n); }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-inline hipError_t hipFreeAsync(void* p, hipStream_t) { free(p); return hipSuccess; }
+inline hipError_t hipFree(void* p) { if (p) --emu::live_allocs; free(p); return hipSuccess; }
+inline hipError_t hipFreeAsync(void* p, hipStream_t) { return hipFree(p); }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, int) { memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, int, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
 inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return hipSuccess; }
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = emu::log_handle(nullptr); return hipSuccess; }
 constexpr int hipEventDisableTiming = 2;
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, int) { *e = (hipEvent_t)1; return hipSuccess; }
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, int) { return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, int) { *e = emu::log_handle((hipEvent_t)1); return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, int) { EMU_LOG("wait event %p stream %p\n", e, s); return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 typedef void* hipGraph_t; typedef void* hipGraphExec_t;
 constexpr int hipStreamCaptureModeRelaxed = 2;
@@ -131,10 +154,10 @@ inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return 1; }
 inline hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
 inline hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
 constexpr int hipStreamNonBlocking = 1;
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, int) { *s = nullptr; return hipSuccess; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, int) { *s = emu::log_handle(nullptr); return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
 inline hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t = nullptr) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s = nullptr) { EMU_LOG("record event %p stream %p\n", e, s); return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 
@@ -385,7 +408,13 @@ inline void lds_guard(size_t asked, bool check, dim3 b) {
 }  // namespace emu
 
 template <typename K, typename... Args>
-void emu_launch(K kernel, dim3 grid, dim3 block, size_t dyn_lds, Args... args) {
+void emu_launch(const char* text, hipStream_t stream, K kernel, dim3 grid, dim3 block, size_t dyn_lds, Args... args) {
+    if (emu::launch_log()) {                 // (the symbol carries a template's arguments, where the kernel has one)
+        Dl_info di;
+        const bool sym = dladdr(reinterpret_cast<const void*>(kernel), &di) && di.dli_sname;
+        EMU_LOG("launch %s %s grid %u %u %u block %u %u %u lds %zu stream %p\n", text, sym ? di.dli_sname : "-", grid.x, grid.y,
+                grid.z, block.x, block.y, block.z, dyn_lds, stream);
+    }
     static const bool guard = getenv("SSQ_EMU_LDSGUARD") != nullptr;
     if (dyn_lds > emu::DYN_LDS_BYTES) { fprintf(stderr, "emu: %zu bytes of dynamic LDS requested\n", dyn_lds); abort(); }
     const std::function<void()> kbody = [=] { kernel(args...); };
@@ -416,4 +445,4 @@ void emu_launch(K kernel, dim3 grid, dim3 block, size_t dyn_lds, Args... args) {
 }
 // (kernel), grid, block, dynamic LDS bytes, stream, args...
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) \
-    emu_launch(kernel, dim3(grid), dim3(block), (size_t)(lds), __VA_ARGS__)
+    emu_launch(#kernel, stream, kernel, dim3(grid), dim3(block), (size_t)(lds), __VA_ARGS__)

@@ -3,6 +3,7 @@
 // scale factor), computed in double precision on the CPU. TEST INFRASTRUCTURE ONLY
 // (tests/emu/): lets the plans run where there is no GPU.
 #pragma once
+#include "hip/hip_runtime.h"     // (EMU_LOG)
 #include <cmath>
 #include <complex>
 #include <cstddef>
@@ -156,6 +157,7 @@ void run(rocfft_plan p, void* in, void* out) {
 
 inline rocfft_status rocfft_execute(rocfft_plan p, void** in, void** out, rocfft_execution_info) {
     void* o = out ? out[0] : nullptr;
+    EMU_LOG("transform type %d n %zu batch %zu %s\n", (int)p->type, p->n, p->batch, o ? "out of place" : "in place");
     static const bool fft32 = getenv("SSQ_EMU_FFT32") != nullptr;
     if (p->prec == rocfft_precision_single) {
         if (fft32) emu_fft::run<float, float>(p, in[0], o);

@@ -250,6 +250,48 @@ def test_batches_larger_than_a_launch_group(S):
         assert_tx_repeat(Tb[s].cpu().numpy(), T1.cpu().numpy(), what=s)
 
 
+@pytest.mark.parametrize('way', ['tiles', 'no_tiles', 'ordered'])
+def test_plan_timing_stages(S, way, monkeypatch, N=4201, na=64, B=17):
+    """`plan.timing` (the per-stage HIP-event timing `bench.py --full` reads) over two launch groups -- 17 signals,
+    16 to a group -- on the tile path, without it (`SSQ_CWT_TILES=0`) and with the ordered tile kernel: the timed
+    execute counts its 17 signals and four finite stage times >= 0 whose sum is > 0, and it computes what the untimed
+    one does (timed, the tile path's decimated samples run in line, not on the side stream). The plan is the one of
+    tests/test_gpu_tile_rows.py: `gmw` float32, `na` log-spaced scales, through the plan interface."""
+    import torch
+    from ssqueezepy_amd import _cwt, algos
+    from test_gpu_tile_rows import design_of, GAMMA
+    if way == 'no_tiles':
+        monkeypatch.setenv('SSQ_CWT_TILES', '0')
+    else:
+        needs_tile_path()
+    monkeypatch.setenv('SSQ_TILE_ORDER', 'ordered' if way == 'ordered' else os.environ.get('SSQ_TILE_ORDER', ''))
+    wav, scales_dt, _, _, grid, params = design_of(S, N, na, 'log')
+    xb = np.stack([two_chirps(N, seed=N + 7 * s) for s in range(B)])
+    _cwt.clear_plan_cache()
+    try:
+        plan = _cwt.get_cwt_plan(wav, scales_dt, N, 'reflect', 1., True, B)
+        assert plan.group == 16
+        assert plan.algo.endswith('+tiles') == (way != 'no_tiles'), plan.algo
+        plan.set_ssq(grid, params, np.log(2) / 32, True, GAMMA)
+        xd = algos.to_device(xb, torch.float32)
+        run = lambda: {k: v.cpu().numpy() for k, v in plan.execute(xd, want_Tx=True).items()}
+        plain = run()
+        assert plan.timing(1) == ([0.0] * 4, 0)
+        timed = run()
+        ms, signals = plan.timing(0)
+        again = run()
+        assert plan.timing() == ([0.0] * 4, 0)               # switched off: nothing is counted any more
+    finally:
+        _cwt.clear_plan_cache()
+    assert signals == B
+    assert len(ms) == 4 and all(np.isfinite(v) and v >= 0 for v in ms), ms
+    if os.environ.get('SSQ_EMULATE') != '1':                 # (the emulator's events carry no time)
+        assert sum(ms) > 0, ms
+    for other in (timed, again):
+        assert np.array_equal(other['Wx'], plain['Wx'])
+        assert_tx_repeat(other['Tx'], plain['Tx'], what=way)
+
+
 @pytest.mark.parametrize('N', [100000, 1 << 20])
 def test_tile_intermediates_four_step_vs_rocfft(S, N, monkeypatch):
     """The long classes of the tile path's intermediates on the four-step kernels (default) against

@@ -369,6 +369,18 @@ def test_tile_path_emulated_partial_launch_group():
             assert_tx_repeat(Tb[s], T1, what=s)
 
 
+@pytest.mark.parametrize('way', ['tiles', 'no_tiles', 'ordered'])
+def test_plan_timing_stages_emulated(way, monkeypatch):
+    """tests/test_gpu_edge_cases.py::test_plan_timing_stages under the emulator: the timed execute's event bookkeeping
+    over two launch groups, its signal count, and the same `Wx`, `Tx` timed or not (the emulator's events carry no
+    time: the stage times are zeros, and only the device's run asserts their sum)."""
+    import emu_backend
+    import test_gpu_edge_cases as E
+    monkeypatch.setenv('SSQ_EMULATE', '1')
+    with emu_backend.emulated() as S:
+        E.test_plan_timing_stages(S, way, monkeypatch)
+
+
 def test_tile_path_emulated_fewer_steps_than_wavefronts(tile_mode):
     """Very few scales: some wavefronts of the tile kernels have no step / item at all and only take
     part in the write-out of each tile."""
