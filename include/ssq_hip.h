@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 113 (112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 114 (113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -269,6 +269,46 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx,
                     const void* cst, int cst_f64, int64_t batch, int64_t na,
                     int64_t n, int grid, const double* params, int flipud,
                     void* stream);
+
+/* Multisynchrosqueezing, MSST (ABI 114; Yu, Wang, Zhao 2019): the first-order frequency map
+ * applied to its own output n_iter - 1 times within a column, on real-valued frequencies, then ssq_indexed_sum's
+ * accumulate from the final frequency of every point.
+ *   Sx      (batch, rows, n) complex `dtype`, device
+ *   w       (batch, rows, n) real `dtype`: the phase transform ssq_phase_stft or ssq_stft2_phase wrote; inf = skip
+ *   Tx      (batch, rows, n) complex `dtype`; overwritten
+ *   wf      optional (NULL), (batch, rows, n) real `dtype`: the final frequency of every point, inf where skipped
+ *   cst, cst_f64, grid, params, flipud   exactly ssq_indexed_sum's: the weights and the bins of the output
+ *   f0, df  the rows' grid: row i sits at f0 + i df. The iteration runs on it, the final binning on `params`; the two
+ *           need not coincide
+ *   n_iter  1 .. 1024;  interp: 0 = the nearest row (the paper's form), 1 = linear interpolation between two rows
+ * Per signal and column, for every row i ascending with w[i] finite (a NaN is skipped like an inf; ssq_indexed_sum
+ * puts it in bin 0), in float64 for both dtypes (a float32 w is promoted), basic IEEE operations only, no contraction:
+ *       f = w[i]
+ *       repeat at most n_iter - 1 times:
+ *           p = (f - f0) / df
+ *           if not (p >= 0 and p <= rows - 1): break            NaN included
+ *           r = rint(p)  (half to even);  g = w[r]
+ *           interp = 1:  i0 = min(floor(p), rows - 2);  a = p - i0
+ *                        if w[i0] and w[i0 + 1] are both finite:  g = w[i0] + a * (w[i0 + 1] - w[i0])
+ *           if g is not finite: break                           a row that holds nothing points nowhere
+ *           if g == f: break                                    a fixed point
+ *           f = g
+ *       fT = f rounded once to `dtype`;  wf[i] = fT
+ *       k  = the bin of fT exactly as ssq_indexed_sum bins a stored w (flipud included)
+ *       Tx[k] += Sx[i] * cst[i]                                 term, sum type and order (ascending i): ssq_indexed_sum's
+ * With n_iter = 1, Tx is ssq_indexed_sum's bit for bit. Bit-reproducible from call to call; `batch` signals in one call
+ * equal `batch` calls of one signal. One kernel: a tile of 16, 8 or 4 columns (the widest that fits) keeps its Tx cells
+ * and its columns of w in LDS, 3 reals per row and column; the iteration is a loop of LDS gathers. Refused, with Tx and wf
+ * unwritten and a message that begins with the entry's name: a null Sx, w, Tx, cst or params; batch or n < 1, or rows < 2;
+ * rows > ssq_multi_squeeze_max_rows(dtype); batch rows n >= 2^32; n_iter outside 1 .. 1024; interp outside {0, 1}; df not
+ * finite or <= 0, or f0 not finite; an unknown `grid`. No counterpart in the reference. */
+int ssq_multi_squeeze(int dtype, const void* Sx, const void* w, void* Tx, void* wf,
+                      const void* cst, int cst_f64, int64_t batch, int64_t rows, int64_t n,
+                      double f0, double df, int64_t n_iter, int interp,
+                      int grid, const double* params, int flipud, void* stream);
+/* The most rows ssq_multi_squeeze takes: what a 4-column tile holds in 160 KiB of LDS, 160 KiB / (4 * 3 * sizeof real) =
+ * 3413 (float32) or 1706 (float64); 0 for an unknown dtype. */
+int ssq_multi_squeeze_max_rows(int dtype);
 
 /* w[q] = replacement where |ref[q]| < value.
  * replaces replace_under_abs (algos.py:498-579). */

@@ -28,6 +28,7 @@ def __getattr__(name):
         'conceft_stft': '_conceft', 'hermite_windows': '_conceft', 'conceft_gpu': 'algos',
         'conceft_cwt': '_conceft_cwt', 'morse_wavelets': 'wavelets', 'conceft_cwt_gpu': 'algos',
         'tssq_stft': '_tssq_stft', 'time_reassign_gpu': 'algos',
+        'msst_stft': '_msst_stft', 'multi_squeeze_gpu': 'algos',
         'ssqueeze_fast': 'algos', 'indexed_sum_onfly': 'algos', 'buffer': 'algos',
         'replace_under_abs': 'algos', 'phase_cwt_gpu': 'algos',
         'phase_stft_gpu': 'algos', 'phase_stft2_gpu': 'algos', 'phase_cwt2_gpu': 'algos',

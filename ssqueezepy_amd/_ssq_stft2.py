@@ -28,6 +28,54 @@ def _second_order_windows(g, dg, n_fft, fs):
     return (tau * g64, tau * dg64), (g64, _spectral_derivative(dg64) * fs)
 
 
+def _stft_phase_map(name, x, window, n_fft, win_len, hop_len, fs, t, ssq_freqs, padtype, gamma,
+                    chirp_tol, dtype, order=2):
+    """The host steps of `ssq_stft2` up to its reassignment, for it and for `msst_stft` (`name` in the
+    message): the check of `ssq_freqs`, the plans, the defaults of `gamma`, `ssq_freqs` and `const`,
+    the executions and the map. ``order=2``: three executions and `phase_stft2_gpu`; ``order=1``: one
+    and `phase_stft_gpu`. Returns ``(Sx, w, ssq_freqs, Sfs, const)``."""
+    if order not in (1, 2):
+        raise ValueError("`order` must be 1 or 2 (got %r)" % (order,))
+    if (isinstance(ssq_freqs, np.ndarray) and
+            infer_scaletype(ssq_freqs)[0] != 'linear'):
+        raise ValueError("`ssq_freqs` must be linearly distributed "
+                         "for `%s`" % name)
+    plan, xd, fs, dtype = _stft_setup(x, window, n_fft, win_len, hop_len, fs, t,
+                                      padtype, True, dtype)
+    xd = xd.detach()
+    B = xd.shape[0] if xd.ndim == 2 else 1
+    # the pair the first plan was made with: a cache hit after _stft_setup, which has already
+    # issued the NOLA warnings -- for `g`, the only window they are about
+    n_fft = plan.n_fft
+    if win_len is None:
+        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
+    plans = []
+    if order == 2:
+        g, dg, _ = _window_design(window, win_len, n_fft, hop_len, dtype)
+        pair_t, pair_dd = _second_order_windows(g, dg, n_fft, fs)
+        plans = [get_stft_plan(plan.N, n_fft, hop_len, wa, wb, fs, padtype, True, dtype, B)
+                 for wa, wb in (pair_t, pair_dd)]
+
+    Sfs = _make_Sfs(plan.rows, fs, dtype)
+    if gamma is None:
+        gamma = 10 * (EPS64 if dtype == 'float64' else EPS32)
+    if ssq_freqs is None:
+        ssq_freqs = Sfs
+    ssq_freqs = np.asarray(ssq_freqs)
+    const = (ssq_freqs[1] - ssq_freqs[0])
+
+    out = plan.execute(xd, want_dSx=True)
+    Sx, Vdg = out['Sx'], out['dSx']
+    if order == 1:
+        return Sx, algos.phase_stft_gpu(Sx, Vdg, Sfs, gamma), ssq_freqs, Sfs, const
+    out = plans[0].execute(xd, want_dSx=True)
+    Vtg, Vtdg = out['Sx'], out['dSx']
+    Vddg = plans[1].execute(xd, want_dSx=True)['dSx']
+    w = algos.phase_stft2_gpu(Sx, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol)
+    del Vdg, Vddg, Vtg, Vtdg, out
+    return Sx, w, ssq_freqs, Sfs, const
+
+
 def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=None,
               ssq_freqs=None, padtype='reflect', gamma=None, chirp_tol=1e-3,
               dtype=None, astensor=True, flipud=False, get_w=False):
@@ -53,39 +101,8 @@ def ssq_stft2(x, window=None, n_fft=None, win_len=None, hop_len=1, fs=None, t=No
 
     Costs three plan executions (five transforms are needed, six are made), the map and the
     reassignment. The outputs carry no `grad_fn`, whatever `x` requires."""
-    if (isinstance(ssq_freqs, np.ndarray) and
-            infer_scaletype(ssq_freqs)[0] != 'linear'):
-        raise ValueError("`ssq_freqs` must be linearly distributed "
-                         "for `ssq_stft2`")
-    plan, xd, fs, dtype = _stft_setup(x, window, n_fft, win_len, hop_len, fs, t,
-                                      padtype, True, dtype)
-    xd = xd.detach()
-    B = xd.shape[0] if xd.ndim == 2 else 1
-    # the pair the first plan was made with: a cache hit after _stft_setup, which has already
-    # issued the NOLA warnings -- for `g`, the only window they are about
-    n_fft = plan.n_fft
-    if win_len is None:
-        win_len = len(window) if isinstance(window, np.ndarray) else n_fft
-    g, dg, _ = _window_design(window, win_len, n_fft, hop_len, dtype)
-    pair_t, pair_dd = _second_order_windows(g, dg, n_fft, fs)
-    plans = [get_stft_plan(plan.N, n_fft, hop_len, wa, wb, fs, padtype, True, dtype, B)
-             for wa, wb in (pair_t, pair_dd)]
-
-    Sfs = _make_Sfs(plan.rows, fs, dtype)
-    if gamma is None:
-        gamma = 10 * (EPS64 if dtype == 'float64' else EPS32)
-    if ssq_freqs is None:
-        ssq_freqs = Sfs
-    ssq_freqs = np.asarray(ssq_freqs)
-    const = (ssq_freqs[1] - ssq_freqs[0])
-
-    out = plan.execute(xd, want_dSx=True)
-    Sx, Vdg = out['Sx'], out['dSx']
-    out = plans[0].execute(xd, want_dSx=True)
-    Vtg, Vtdg = out['Sx'], out['dSx']
-    Vddg = plans[1].execute(xd, want_dSx=True)['dSx']
-    w = algos.phase_stft2_gpu(Sx, Vdg, Vddg, Vtg, Vtdg, Sfs, gamma, chirp_tol)
-    del Vdg, Vddg, Vtg, Vtdg, out
+    Sx, w, ssq_freqs, Sfs, const = _stft_phase_map('ssq_stft2', x, window, n_fft, win_len, hop_len, fs, t,
+                                                   ssq_freqs, padtype, gamma, chirp_tol, dtype)
     Tx = algos.indexed_sum_onfly(Sx, w, ssq_freqs, const, False, flipud)
     if flipud:
         ssq_freqs = ssq_freqs[::-1]

@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -435,6 +435,58 @@ def time_reassign_gpu(Sx, Vtg, n_fft, hop_len, fs, gamma, rot=None, dmax=None, o
     check(lib.ssq_time_reassign(_CDT[Sx.dtype], _ptr(Sx), _ptr(Vtg), _ptr(rot), _ptr(out), B, rows, n, n_fft, hop_len,
                                 float(fs) / hop_len, int(dmax), float(gamma), stream()))
     return out
+
+
+def _linear_grid(name, v):
+    """`v` as a float64 host vector of two or more evenly spaced values (`name` in the message)."""
+    if hasattr(v, 'detach'):
+        v = v.detach().cpu().numpy()
+    v = np.asarray(v)
+    eps = np.finfo(v.dtype).eps if v.dtype.kind == 'f' else np.finfo(np.float64).eps
+    v = v.astype(np.float64).reshape(-1)
+    if v.size < 2:
+        raise ValueError("`%s` must hold two values or more (got %d)" % (name, v.size))
+    step = v[1] - v[0]
+    if not np.all(np.abs(v - (v[0] + step * np.arange(v.size))) <= 1e3 * eps * np.abs(v).max()):
+        raise ValueError("`%s` must be linearly distributed" % name)
+    return v
+
+
+def multi_squeeze_gpu(Sx, w, Sfs, ssq_freqs, const=1, n_iter=10, interp='linear', flipud=False, out=None, get_w=False):
+    """Multisynchrosqueezing in one kernel (`ssq_multi_squeeze`, include/ssq_hip.h states the definition; DESIGN.md
+    4.5.8). `Sx`: (rows, n) or (B, rows, n) complex; `w`: its phase transform (`phase_stft_gpu`, `phase_stft2_gpu`;
+    ``inf`` = skip), same shape; `Sfs`: (rows,), linear -- row `i` sits at ``f0 + i df``, ``f0 = Sfs[0]``, ``df =
+    Sfs[1] - Sfs[0]`` in float64; `ssq_freqs`: (rows,), the linear grid the bins are taken on; `const` as
+    `indexed_sum_onfly`'s. Per column, every point's frequency ``f = w[i]`` is replaced ``n_iter - 1`` times by `w`
+    at the row `f` points to -- interpolated between the two neighbouring rows (``interp='linear'``) or taken from
+    the nearest (``'nearest'``, the paper's form) --, stopping at a fixed point, outside the rows' range or in front
+    of an ``inf``; the point is then added to the bin of its final frequency, a cell's terms in ascending row order.
+    ``n_iter=1`` is `indexed_sum_onfly`. The iteration runs in float64 for both precisions, the final frequency is
+    rounded once; bit-reproducible. Returns `Tx`, or ``(Tx, w_final)`` with `get_w`."""
+    if interp not in ('linear', 'nearest'):
+        raise ValueError("`interp` must be 'linear' or 'nearest' (got %r)" % (interp,))
+    lib = _lib.load()
+    Sx = to_device(Sx)
+    if Sx.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Sx` must be complex64 or complex128 (got %s)" % Sx.dtype)
+    w = to_device(w, _real_of(Sx.dtype))
+    if Sx.shape != w.shape:
+        raise ValueError("`Sx` and `w` shapes differ")
+    B, rows, n = _shape3(Sx)
+    sfs, grid = _linear_grid('Sfs', Sfs), _linear_grid('ssq_freqs', ssq_freqs)
+    if sfs.size != rows or grid.size != rows:
+        raise ValueError("`Sfs` and `ssq_freqs` must have one entry per row (%d, %d != %d)" % (sfs.size, grid.size, rows))
+    if out is None:
+        out = torch.empty_like(Sx)
+    else:
+        _check_out(out, Sx)
+    wf = torch.empty_like(w) if get_w else None
+    cst, c64 = _const_vector(const, rows, Sx.dtype)
+    kind, p = _grid(ssq_freqs, False)
+    check(lib.ssq_multi_squeeze(_CDT[Sx.dtype], _ptr(Sx), _ptr(w), _ptr(out), _ptr(wf), _ptr(cst), c64, B, rows, n,
+                                float(sfs[0]), float(sfs[1] - sfs[0]), int(n_iter), int(interp == 'linear'), kind, p,
+                                int(bool(flipud)), stream()))
+    return (out, wf) if get_w else out
 
 
 def replace_under_abs(x, ref=None, value=1., replacement=0., parallel=None):

@@ -16,6 +16,8 @@
 //       the tile out once. HBM traffic = read Wx + dWx (or w / bin map) once, write
 //       Tx once -- no read-modify-write, no atomics, deterministic.
 //   accumulate_global_kernel fallback for `na` too large for an LDS tile.
+//   multi_squeeze_kernel     (ssq_multi_squeeze.inl) the ordered accumulate from `w` iterated on itself: a second LDS
+//       slab per wavefront holds its columns of `w`, the iteration is a loop of LDS gathers.
 //   phase_kernel             w = |Im(dWx/Wx)|/2pi (CWT) or |Sfs - ...| (STFT).
 //   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
 //   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
@@ -558,6 +560,9 @@ int launch_accumulate(int dtype, int binsrc, const void* Wx, const void* src, co
     });
 }
 
+// ------------------------------------------------- iterated frequency map + accumulate (ssq_multi_squeeze)
+#include "ssq_multi_squeeze.inl"
+
 // ------------------------------------------------- adjoint of the reassignment
 // The bins are integers, piecewise constant in the data: with them held fixed Tx is linear in Wx and its adjoint is a
 // gather, gWx[i][j] (+)= cst[i] * gTx[k(i, j)][j] (0 below gamma), k from the forward's own point math. Reads run along
@@ -840,7 +845,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 113; }   // 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 114; }   // 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -1017,6 +1022,38 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const vo
     SsqParams sp;
     if (fill_params(sp, grid, params, flipud, 0.0, cst_f64)) return -1;
     return launch_accumulate(dtype, BIN_FROM_W, Wx, w, nullptr, Tx, cst, sp, batch, na, n, nullptr, as_stream(stream));
+}
+
+int ssq_multi_squeeze_max_rows(int dtype) {
+    if (dtype == SSQ_F32) return (int)msst_tile_rows<float>(MSST_WC);
+    return dtype == SSQ_F64 ? (int)msst_tile_rows<double>(MSST_WC) : 0;
+}
+
+int ssq_multi_squeeze(int dtype, const void* Sx, const void* w, void* Tx, void* wf, const void* cst, int cst_f64,
+                      int64_t batch, int64_t rows, int64_t n, double f0, double df, int64_t n_iter, int interp, int grid,
+                      const double* params, int flipud, void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(Sx && w && Tx && cst && params, "ssq_multi_squeeze: null pointer");
+    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "ssq_multi_squeeze: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1",
+                (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(rows <= ssq_multi_squeeze_max_rows(dtype), "ssq_multi_squeeze: %lld rows, at most %d (a 4-column tile of Tx and w in LDS)",
+                (long long)rows, ssq_multi_squeeze_max_rows(dtype));
+    if (check_point_count("ssq_multi_squeeze", batch, rows, n)) return -1;
+    SSQ_REQUIRE(n_iter >= 1 && n_iter <= MSST_MAX_ITER, "ssq_multi_squeeze: n_iter = %lld, 1 .. %lld", (long long)n_iter,
+                (long long)MSST_MAX_ITER);
+    SSQ_REQUIRE(interp == 0 || interp == 1, "ssq_multi_squeeze: interp = %d, 0 (nearest row) or 1 (linear)", interp);
+    SSQ_REQUIRE(df > 0.0 && df <= DBL_MAX && fabs(f0) <= DBL_MAX,
+                "ssq_multi_squeeze: f0 = %g, df = %g: f0 finite, df positive and finite", f0, df);
+    SsqParams sp;
+    if (fill_params(sp, grid, params, flipud, 0.0, cst_f64, "ssq_multi_squeeze")) return -1;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dispatch_bool(cst_f64 != 0, [&](auto c) {
+            constexpr bool C64 = decltype(c)::value && sizeof(T) == 4;    // (as launch_accumulate_b)
+            return launch_multi_squeeze<T, C64>(Sx, w, Tx, wf, cst, sp, batch, rows, n, f0, df, n_iter, interp,
+                                                as_stream(stream));
+        });
+    });
 }
 
 int ssq_replace_under_abs(int dtype, void* w, const void* ref, int64_t count, double value,
