@@ -56,6 +56,7 @@ struct BlockPlan {
     int n_analytic = 0;
     bool own4096 = false;            // float32: the P = 4096 classes' spectra by block_spectra4096_kernel (one launch)
     bool own_big = false;            // ... and short launches of P = 8192 / 16384 blocks by block_spectra_multi_kernel
+    bool paired = true;              // float32: Wx and dWx through each LDS pass as a pair (SSQ_DEBUG_BLOCK_PAIRED=0: one after the other)
     int64_t n_generic = 0;
     // exact (full-length, four-step) path for the rows the blocks cannot take
     bool exact_ok = false;

@@ -17,7 +17,7 @@
 // column index fastest -- so every LDS access of the Stockham passes is
 // conflict-free for G >= 16, and the final outputs (held in registers) go to HBM as
 // runs of G adjacent time samples (128-byte segments for G = 16). Per workgroup:
-// 32 KiB of LDS for the FFT + up to 17 KiB of staged band / twiddle powers; 140-160 VGPRs
+// 32 KiB of LDS for the FFT (34 where the paired transforms pad it) + up to 17 KiB of staged band / twiddle powers; 140-160 VGPRs
 // -> 3 workgroups per CU. HBM traffic: Wx (8 B/pt) + bin map
 // (2 B/pt) written once; the inputs (band of X_b, psi, twiddles: a few KiB per
 // workgroup) come from L2. No intermediate array is ever written.
@@ -151,7 +151,11 @@ struct BlockArgs {
 // in ONE launch, for transforms too small to fill the GPU per class -- shares one set between the classes.
 // NOD: the call asks for Wx alone (a plain cwt: no dWx, no w, no bin map) -- the derivative's inputs, its transform and
 // its share of the epilogue are compiled out (config 1's block rows 27 -> 17 us).
-template <int L, bool LEAN, bool NOD = false>
+// PAIRED: Wx and dWx go through each LDS pass as a pair (lds_ifft2: one set of twiddle loads per pass for both planes, a
+// padded buffer of lds_ifft2_points<L> entries whose pass-1 stores meet no bank conflict; the same bits -- block rows 57.1
+// -> 51.1 us at config 2, profiles/block_paired_passes.txt); false: one transform after the other, as before
+// (SSQ_DEBUG_BLOCK_PAIRED=0, what the tests compare with).
+template <int L, bool LEAN, bool NOD = false, bool PAIRED = true>
 __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqParams& sp, int item_idx,
                                                c32* __restrict__ buf, c32* __restrict__ spow,
                                                c32* __restrict__ wrapf, c32* __restrict__ bandW,
@@ -278,8 +282,12 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     }
     // (twiddles requested ahead of each pass' barrier; nothing has touched `buf` before the first transform:
     // 58.9 -> 56.7 -> 56.2 us at config 2, round 5)
-    lds_ifft<L, true, true>(zw, buf, A.ftw, tid);
-    if constexpr (!NOD) lds_ifft<L, true>(zd, buf, A.ftw, tid);
+    if constexpr (PAIRED && !NOD) {
+        lds_ifft2<L>(zw, zd, buf, A.ftw, tid);
+    } else {
+        lds_ifft<L, true, true>(zw, buf, A.ftw, tid);
+        if constexpr (!NOD) lds_ifft<L, true>(zd, buf, A.ftw, tid);
+    }
 
     // ---- epilogue: unpad, store, phase transform, bin map
     constexpr int NB = PPT / RL, STR = L / RL;
@@ -329,13 +337,13 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     }
 }
 
-template <int L, bool LEAN, bool NOD = false>
+template <int L, bool LEAN, bool NOD = false, bool PAIRED = true>
 __global__ __launch_bounds__(NT) void blockzoom_kernel(BlockArgs A, SsqParams sp) {
-    __shared__ c32 buf[D_POINTS];
+    __shared__ c32 buf[(PAIRED && !NOD) ? lds_ifft2_points<L> : D_POINTS];
     __shared__ c32 spow[FftShape<L>::R1 * FftShape<L>::G];
     __shared__ c32 wrapf[FftShape<L>::G];
     __shared__ c32 bandW[(L <= 512) ? L : 1], bandD[(L <= 512) ? L : 1];
-    blockzoom_body<L, LEAN, NOD>(A, sp, (int)blockIdx.x, buf, spow, wrapf, bandW, bandD);
+    blockzoom_body<L, LEAN, NOD, PAIRED>(A, sp, (int)blockIdx.x, buf, spow, wrapf, bandW, bandD);
 }
 
 // every class of a plan in one launch: workgroup b belongs to the class whose item range holds b
@@ -344,9 +352,9 @@ struct BlockMultiArgs {
     const int4* items[5]; const c32* ftw[5];
     int first[6];                      // first workgroup of class s; first[5] = grid size
 };
-template <bool LEAN, bool NOD = false>
+template <bool LEAN, bool NOD = false, bool PAIRED = true>
 __global__ __launch_bounds__(NT) void blockzoom_multi_kernel(BlockMultiArgs M, SsqParams sp) {
-    __shared__ c32 buf[D_POINTS];
+    __shared__ c32 buf[(PAIRED && !NOD) ? lds_ifft2_points<2048> : D_POINTS];      // (the padded buffer: the same for every L' that pads)
     __shared__ c32 spow[512];          // max R1 * G (16 x 32)
     __shared__ c32 wrapf[32];
     __shared__ c32 bandW[512], bandD[512];
@@ -359,11 +367,11 @@ __global__ __launch_bounds__(NT) void blockzoom_multi_kernel(BlockMultiArgs M, S
     const int it = b - M.first[s];
     // (written out: through fft_switch's lambda the compiler lays this kernel out differently from the code that was measured)
     switch (s) {
-        case 0: blockzoom_body<128, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 1: blockzoom_body<256, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 2: blockzoom_body<512, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 3: blockzoom_body<1024, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        default: blockzoom_body<2048, LEAN, NOD>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 0: blockzoom_body<128, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 1: blockzoom_body<256, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 2: blockzoom_body<512, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 3: blockzoom_body<1024, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        default: blockzoom_body<2048, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
     }
 }
 
@@ -968,15 +976,19 @@ __global__ __launch_bounds__(NT * QMAX) void block_spectra_multi_kernel(BlockSpe
 }
 
 template <int L>
-static int launch_zoom(const BlockArgs& A, const SsqParams& sp, int nsig, hipStream_t stream) {
+static int launch_zoom(const BlockArgs& A, const SsqParams& sp, int nsig, bool paired, hipStream_t stream) {
     if (A.n_items == 0) return 0;
     const dim3 grid((unsigned)A.n_items, (unsigned)nsig);
-    if (A.lean())
-        hipLaunchKernelGGL((blockzoom_kernel<L, true>), grid, dim3(NT), 0, stream, A, sp);
-    else if (A.wx_alone())
+    if (A.wx_alone())
         hipLaunchKernelGGL((blockzoom_kernel<L, false, true>), grid, dim3(NT), 0, stream, A, sp);
-    else
+    else if (A.lean() && paired)
+        hipLaunchKernelGGL((blockzoom_kernel<L, true>), grid, dim3(NT), 0, stream, A, sp);
+    else if (A.lean())
+        hipLaunchKernelGGL((blockzoom_kernel<L, true, false, false>), grid, dim3(NT), 0, stream, A, sp);
+    else if (paired)
         hipLaunchKernelGGL((blockzoom_kernel<L, false>), grid, dim3(NT), 0, stream, A, sp);
+    else
+        hipLaunchKernelGGL((blockzoom_kernel<L, false, false, false>), grid, dim3(NT), 0, stream, A, sp);
     SSQ_LAUNCH_CHECK();
     return 0;
 }
@@ -1046,6 +1058,8 @@ int BlockPlan::create(const ssq_cwt_blocks_desc& d, int dtype_, int64_t M_, int6
     own4096 = dtype == SSQ_F32 && M > 4096 && !(getenv("SSQ_DEBUG_BLOCK_SPECTRA") && !strcmp(getenv("SSQ_DEBUG_BLOCK_SPECTRA"), "rocfft"));
     // (SSQ_DEBUG_BLOCK_SPECTRA=4096: the one-launch kernel for the P = 4096 classes only, as until round 6's second half)
     own_big = own4096 && !(getenv("SSQ_DEBUG_BLOCK_SPECTRA") && !strcmp(getenv("SSQ_DEBUG_BLOCK_SPECTRA"), "4096"));
+    // (SSQ_DEBUG_BLOCK_PAIRED=0: Wx's transform, then dWx's, as before the paired passes -- the same bits, for tests)
+    paired = !(getenv("SSQ_DEBUG_BLOCK_PAIRED") && atoi(getenv("SSQ_DEBUG_BLOCK_PAIRED")) == 0);
     {   // the CU count of the device the plan lives on (the multi-class launch asks how full a launch is)
         int dev = 0; hipDeviceProp_t pr;
         bool lds128 = false;                       // (block_spectra_multi_kernel<4>: 128 KB of LDS; gfx950 has 160 KB)
@@ -1231,12 +1245,16 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
             }
             Mx.first[5] = acc;
             const dim3 grid((unsigned)total, (unsigned)nsig);
-            if (lean)
-                hipLaunchKernelGGL((blockzoom_multi_kernel<true>), grid, dim3(NT), 0, stream, Mx, sp);
-            else if (A.wx_alone())
+            if (A.wx_alone())
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false, true>), grid, dim3(NT), 0, stream, Mx, sp);
-            else
+            else if (lean && paired)
+                hipLaunchKernelGGL((blockzoom_multi_kernel<true>), grid, dim3(NT), 0, stream, Mx, sp);
+            else if (lean)
+                hipLaunchKernelGGL((blockzoom_multi_kernel<true, false, false>), grid, dim3(NT), 0, stream, Mx, sp);
+            else if (paired)
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false>), grid, dim3(NT), 0, stream, Mx, sp);
+            else
+                hipLaunchKernelGGL((blockzoom_multi_kernel<false, false, false>), grid, dim3(NT), 0, stream, Mx, sp);
             SSQ_LAUNCH_CHECK();
             return 0;
         }
@@ -1244,7 +1262,7 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
     for (int s = 0; s < 5; ++s) {                  // the plan's item lists: L' = 128 << s
         A.items = (const int4*)items[s]; A.n_items = limit ? limit[s] : n_items[s];
         A.ftw = (const c32*)ftw + ftw_off[s];
-        const int rc = fft_dispatch<128, 2048>(128 << s, [&](auto len) { return launch_zoom<decltype(len)::value>(A, sp, nsig, stream); });
+        const int rc = fft_dispatch<128, 2048>(128 << s, [&](auto len) { return launch_zoom<decltype(len)::value>(A, sp, nsig, paired, stream); });
         if (rc) return rc;
     }
     return 0;

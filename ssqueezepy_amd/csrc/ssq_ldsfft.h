@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "ssq_common.h"
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace ssq {
@@ -259,6 +260,135 @@ __device__ __forceinline__ void lds_ifft(cx<R> (&v)[PPT], cx<R>* __restrict__ bu
             for (int k = 0; k < R3; ++k) v[it * R3 + k] = t[k];
         }
     }
+}
+
+// Two transforms of the same shape as a pair (float32; the block rows' Wx and dWx): `lds_ifft<L, true, true>(vw)` and then
+// `lds_ifft<L, true>(vd)`, with each pass' twiddles loaded once and its LDS addresses formed once for both planes. Per
+// plane the butterflies, their operands and their order are lds_ifft's, so every output bit is. Both planes go through
+// the one buffer inside a pass -- write W, barrier, read W, barrier, write D, barrier, read D -- which takes the seven
+// barriers the two calls take (three passes; three for two passes), and one plane's butterflies are issued while the
+// other plane's points are on their way through the buffer: behind its write and ahead of the barrier that follows.
+// As there: `buf` holds nothing a wavefront may still be reading on entry, and the twiddles of passes 2 and 3 are
+// requested ahead of a barrier in front of them.
+// The buffer is padded: point i sits at i + 2 (i / 32) when a workgroup has G <= 8 columns (`lds_ifft2_points<L>`
+// elements instead of 4096). Unpadded, the 16 lanes a `ds_write_b64` serves together write pass 1's outputs R1 G
+// points apart (G = 2: 256 B, eight lanes on each bank; G = 4: four) -- more than half of the kernel's LDS cycles went
+// to those conflicts; padded, every access of the passes is conflict-free at G <= 4. All strides stay compile-time offsets.
+constexpr int lds_ifft2_pad(int L) { return (FftGeom<float>::D / L <= 8) ? 2 : 0; }
+template <int L> constexpr int lds_ifft2_points = FftGeom<float>::D + lds_ifft2_pad(L) * (FftGeom<float>::D / 32);
+template <int L>
+__device__ __forceinline__ void lds_ifft2(cx<float> (&vw)[PPT], cx<float> (&vd)[PPT], cx<float>* __restrict__ buf,
+                                          const cx<float>* __restrict__ ftw, int tid) {
+    using C = cx<float>;
+    constexpr int NT = FftGeom<float>::NT, G = NT * PPT / L;
+    constexpr int R1 = FftShape<L>::R1, R2 = FftShape<L>::R2, R3 = FftShape<L>::R3;
+    constexpr bool three = (R3 > 1);
+    constexpr int NB1 = PPT / R1, NB2 = PPT / R2, STR2 = L / R2;
+    // slot of point i, and of a compile-time stride added to it (a multiple of 32 points, or one that stays inside i's 32)
+    constexpr int PADE = lds_ifft2_pad(L);
+    static_assert(L >= 128 && (R1 * G) % 32 == 0 && 32 % (G < 32 ? G : 32) == 0, "lds_ifft2: strides and the padding");
+    auto slot = [](int i) { return i + PADE * (i >> 5); };
+#define SSQ_PADDED(o) ((o) + PADE * ((o) >> 5))
+    // butterflies of one pass on one plane, in place: radix RR, twiddles tw[it][1 .. RR-1] (none: pass 1)
+    auto butterflies = [](auto rr, C (&v)[PPT], auto* tw) {
+        constexpr int RR = decltype(rr)::value;
+#pragma unroll
+        for (int it = 0; it < PPT / RR; ++it) {
+            C t[RR];
+            t[0] = v[it * RR];
+#pragma unroll
+            for (int k = 1; k < RR; ++k) {
+                if constexpr (std::is_same_v<decltype(tw), std::nullptr_t*>) t[k] = v[it * RR + k];
+                else t[k] = cmul_v(v[it * RR + k], tw[it][k]);
+            }
+            Dft<RR>::run(t);
+#pragma unroll
+            for (int k = 0; k < RR; ++k) v[it * RR + k] = t[k];
+        }
+    };
+    constexpr std::nullptr_t* none = nullptr;
+    int w1[NB1], r2[NB2];                          // first slot a pass-1 butterfly writes, a pass-2 butterfly reads
+#pragma unroll
+    for (int it = 0; it < NB1; ++it) { const int idx = tid + it * NT; w1[it] = slot((idx / G) * R1 * G + idx % G); }
+#pragma unroll
+    for (int it = 0; it < NB2; ++it) { const int idx = tid + it * NT; r2[it] = slot(idx); }
+    auto put1 = [&](const C (&v)[PPT]) {
+#pragma unroll
+        for (int it = 0; it < NB1; ++it)
+#pragma unroll
+            for (int k = 0; k < R1; ++k) buf[w1[it] + SSQ_PADDED(k * G)] = v[it * R1 + k];
+    };
+    auto get2 = [&](C (&v)[PPT]) {
+#pragma unroll
+        for (int it = 0; it < NB2; ++it)
+#pragma unroll
+            for (int k = 0; k < R2; ++k) v[it * R2 + k] = buf[r2[it] + SSQ_PADDED(k * STR2 * G)];
+    };
+    // ---- pass 1 (Ns = 1) in registers; W out, D's butterflies on the way to the barrier
+    butterflies(FftLen<R1>{}, vw, none);
+    put1(vw);
+    C tw2[NB2][R2];
+#pragma unroll
+    for (int it = 0; it < NB2; ++it) {
+        const int kk = ((tid + it * NT) / G) % R1;
+        constexpr int TW = L / (R1 * R2);
+#pragma unroll
+        for (int k = 1; k < R2; ++k) tw2[it][k] = ftw[kk * k * TW];
+    }
+    butterflies(FftLen<R1>{}, vd, none);
+    __syncthreads();
+    get2(vw);
+    __syncthreads();
+    put1(vd);
+    // ---- pass 2 (Ns = R1): W's butterflies while D goes through the buffer
+    butterflies(FftLen<R2>{}, vw, tw2);
+    __syncthreads();
+    get2(vd);
+    if constexpr (!three) {
+        butterflies(FftLen<R2>{}, vd, tw2);
+    } else {
+        constexpr int NB3 = PPT / R3, STR3 = L / R3;
+        int w2[NB2], r3[NB3];
+#pragma unroll
+        for (int it = 0; it < NB2; ++it) {
+            const int idx = tid + it * NT, g = idx % G, u = idx / G;
+            w2[it] = slot(((u / R1) * R1 * R2 + u % R1) * G + g);
+        }
+#pragma unroll
+        for (int it = 0; it < NB3; ++it) { const int idx = tid + it * NT; r3[it] = slot(idx); }
+        auto put2 = [&](const C (&v)[PPT]) {
+#pragma unroll
+            for (int it = 0; it < NB2; ++it)
+#pragma unroll
+                for (int k = 0; k < R2; ++k) buf[w2[it] + SSQ_PADDED(k * R1 * G)] = v[it * R2 + k];
+        };
+        auto get3 = [&](C (&v)[PPT]) {
+#pragma unroll
+            for (int it = 0; it < NB3; ++it)
+#pragma unroll
+                for (int k = 0; k < R3; ++k) v[it * R3 + k] = buf[r3[it] + SSQ_PADDED(k * STR3 * G)];
+        };
+        __syncthreads();                           // in place: every read of D before any write
+        put2(vw);
+        butterflies(FftLen<R2>{}, vd, tw2);
+        C tw3[NB3][R3];
+#pragma unroll
+        for (int it = 0; it < NB3; ++it) {
+            const int kk = ((tid + it * NT) / G) % (R1 * R2);
+#pragma unroll
+            for (int k = 1; k < R3; ++k) tw3[it][k] = ftw[kk * k];
+        }
+        __syncthreads();
+        get3(vw);
+        __syncthreads();
+        put2(vd);
+        // ---- pass 3 (Ns = R1 R2)
+        butterflies(FftLen<R3>{}, vw, tw3);
+        __syncthreads();
+        get3(vd);
+        butterflies(FftLen<R3>{}, vd, tw3);
+    }
+#undef SSQ_PADDED
 }
 
 }  // namespace ssq
