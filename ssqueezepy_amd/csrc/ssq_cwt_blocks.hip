@@ -17,8 +17,8 @@
 // column index fastest -- so every LDS access of the Stockham passes is
 // conflict-free for G >= 16, and the final outputs (held in registers) go to HBM as
 // runs of G adjacent time samples (128-byte segments for G = 16). Per workgroup:
-// 32 KiB of LDS for the FFT (34 where the paired transforms pad it) + up to 17 KiB of staged band / twiddle powers; 140-160 VGPRs
-// -> 3 workgroups per CU. HBM traffic: Wx (8 B/pt) + bin map
+// 32 KiB of LDS for the FFT (34 where the paired transforms pad it; the staged band sits inside it until pass 1) + up to
+// 4 KiB of twiddle powers; 128 VGPRs -> 4 workgroups per CU for the lean multi-class kernel, 140-160 -> 3 for the others. HBM traffic: Wx (8 B/pt) + bin map
 // (2 B/pt) written once; the inputs (band of X_b, psi, twiddles: a few KiB per
 // workgroup) come from L2. No intermediate array is ever written.
 //
@@ -155,7 +155,11 @@ struct BlockArgs {
 // padded buffer of lds_ifft2_points<L> entries whose pass-1 stores meet no bank conflict; the same bits -- block rows 57.1
 // -> 51.1 us at config 2, profiles/block_paired_passes.txt); false: one transform after the other, as before
 // (SSQ_DEBUG_BLOCK_PAIRED=0, what the tests compare with).
-template <int L, bool LEAN, bool NOD = false, bool PAIRED = true>
+// BAND (paired kernels only): the band is staged once per workgroup in `buf`, which the transform does not touch before
+// pass 1's first store (see the prologue); false: bandW / bandD arrays of their own for L' <= 512 and three global loads
+// per point for L' >= 1024, as before (SSQ_DEBUG_BLOCK_BAND=0 -- the same bits, what the tests compare with).
+struct __align__(16) BandRec { c32 b; float mm, pad; };     // psi X / P and pxi / dt of one band element: one 16-byte LDS access
+template <int L, bool LEAN, bool NOD = false, bool PAIRED = true, bool BAND = PAIRED && !NOD>
 __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqParams& sp, int item_idx,
                                                c32* __restrict__ buf, c32* __restrict__ spow,
                                                c32* __restrict__ wrapf, c32* __restrict__ bandW,
@@ -186,7 +190,20 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     // The band itself (psi X / P and its derivative multiple) is the same for all G
     // columns of the workgroup: for the small transforms it is formed once per
     // workgroup in LDS instead of once per point from global memory (bandW, bandD: L entries).
+    // With BAND the staged band lives in the transform buffer, idle until pass 1's first store (lds_ifft2<L, false> takes a
+    // barrier there). L' <= 512: bandW and bandD are its first 2 L' entries. L' >= 1024: a work-item loads L' / 256 band
+    // elements at consecutive addresses -- not 16 per point, the same ones in each of the G lanes of a column group
+    // -- forms psi X / P and pxi / dt once per element and stores them as a 16-byte record at the element's FFT slot
+    // (klo + off) mod L'; behind the barrier it reads its 16 records at u + k STR, compile-time offsets from one address
+    // (consecutive lanes: consecutive records, the G lanes of a group the same one: conflict-free), and the products
+    // with the column twiddle and with pxi / dt are the ones made before, on the same operands in the same order.
+    static_assert(!BAND || (PAIRED && !NOD), "blockzoom_body: the band goes through the paired transform's buffer");
     constexpr bool STAGE = (L <= 512);
+    constexpr bool BAND_REC = BAND && !STAGE;
+    static_assert(sizeof(BandRec) == 2 * sizeof(c32) && 2 * L <= lds_ifft2_points<L>, "either form of the band: 2 L' entries of buf");
+    BandRec* __restrict__ const rec = reinterpret_cast<BandRec*>(buf);
+    c32* const bW = BAND ? buf : bandW;
+    c32* const bD = BAND ? buf + L : bandD;
     const float invP = 1.0f / (float)P;             // exact (P is a power of two)
     // Round 5, the large classes (no band staging): every global load of the prologue -- the staged twiddles, the
     // work-item's first column twiddle and the band's three loads per point -- is issued up front, into registers,
@@ -194,8 +211,9 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     // staging instead of starting behind its barrier. Block rows 69.4 -> 64.0 us (an ablation without the band's
     // loads runs at 51.8: profiles/r5_ab_history.txt).
     constexpr bool EARLY = !STAGE && (R1 * G <= NT);
-    float e_p[EARLY ? PPT : 1], e_m[EARLY ? PPT : 1];
-    c32 e_X[EARLY ? PPT : 1], e_cw[EARLY ? PPT / R1 : 1];
+    constexpr bool PERPT = EARLY && !BAND_REC;      // the band's loads per point
+    float e_p[PERPT ? PPT : 1], e_m[PERPT ? PPT : 1];
+    c32 e_X[PERPT ? PPT : 1], e_cw[EARLY ? PPT / R1 : 1];
     if constexpr (EARLY) {
         constexpr int NBe = PPT / R1, STR = L / R1;
         c32 st_v = {0.f, 0.f}, st_w = {0.f, 0.f};
@@ -209,13 +227,36 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
             const int idx = tid + it * NT, g = idx % G, u = idx / G;
             const int off0 = (u - r.klo) & (L - 1);
             e_cw[it] = ctw[((unsigned)(r.klo + off0) * (unsigned)(c0 + g)) & (unsigned)(P - 1)];
+            if constexpr (PERPT) {
 #pragma unroll
-            for (int k = 0; k < R1; ++k) {
-                const int off = (off0 + k * STR) & (L - 1);
-                const bool in = off < r.KP;              // slots past the band: zeros
-                e_p[it * R1 + k] = in ? psi[off] : 0.f;
-                e_X[it * R1 + k] = in ? xb[r.klo + off] : c32{0.f, 0.f};
-                e_m[it * R1 + k] = in ? pxi[off] : 0.f;
+                for (int k = 0; k < R1; ++k) {
+                    const int off = (off0 + k * STR) & (L - 1);
+                    const bool in = off < r.KP;              // slots past the band: zeros
+                    e_p[it * R1 + k] = in ? psi[off] : 0.f;
+                    e_X[it * R1 + k] = in ? xb[r.klo + off] : c32{0.f, 0.f};
+                    e_m[it * R1 + k] = in ? pxi[off] : 0.f;
+                }
+            }
+        }
+        if constexpr (BAND_REC) {
+            constexpr int NE = L / NT;
+            float s_p[NE], s_m[NE]; c32 s_X[NE];
+#pragma unroll
+            for (int i = 0; i < NE; ++i) {
+                const int off = tid + i * NT;
+                const bool in = off < r.KP;                  // slots past the band: zeros, through the same products
+                s_p[i] = in ? psi[off] : 0.f;
+                s_X[i] = in ? xb[r.klo + off] : c32{0.f, 0.f};
+                s_m[i] = in ? pxi[off] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < NE; ++i) {
+                const float p = s_p[i] * invP;
+                BandRec b;
+                b.b = {p * s_X[i].x, p * s_X[i].y};
+                b.mm = s_m[i] * A.inv_dt;
+                b.pad = 0.f;
+                rec[(r.klo + tid + i * NT) & (L - 1)] = b;
             }
         }
         if (tid < R1 * G) spow[tid] = st_v;
@@ -240,7 +281,7 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
                     const float mm = pxi[off] * A.inv_dt;   // 1j*xi/dt, xi as the reference stores it
                     d = {-(b.y * mm), b.x * mm};
                 }
-                bandW[off] = b; bandD[off] = d;
+                bW[off] = b; bD[off] = d;
             }
         }
     }
@@ -264,8 +305,14 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
                     // zero-padded band: slots past KP hold zeros, no branch needed
                     c32 cw = (k == 0) ? cw0 : cmul_v(cw0, spow[k * G + g]);
                     if (offu >= L) cw = cmul_v(cw, wf);
-                    z = cmul_v(bandW[off], cw);
-                    dz = cmul_v(bandD[off], cw);
+                    z = cmul_v(bW[off], cw);
+                    dz = cmul_v(bD[off], cw);
+                } else if constexpr (BAND_REC) {
+                    const BandRec br = rec[u + k * STR];     // FFT slot q = u + k STR holds band element `off`
+                    c32 cw = (k == 0) ? cw0 : cmul_v(cw0, spow[k * G + g]);
+                    if (offu >= L) cw = cmul_v(cw, wf);
+                    z = cmul_v(br.b, cw);
+                    dz = {-(z.y * br.mm), z.x * br.mm};
                 } else if (EARLY || off < r.KP) {            // (EARLY: slots past the band were loaded as zeros)
                     const float p = (EARLY ? e_p[EARLY ? it * R1 + k : 0] : psi[off]) * invP;
                     const c32 X = EARLY ? e_X[EARLY ? it * R1 + k : 0] : xb[r.klo + off];
@@ -282,8 +329,9 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     }
     // (twiddles requested ahead of each pass' barrier; nothing has touched `buf` before the first transform:
     // 58.9 -> 56.7 -> 56.2 us at config 2, round 5)
+    // (... with BAND it holds the band, and the paired transform waits for every wavefront's reads of it)
     if constexpr (PAIRED && !NOD) {
-        lds_ifft2<L>(zw, zd, buf, A.ftw, tid);
+        lds_ifft2<L, !BAND>(zw, zd, buf, A.ftw, tid);
     } else {
         lds_ifft<L, true, true>(zw, buf, A.ftw, tid);
         if constexpr (!NOD) lds_ifft<L, true>(zd, buf, A.ftw, tid);
@@ -337,13 +385,13 @@ __device__ __forceinline__ void blockzoom_body(const BlockArgs& A, const SsqPara
     }
 }
 
-template <int L, bool LEAN, bool NOD = false, bool PAIRED = true>
+template <int L, bool LEAN, bool NOD = false, bool PAIRED = true, bool BAND = PAIRED && !NOD>
 __global__ __launch_bounds__(NT) void blockzoom_kernel(BlockArgs A, SsqParams sp) {
-    __shared__ c32 buf[(PAIRED && !NOD) ? lds_ifft2_points<L> : D_POINTS];
+    __shared__ __align__(16) c32 buf[(PAIRED && !NOD) ? lds_ifft2_points<L> : D_POINTS];
     __shared__ c32 spow[FftShape<L>::R1 * FftShape<L>::G];
     __shared__ c32 wrapf[FftShape<L>::G];
-    __shared__ c32 bandW[(L <= 512) ? L : 1], bandD[(L <= 512) ? L : 1];
-    blockzoom_body<L, LEAN, NOD, PAIRED>(A, sp, (int)blockIdx.x, buf, spow, wrapf, bandW, bandD);
+    __shared__ c32 bandW[(L <= 512 && !BAND) ? L : 1], bandD[(L <= 512 && !BAND) ? L : 1];
+    blockzoom_body<L, LEAN, NOD, PAIRED, BAND>(A, sp, (int)blockIdx.x, buf, spow, wrapf, bandW, bandD);
 }
 
 // every class of a plan in one launch: workgroup b belongs to the class whose item range holds b
@@ -352,12 +400,18 @@ struct BlockMultiArgs {
     const int4* items[5]; const c32* ftw[5];
     int first[6];                      // first workgroup of class s; first[5] = grid size
 };
-template <bool LEAN, bool NOD = false, bool PAIRED = true>
-__global__ __launch_bounds__(NT) void blockzoom_multi_kernel(BlockMultiArgs M, SsqParams sp) {
-    __shared__ c32 buf[(PAIRED && !NOD) ? lds_ifft2_points<2048> : D_POINTS];      // (the padded buffer: the same for every L' that pads)
+// With the band inside `buf` four workgroups fit a CU's 160 KiB of LDS (4 x 39 168 B). The lean build is held to the 128
+// registers that four wavefronts per SIMD leave each of them (left alone it takes 138, which is three): block rows
+// 51.2 -> 46.7 us at config 2, every run below every run of the parent (profiles/block_band_staged.txt; at three
+// workgroups per CU the staged band alone does not separate from the parent). 20 registers spill. The other builds stay
+// as the compiler sizes them (the full build would spill 65).
+template <bool LEAN, bool NOD = false, bool PAIRED = true, bool BAND = PAIRED && !NOD>
+__global__ __launch_bounds__(NT) SSQ_WAVES_PER_EU((LEAN && BAND) ? 4 : 1, (LEAN && BAND) ? 4 : 8)
+void blockzoom_multi_kernel(BlockMultiArgs M, SsqParams sp) {
+    __shared__ __align__(16) c32 buf[(PAIRED && !NOD) ? lds_ifft2_points<2048> : D_POINTS];      // (the padded buffer: the same for every L' that pads)
     __shared__ c32 spow[512];          // max R1 * G (16 x 32)
     __shared__ c32 wrapf[32];
-    __shared__ c32 bandW[512], bandD[512];
+    __shared__ c32 bandW[BAND ? 1 : 512], bandD[BAND ? 1 : 512];   // (BAND: inside buf -- 39 KB of LDS instead of 47)
     const int b = (int)blockIdx.x;
     int s = 0;
 #pragma unroll
@@ -367,11 +421,11 @@ __global__ __launch_bounds__(NT) void blockzoom_multi_kernel(BlockMultiArgs M, S
     const int it = b - M.first[s];
     // (written out: through fft_switch's lambda the compiler lays this kernel out differently from the code that was measured)
     switch (s) {
-        case 0: blockzoom_body<128, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 1: blockzoom_body<256, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 2: blockzoom_body<512, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        case 3: blockzoom_body<1024, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
-        default: blockzoom_body<2048, LEAN, NOD, PAIRED>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 0: blockzoom_body<128, LEAN, NOD, PAIRED, BAND>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 1: blockzoom_body<256, LEAN, NOD, PAIRED, BAND>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 2: blockzoom_body<512, LEAN, NOD, PAIRED, BAND>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        case 3: blockzoom_body<1024, LEAN, NOD, PAIRED, BAND>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
+        default: blockzoom_body<2048, LEAN, NOD, PAIRED, BAND>(A, sp, it, buf, spow, wrapf, bandW, bandD); break;
     }
 }
 
@@ -976,17 +1030,21 @@ __global__ __launch_bounds__(NT * QMAX) void block_spectra_multi_kernel(BlockSpe
 }
 
 template <int L>
-static int launch_zoom(const BlockArgs& A, const SsqParams& sp, int nsig, bool paired, hipStream_t stream) {
+static int launch_zoom(const BlockArgs& A, const SsqParams& sp, int nsig, bool paired, bool band, hipStream_t stream) {
     if (A.n_items == 0) return 0;
     const dim3 grid((unsigned)A.n_items, (unsigned)nsig);
     if (A.wx_alone())
         hipLaunchKernelGGL((blockzoom_kernel<L, false, true>), grid, dim3(NT), 0, stream, A, sp);
-    else if (A.lean() && paired)
+    else if (A.lean() && paired && band)
         hipLaunchKernelGGL((blockzoom_kernel<L, true>), grid, dim3(NT), 0, stream, A, sp);
+    else if (A.lean() && paired)
+        hipLaunchKernelGGL((blockzoom_kernel<L, true, false, true, false>), grid, dim3(NT), 0, stream, A, sp);
     else if (A.lean())
         hipLaunchKernelGGL((blockzoom_kernel<L, true, false, false>), grid, dim3(NT), 0, stream, A, sp);
-    else if (paired)
+    else if (paired && band)
         hipLaunchKernelGGL((blockzoom_kernel<L, false>), grid, dim3(NT), 0, stream, A, sp);
+    else if (paired)
+        hipLaunchKernelGGL((blockzoom_kernel<L, false, false, true, false>), grid, dim3(NT), 0, stream, A, sp);
     else
         hipLaunchKernelGGL((blockzoom_kernel<L, false, false, false>), grid, dim3(NT), 0, stream, A, sp);
     SSQ_LAUNCH_CHECK();
@@ -1060,6 +1118,8 @@ int BlockPlan::create(const ssq_cwt_blocks_desc& d, int dtype_, int64_t M_, int6
     own_big = own4096 && !(getenv("SSQ_DEBUG_BLOCK_SPECTRA") && !strcmp(getenv("SSQ_DEBUG_BLOCK_SPECTRA"), "4096"));
     // (SSQ_DEBUG_BLOCK_PAIRED=0: Wx's transform, then dWx's, as before the paired passes -- the same bits, for tests)
     paired = !(getenv("SSQ_DEBUG_BLOCK_PAIRED") && atoi(getenv("SSQ_DEBUG_BLOCK_PAIRED")) == 0);
+    // (SSQ_DEBUG_BLOCK_BAND=0: the paired kernels with the band outside the transform buffer, as before -- the same bits, for tests)
+    band = !(getenv("SSQ_DEBUG_BLOCK_BAND") && atoi(getenv("SSQ_DEBUG_BLOCK_BAND")) == 0);
     {   // the CU count of the device the plan lives on (the multi-class launch asks how full a launch is)
         int dev = 0; hipDeviceProp_t pr;
         bool lds128 = false;                       // (block_spectra_multi_kernel<4>: 128 KB of LDS; gfx950 has 160 KB)
@@ -1247,12 +1307,16 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
             const dim3 grid((unsigned)total, (unsigned)nsig);
             if (A.wx_alone())
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false, true>), grid, dim3(NT), 0, stream, Mx, sp);
-            else if (lean && paired)
+            else if (lean && paired && band)
                 hipLaunchKernelGGL((blockzoom_multi_kernel<true>), grid, dim3(NT), 0, stream, Mx, sp);
+            else if (lean && paired)
+                hipLaunchKernelGGL((blockzoom_multi_kernel<true, false, true, false>), grid, dim3(NT), 0, stream, Mx, sp);
             else if (lean)
                 hipLaunchKernelGGL((blockzoom_multi_kernel<true, false, false>), grid, dim3(NT), 0, stream, Mx, sp);
-            else if (paired)
+            else if (paired && band)
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false>), grid, dim3(NT), 0, stream, Mx, sp);
+            else if (paired)
+                hipLaunchKernelGGL((blockzoom_multi_kernel<false, false, true, false>), grid, dim3(NT), 0, stream, Mx, sp);
             else
                 hipLaunchKernelGGL((blockzoom_multi_kernel<false, false, false>), grid, dim3(NT), 0, stream, Mx, sp);
             SSQ_LAUNCH_CHECK();
@@ -1262,7 +1326,7 @@ int BlockPlan::run(int sig, int nsig, float* Wx, float* dWx, float* w, unsigned 
     for (int s = 0; s < 5; ++s) {                  // the plan's item lists: L' = 128 << s
         A.items = (const int4*)items[s]; A.n_items = limit ? limit[s] : n_items[s];
         A.ftw = (const c32*)ftw + ftw_off[s];
-        const int rc = fft_dispatch<128, 2048>(128 << s, [&](auto len) { return launch_zoom<decltype(len)::value>(A, sp, nsig, paired, stream); });
+        const int rc = fft_dispatch<128, 2048>(128 << s, [&](auto len) { return launch_zoom<decltype(len)::value>(A, sp, nsig, paired, band, stream); });
         if (rc) return rc;
     }
     return 0;

@@ -268,15 +268,16 @@ __device__ __forceinline__ void lds_ifft(cx<R> (&v)[PPT], cx<R>* __restrict__ bu
 // the one buffer inside a pass -- write W, barrier, read W, barrier, write D, barrier, read D -- which takes the seven
 // barriers the two calls take (three passes; three for two passes), and one plane's butterflies are issued while the
 // other plane's points are on their way through the buffer: behind its write and ahead of the barrier that follows.
-// As there: `buf` holds nothing a wavefront may still be reading on entry, and the twiddles of passes 2 and 3 are
-// requested ahead of a barrier in front of them.
+// As there: the twiddles of passes 2 and 3 are requested ahead of a barrier in front of them. FRESH: `buf` holds nothing
+// a wavefront may still be reading on entry; false (the block rows keep their staged band in it): one more barrier, behind
+// pass 1's butterflies of W and in front of the pass' first store.
 // The buffer is padded: point i sits at i + 2 (i / 32) when a workgroup has G <= 8 columns (`lds_ifft2_points<L>`
 // elements instead of 4096). Unpadded, the 16 lanes a `ds_write_b64` serves together write pass 1's outputs R1 G
 // points apart (G = 2: 256 B, eight lanes on each bank; G = 4: four) -- more than half of the kernel's LDS cycles went
 // to those conflicts; padded, every access of the passes is conflict-free at G <= 4. All strides stay compile-time offsets.
 constexpr int lds_ifft2_pad(int L) { return (FftGeom<float>::D / L <= 8) ? 2 : 0; }
 template <int L> constexpr int lds_ifft2_points = FftGeom<float>::D + lds_ifft2_pad(L) * (FftGeom<float>::D / 32);
-template <int L>
+template <int L, bool FRESH = true>
 __device__ __forceinline__ void lds_ifft2(cx<float> (&vw)[PPT], cx<float> (&vd)[PPT], cx<float>* __restrict__ buf,
                                           const cx<float>* __restrict__ ftw, int tid) {
     using C = cx<float>;
@@ -326,6 +327,7 @@ __device__ __forceinline__ void lds_ifft2(cx<float> (&vw)[PPT], cx<float> (&vd)[
     };
     // ---- pass 1 (Ns = 1) in registers; W out, D's butterflies on the way to the barrier
     butterflies(FftLen<R1>{}, vw, none);
+    if constexpr (!FRESH) __syncthreads();         // every wavefront is through with what `buf` held
     put1(vw);
     C tw2[NB2][R2];
 #pragma unroll
