@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 114 (113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 115 (114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -232,6 +232,63 @@ int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* ro
 /* The destination columns a wavefront of ssq_time_reassign owns, and the largest dmax the entry accepts. */
 int ssq_time_reassign_segment(void);
 int ssq_time_reassign_max_dmax(void);
+
+/* The reassigned spectrogram (ABI 115; Kodera, Gendrin, de Villedary 1978; Auger, Flandrin 1995; DESIGN.md section
+ * 4.5.9): the energy of every point of an STFT moves along both axes at once, to its instantaneous frequency (rows) and
+ * its group delay (columns).
+ *   Sx, dSx, Vtg (batch, rows, n) complex `dtype`, device: the STFT with window g, with its derivative g' and with
+ *           tau g (tau the window's time axis in seconds, 0 at the centre). dSx may be NULL when the frequency axis is
+ *           off, Vtg when dmax = 0
+ *   Rx      (batch, rows, n) REAL `dtype`; overwritten
+ *   acc     (batch, rows, n) uint64 and peak (batch,) uint64: caller-owned scratch, overwritten; readable afterwards
+ *           (the fixed-point sums and the bits of the largest kept energy of every signal)
+ *   fs, cols_per_second = fs / hop_len;  kmax, dmax: the largest displacement kept, in rows and in columns
+ *   flags   SSQ_REASSIGN2D_FREQ: the frequency axis is on. dmax = 0 turns the time axis off.
+ *           SSQ_REASSIGN2D_NO_WINDOW: every term goes to `acc` with a global atomic, none through the LDS window --
+ *           the same bits, slower; for measurements
+ * Evaluated in float64 for both dtypes (float32 planes are promoted per point), basic IEEE operations only, no
+ * contraction. Per signal b, with df = fs / n_fft, for every point of row k, column c:
+ *       gr, gi = Sx[b,k,c];  e = gr*gr + gi*gi
+ *       kept   = not (|Sx| < gamma) and e finite        |Sx| as ssq_time_reassign takes it
+ *       m  = rint(((-(di*gr - dr*gi) / e) / 6.283185307179586) / df)    dr, di = dSx[b,k,c]; rows; round half to even
+ *            0 when the frequency axis is off
+ *       d  = rint(((tr*gr + ti*gi) / e) * cols_per_second)              tr, ti = Vtg[b,k,c]; columns
+ *            0 when dmax = 0
+ *       k2 = |k + m|                                    reflected at row 0
+ *       dropped: not (|m| <= kmax), k2 > rows - 1, not (|d| <= dmax), c + d outside [0, n)    (NaN included)
+ *       Rx[b, k2, c + d] += e
+ * The sum of a cell is taken in fixed point, so that it does not depend on the order of the additions -- on the grid, the
+ * tiling or the schedule -- and is exact:
+ *       emax = the largest e over the kept points of signal b (dropped ones included);  peak[b] = its bits, 0 if none
+ *       ex   = frexp(emax)'s exponent:  emax = f 2^ex, 1/2 <= f < 1
+ *       C    = rows * min(2 dmax + 1, n), the most terms a cell can receive;  H = bit_length(C)
+ *       sh   = 62 - H - ex
+ *       q    = (uint64) ldexp(e, sh), truncated: the term of a point that lands
+ *       acc[b, k2, c2] = the uint64 sum of its terms, below 2^62 by construction
+ *       Rx   = (dtype) ldexp((double) acc, -sh)
+ * A signal without a kept point gives zeros. Every term loses less than 2^-sh to the truncation: a cell that received t
+ * terms lies below the exact sum by less than t 2^-sh (2^-sh <= emax 2^(H - 61), so less than emax 2^(2H - 61) for any
+ * cell), before the one rounding to `dtype` (an acc beyond 2^53 rounds once to float64 first). Bit-reproducible
+ * from call to call; `batch` signals in one call equal `batch` calls of one signal bit for bit. Three launches and two
+ * clears on `stream`, no host synchronisation: the peak (fetch_max on the double's bits), the scatter (a workgroup per
+ * tile of ssq_reassign2d_tile(0) x ssq_reassign2d_tile(1) sources adds into an LDS window that is
+ * ssq_reassign2d_tile(2) rows and ssq_reassign2d_tile(3) columns wider on every side; terms outside it are global 64-bit
+ * integer atomics; at the tile's end the window's non-zero cells are added to `acc`, a wavefront per line of 64 cells, in
+ * runs of neighbouring cells) and the conversion.
+ * Planes that do not start on a 16-byte boundary take an element-load instance. Refused, with nothing written and a
+ * message that begins with the entry's name: a null Sx, Rx, acc or peak, a null dSx with the frequency axis on, a null
+ * Vtg with dmax > 0; batch, rows or n < 1; batch rows n >= 2^32; n_fft < 1 (or >= 2^31) or hop_len < 1; rows > n_fft;
+ * dmax < 0 or > ssq_time_reassign_max_dmax(); kmax < 0; fs or cols_per_second not finite or <= 0; gamma < 0 or NaN;
+ * rows * min(2 dmax + 1, n) >= 2^40; unknown flags. No counterpart in the reference. */
+#define SSQ_REASSIGN2D_FREQ 1
+#define SSQ_REASSIGN2D_NO_WINDOW 2
+int ssq_reassign2d(int dtype, const void* Sx, const void* dSx, const void* Vtg, void* Rx, void* acc, void* peak,
+                   int64_t batch, int64_t rows, int64_t n, int64_t n_fft, int64_t hop_len, double fs,
+                   double cols_per_second, int64_t kmax, int64_t dmax, double gamma, int flags, void* stream);
+/* The scatter's sizes: which = 0, 1: the rows and columns of a tile of sources; 2, 3: the rows and columns of the
+ * window's halo on every side; 4: the most workgroups of the windowed scatter (with more tiles than that a workgroup
+ * walks several); anything else: 0. */
+int ssq_reassign2d_tile(int which);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('SSQ_HIP_LIB') or os.path.join(HERE, 'libssq_hip.so')
 
 F32, F64 = 0, 1
 GRID_LOG, GRID_LOG_PIECEWISE, GRID_LIN = 0, 1, 2
+REASSIGN2D_FREQ, REASSIGN2D_NO_WINDOW = 1, 2
 PAD = {None: -1, 'zero': 0, 'reflect': 1, 'symmetric': 2, 'replicate': 3,
        'wrap': 4}
 
@@ -86,6 +87,10 @@ _PROTOS = {
                                   c_int64, c_double, c_int64, c_double, c_void_p]),
     'ssq_time_reassign_segment': (c_int, []),
     'ssq_time_reassign_max_dmax': (c_int, []),
+    'ssq_reassign2d': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                               c_int64, c_int64, c_int64, c_double, c_double, c_int64, c_int64, c_double, c_int,
+                               c_void_p]),
+    'ssq_reassign2d_tile': (c_int, [c_int]),
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
@@ -172,7 +177,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 114    # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 115    # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'reassign2d_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -435,6 +435,63 @@ def time_reassign_gpu(Sx, Vtg, n_fft, hop_len, fs, gamma, rot=None, dmax=None, o
     check(lib.ssq_time_reassign(_CDT[Sx.dtype], _ptr(Sx), _ptr(Vtg), _ptr(rot), _ptr(out), B, rows, n, n_fft, hop_len,
                                 float(fs) / hop_len, int(dmax), float(gamma), stream()))
     return out
+
+
+def reassign2d_gpu(Sx, dSx, Vtg, n_fft, hop_len, fs, gamma, kmax=None, dmax=None, out=None, return_acc=False,
+                   window=True):
+    """The reassigned spectrogram in three launches (`ssq_reassign2d`, include/ssq_hip.h states the definition;
+    DESIGN.md 4.5.9). `Sx`, `dSx`, `Vtg`: (rows, n) or (B, rows, n) complex -- the STFTs of one signal with the window
+    `g`, with its derivative and with ``tau g``, `tau` the window's time axis in seconds (0 at the centre). The energy
+    ``e = |Sx|^2`` of every point with ``|Sx| >= gamma`` moves by ``m = rint(-Im(dSx / Sx) / (2 pi) / (fs / n_fft))``
+    rows, reflected at row 0, and by ``d = rint(Re(Vtg / Sx) fs / hop_len)`` columns, if ``|m| <= kmax``, ``|d| <=
+    dmax`` and the target is a cell of the plane. ``dSx=None`` turns the frequency axis off (``m = 0``), ``Vtg=None``
+    or ``dmax=0`` the time axis (``d = 0``). `kmax`: None -> ``rows - 1``; `dmax`: None -> ``ceil((n_fft // 2) /
+    hop_len)``. Returns `Rx`, real, of `Sx`'s shape; with `return_acc` ``(Rx, acc, peak)``: the int64 fixed-point sums
+    and, per signal, the bits of the largest kept energy.
+
+    Float64 arithmetic for both precisions. A cell's sum is taken in fixed point -- every term is ``e 2^sh`` truncated to
+    an integer, ``sh = 62 - bit_length(rows min(2 dmax + 1, n)) - frexp(max e)[1]`` per signal -- so it does not depend on
+    the order of the additions: bit-reproducible, and below the exact sum by less than (the cell's terms) x ``2^-sh``,
+    before the one rounding to the output's precision. ``window=False`` sends every term through a global atomic (the
+    same bits, slower; for measurements)."""
+    if gamma is None:
+        raise ValueError("`gamma` must not be None")
+    lib = _lib.load()
+    Sx = to_device(Sx)
+    if Sx.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Sx` must be complex64 or complex128 (got %s)" % Sx.dtype)
+    B, rows, n = _shape3(Sx)
+    planes = []
+    for name, P in (('dSx', dSx), ('Vtg', Vtg)):
+        if P is not None:
+            P = to_device(P, Sx.dtype)
+            if P.shape != Sx.shape:
+                raise ValueError("`Sx` and `%s` must share one shape (got %s and %s)"
+                                 % (name, tuple(Sx.shape), tuple(P.shape)))
+        planes.append(P)
+    dSx, Vtg = planes
+    n_fft, hop_len = int(n_fft), int(hop_len)
+    if n_fft < 1 or hop_len < 1:
+        raise ValueError("`n_fft` and `hop_len` must be >= 1 (got %d, %d)" % (n_fft, hop_len))
+    if dmax is None:
+        dmax = default_dmax(n_fft, hop_len)
+    if Vtg is None:
+        dmax = 0
+    if kmax is None:
+        kmax = rows - 1
+    rdt = _real_of(Sx.dtype)
+    if out is None:
+        out = torch.empty(Sx.shape, dtype=rdt, device=Sx.device)
+    elif not (isinstance(out, torch.Tensor) and out.shape == Sx.shape and out.dtype == rdt and out.is_cuda
+              and out.is_contiguous()):
+        raise ValueError("`out` must be a contiguous real GPU tensor of `Sx`'s shape and precision")
+    acc = torch.empty(Sx.shape, dtype=torch.int64, device=Sx.device)
+    peak = torch.empty((B,), dtype=torch.int64, device=Sx.device)
+    flags = (_lib.REASSIGN2D_FREQ if dSx is not None else 0) | (0 if window else _lib.REASSIGN2D_NO_WINDOW)
+    check(lib.ssq_reassign2d(_CDT[Sx.dtype], _ptr(Sx), _ptr(dSx), _ptr(Vtg), _ptr(out), _ptr(acc), _ptr(peak), B, rows, n,
+                             n_fft, hop_len, float(fs), float(fs) / hop_len, int(kmax), int(dmax), float(gamma), flags,
+                             stream()))
+    return (out, acc, peak) if return_acc else out
 
 
 def _linear_grid(name, v):

@@ -184,3 +184,7 @@ int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* ro
 }
 
 }  // extern "C"
+
+// ssq_reassign2d (the reassigned spectrogram: both axes at once, a fixed-point scatter) shares this unit's flags and point
+// types
+#include "ssq_reassign2d.inl"
