@@ -56,8 +56,8 @@ struct BlockPlan {
     int n_analytic = 0;
     bool own4096 = false;            // float32: the P = 4096 classes' spectra by block_spectra4096_kernel (one launch)
     bool own_big = false;            // ... and short launches of P = 8192 / 16384 blocks by block_spectra_multi_kernel
-    bool paired = true;              // float32: Wx and dWx through each LDS pass as a pair (SSQ_DEBUG_BLOCK_PAIRED=0: one after the other)
-    bool band = true;                // ... and the band staged once per workgroup in the transform buffer (SSQ_DEBUG_BLOCK_BAND=0: outside it)
+    bool paired = true;              // float32 zoom builds (dispatch_zoom_build). false (SSQ_DEBUG_BLOCK_PAIRED=0): Unpaired, one transform after the other
+    bool band = true;                // false (SSQ_DEBUG_BLOCK_BAND=0): BandOut, the band outside the transform buffer
     int64_t n_generic = 0;
     // exact (full-length, four-step) path for the rows the blocks cannot take
     bool exact_ok = false;

@@ -124,6 +124,9 @@ typedef float ssq_f2 __attribute__((ext_vector_type(2)));
 namespace ssq {
 
 void set_error(const char* fmt, ...);
+// a switch of the environment set to 0 (SSQ_DEBUG_X=0 turns X off) / set to this word
+static inline bool env_is_zero(const char* name) { const char* v = getenv(name); return v && atoi(v) == 0; }
+static inline bool env_equals(const char* name, const char* word) { const char* v = getenv(name); return v && !strcmp(v, word); }
 
 #define SSQ_CHECK_HIP(expr)                                                        \
     do {                                                                           \

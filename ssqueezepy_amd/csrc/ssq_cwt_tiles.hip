@@ -303,7 +303,7 @@ int TilePlan::create(const ssq_cwt_tiles_desc& d, int64_t M_, int64_t N_, int64_
     cls.resize(d.n_classes);
     // classes of 2^14 entries and more: four-step kernels, L = A B with A <= B, both 128 .. 2048
     // (SSQ_DEBUG_TILE_FFT=rocfft keeps every class on rocFFT)
-    const bool own_fft = !(getenv("SSQ_DEBUG_TILE_FFT") && !strcmp(getenv("SSQ_DEBUG_TILE_FFT"), "rocfft"));
+    const bool own_fft = !env_equals("SSQ_DEBUG_TILE_FFT", "rocfft");
     int64_t y_entries = 0;
     for (int c = 0; c < d.n_classes; ++c) {
         cls[c] = {d.classes[4 * c], d.classes[4 * c + 1], d.classes[4 * c + 2], 0, 0, 0};

@@ -334,7 +334,7 @@ int TilePlan::spectra(int sig, int nsig, const void* xh_all, hipStream_t stream)
 // ---- the analytic signal through the four-step kernels (ssq_tiles.h)
 bool AnalyticFft::supports(int dtype, int64_t M) {
     if (dtype != SSQ_F32 || (M & (M - 1))) return false;
-    if (getenv("SSQ_DEBUG_TILE_FFT") && !strcmp(getenv("SSQ_DEBUG_TILE_FFT"), "rocfft")) return false;
+    if (env_equals("SSQ_DEBUG_TILE_FFT", "rocfft")) return false;
     return M >= ((int64_t)1 << 13) && M <= ((int64_t)1 << 22);
 }
 int AnalyticFft::create(int64_t M_, int64_t max_batch_) {
