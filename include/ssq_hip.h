@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 115 (114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 116 (115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -733,6 +733,13 @@ int  ssq_stft_plan_shape(const ssq_stft_plan* plan, int64_t* rows, int64_t* n_ho
  * shape n_fft = 598, examples/benchmarks.py:78-79), "rocfft" (everything else, float64: framing kernel + batched
  * rocFFT with strided output). Tests assert on it. */
 const char* ssq_stft_plan_algo(const ssq_stft_plan* plan);
+/* What a float32 plan of window length n_fft runs when its route is "fused-mixed-radix", without a plan and without a
+ * device call (ABI 116): 1 and the passes' radices in order (radix[0 .. *npass), the rest of the 10 entries 0 -- 16s,
+ * 8s, 4s, a 2, then the odd primes 3 .. 31 ascending) and the frames a workgroup transforms together (*G: 16, 8, 4, 2 or
+ * 1), or 0 (outputs zeroed) where that kernel does not take n_fft: the powers of two 128 .. 2048 ("fused"), a prime
+ * factor above 31, more than 10 passes, n_fft above 4992 ("rocfft"). Any of the pointers may be NULL. Tests assert
+ * on it. */
+int  ssq_stft_generic_shape(int64_t n_fft, int* radix /*[10]*/, int* npass, int* G);
 /* x: (batch, n). Sx, dSx, Tx: (batch, rows, n_hops) complex; w: real. */
 int  ssq_stft_execute(ssq_stft_plan* plan, const void* x, int64_t batch, void* Sx,
                       void* dSx, void* Tx, void* w, void* stream);

@@ -168,6 +168,7 @@ _PROTOS = {
                                       c_void_p, c_int, c_int, c_double]),
     'ssq_stft_plan_shape': (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
     'ssq_stft_plan_algo': (c_char_p, [c_void_p]),
+    'ssq_stft_generic_shape': (c_int, [c_int64, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     'ssq_stft_execute': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     'ssq_stft_adjoint': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
@@ -177,7 +178,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 115    # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 116    # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

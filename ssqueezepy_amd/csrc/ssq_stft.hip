@@ -569,6 +569,19 @@ const char* ssq_stft_plan_algo(const ssq_stft_plan* pl) {
     return !pl ? "" : pl->fused ? "fused" : pl->generic_fused ? "fused-mixed-radix" : "rocfft";
 }
 
+int ssq_stft_generic_shape(int64_t n_fft, int* radix, int* npass, int* G) {
+    int r[GEN_MAX_PASSES] = {0}, np = 0, g = 0;
+    for (int p = 0; radix && p < GEN_MAX_PASSES; ++p) radix[p] = 0;
+    if (npass) *npass = 0;
+    if (G) *G = 0;
+    const bool pow2 = (n_fft & (n_fft - 1)) == 0;
+    if ((pow2 && n_fft >= 128 && n_fft <= 2048) || !stft_generic_plan(n_fft, r, &np, &g)) return 0;
+    for (int p = 0; radix && p < np; ++p) radix[p] = r[p];
+    if (npass) *npass = np;
+    if (G) *G = g;
+    return 1;
+}
+
 int ssq_stft_plan_shape(const ssq_stft_plan* pl, int64_t* rows, int64_t* n_hops) {
     SSQ_REQUIRE(pl, "ssq_stft_plan_shape: null plan");
     if (rows) *rows = pl->rows;

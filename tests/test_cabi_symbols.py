@@ -28,6 +28,26 @@ def test_library_builds_loads_and_exports_header_symbols():
     assert lib.ssq_version() >= 105
 
 
+def test_stft_generic_shape_needs_no_device():
+    """`ssq_stft_generic_shape` (ABI 116): what the mixed-radix STFT kernel runs for a window length, answered on the
+    host -- the reference's published shape, a power of two of the other kernel, a prime above 31, the first length
+    past the LDS (tests/test_stft_lengths_design.py: every length against the rule)."""
+    from ssqueezepy_amd import build, _lib
+    lib = ctypes.CDLL(build.build(verbose=False))
+    lib.ssq_version.restype = ctypes.c_int
+    assert lib.ssq_version() >= 116 and _lib.ABI_VERSION >= 116 and 'ssq_stft_generic_shape' in _lib.EXPORTS
+    fn = lib.ssq_stft_generic_shape
+    fn.restype, fn.argtypes = _lib._PROTOS['ssq_stft_generic_shape']
+    radix, npass, G = (ctypes.c_int * 10)(), ctypes.c_int(), ctypes.c_int()
+    assert fn(598, radix, ctypes.byref(npass), ctypes.byref(G)) == 1
+    assert (list(radix), npass.value, G.value) == ([2, 13, 23] + [0] * 7, 3, 4)
+    assert fn(4992, radix, ctypes.byref(npass), ctypes.byref(G)) == 1
+    assert (list(radix), npass.value, G.value) == ([16, 8, 3, 13] + [0] * 6, 4, 1)
+    for n in (256, 97, 4998, 0):
+        assert fn(n, radix, ctypes.byref(npass), ctypes.byref(G)) == 0
+        assert (list(radix), npass.value, G.value) == ([0] * 10, 0, 0)
+
+
 def test_product_path_never_imports_the_oracle():
     pkg = os.path.join(ROOT, 'ssqueezepy_amd')
     for dirpath, _, files in os.walk(pkg):

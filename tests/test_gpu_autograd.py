@@ -42,10 +42,7 @@ def _signal(N, B, seed=0, silent=False):
     return x if B else x[0]
 
 
-def _pad_sources(S, N, n_fft, padtype):
-    """Source sample of every padded position (-1: a zero), read off the padding of 1..N."""
-    xp = S.padsignal(np.arange(1, N + 1.), padtype, padlength=N + n_fft - 1)
-    return np.rint(xp).astype(np.int64) - 1
+from stft_lengths import pad_sources as _pad_sources      # noqa: E402  (source sample of every padded position)
 
 
 def _windows(S, n_fft, win_len, modulated, fs, dtype):
