@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 116 (115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 117 (116: without ssq_reassign_cwt; 115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -289,6 +289,66 @@ int ssq_reassign2d(int dtype, const void* Sx, const void* dSx, const void* Vtg, 
  * window's halo on every side; 4: the most workgroups of the windowed scatter (with more tiles than that a workgroup
  * walks several); anything else: 0. */
 int ssq_reassign2d_tile(int which);
+
+/* The reassigned scalogram (ABI 117; Auger, Flandrin 1995): the energy of every point of a CWT
+ * moves along both axes at once, to the bin of its instantaneous frequency on the synchrosqueezing grid (rows) and to its
+ * group delay (columns). The CWT form of ssq_reassign2d, with which it shares the peak and conversion kernels, the shift
+ * rule and the fixed-point sum.
+ *   W, dW, Wd (batch, rows, n) complex `dtype`, device: the CWT over psih(w), its time derivative, and the CWT over
+ *           psih'(w) (T = -1j r Wd, r = scales / fs, is the CWT taken with t psi(t)). dW may be NULL when the frequency
+ *           axis is off, Wd when the time axis is
+ *   cst     (rows,) float64, device: the weight of row i (ssq_ssqueeze's cst with cst_f64 = 1, da / a), >= 0 and finite
+ *   rsc     (rows,) float64, device: the scale of row i in samples (columns): Re(T / W) in columns is Im(Wd / W) rsc[i]
+ *   dmax    (rows,) int32, HOST: the largest displacement kept in row i, in columns; uploaded once per content
+ *   home    (rows,) int32, device: the bin where the energy of row i is expected to land. It places the LDS window of a
+ *           tile and changes nothing else: any values, out of range included, give the same bits
+ *   Rx      (batch, rows, n) REAL `dtype`; overwritten
+ *   acc     (batch, rows, n) uint64 and peak (batch,) uint64: caller-owned scratch, overwritten; readable afterwards
+ *   grid, params, flipud: as ssq_ssqueeze (params: 5 entries); not looked at when the frequency axis is off
+ *   flags   SSQ_REASSIGN_CWT_FREQ, SSQ_REASSIGN_CWT_TIME: the axis is on. SSQ_REASSIGN_CWT_NO_WINDOW: every term goes to
+ *           `acc` with a global atomic, none through the LDS window -- the same bits; for measurements
+ * Evaluated in float64 for both dtypes (float32 planes are promoted per point), basic IEEE operations only, no
+ * contraction. Per signal b, for every point of row i, column c:
+ *       gr, gi = W[b,i,c];  e = gr*gr + gi*gi
+ *       kept   = not (|W| < gamma) and e finite          |W| as ssq_time_reassign takes it
+ *       freq on:   w = | (di*gr - dr*gi) / (e * 6.283185307179586) |       dr, di = dW[b,i,c]
+ *                  k = the nearest bin of w on the grid (the exact map, clamped to 0 and rows - 1 as ssq_indexed_sum
+ *                      clamps it; w = 0 -> bin 0);  flipud: k -> rows-1-k
+ *       freq off:  k = i
+ *       time on:   d = rint(((ti*gr - tr*gi) / e) * rsc[i])                tr, ti = Wd[b,i,c]; round half to even
+ *                  dropped: not (|d| <= dmax[i]) (NaN included)
+ *       time off:  d = 0
+ *       dropped: c + d outside [0, n)
+ *       Rx[b, k, c + d] += e * cst[i]
+ * The sum of a cell is ssq_reassign2d's fixed-point sum:
+ *       emax = the largest e * cst[i] over the kept points of signal b (dropped ones included); peak[b] = its bits, 0 if none
+ *       C    = sum_i min(2 dmax[i] + 1, n) with the frequency axis on (a bin can take points of every row),
+ *              max_i min(2 dmax[i] + 1, n) with it off; dmax[i] counts as 0 with the time axis off
+ *       H = bit_length(C);  sh = 62 - H - frexp(emax)'s exponent
+ *       q    = (uint64) ldexp(e * cst[i], sh), truncated;  acc[b,k,c+d] = the uint64 sum of its terms, below 2^62
+ *       Rx   = (dtype) ldexp((double) acc, -sh)
+ * so a cell that received t terms lies below the exact sum by less than t 2^-sh, before the one rounding to `dtype`.
+ * Bit-reproducible from call to call and for every `home`; `batch` signals in one call equal `batch` calls of one signal
+ * bit for bit. Three launches and two clears on `stream`, no host synchronisation once the dmax table is on the device:
+ * the peak, the scatter (a workgroup per tile of ssq_reassign_cwt_tile(0) x ssq_reassign_cwt_tile(1) sources adds into an
+ * LDS window of ssq_reassign_cwt_tile(5) bins x ssq_reassign_cwt_tile(6) columns that starts ssq_reassign_cwt_tile(2) bins
+ * below the smallest home of the tile's rows and ssq_reassign_cwt_tile(3) columns left of the tile; terms outside it are
+ * global 64-bit integer atomics) and the conversion. Planes that do not start on a 16-byte boundary take an element-load
+ * instance. Refused, with nothing written and a message that begins with the entry's name: a null W, cst, Rx, acc or peak,
+ * a null dW or params with the frequency axis on, a null Wd, rsc or dmax with the time axis on, a null home with the
+ * window on; batch or n < 1, rows < 2; batch rows n >= 2^32; gamma < 0 or NaN; an unknown grid (frequency axis on);
+ * unknown flags; a dmax[i] < 0 or > ssq_time_reassign_max_dmax(); C >= 2^40. No counterpart in the reference. */
+#define SSQ_REASSIGN_CWT_FREQ 1
+#define SSQ_REASSIGN_CWT_TIME 2
+#define SSQ_REASSIGN_CWT_NO_WINDOW 4
+int ssq_reassign_cwt(int dtype, const void* W, const void* dW, const void* Wd, const double* cst, const double* rsc,
+                     const int32_t* dmax, const int32_t* home, void* Rx, void* acc, void* peak, int64_t batch,
+                     int64_t rows, int64_t n, double gamma, int grid, const double* params, int flipud, int flags,
+                     void* stream);
+/* The scatter's sizes: which = 0, 1: the rows and columns of a tile of sources; 2, 3: the window's halo in bins (below the
+ * smallest home and above it + the tile's rows) and in columns (on either side); 4: the most workgroups of the windowed
+ * scatter; 5, 6: the window's bins and columns; anything else: 0. */
+int ssq_reassign_cwt_tile(int which);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

@@ -30,6 +30,7 @@ def __getattr__(name):
         'tssq_stft': '_tssq_stft', 'time_reassign_gpu': 'algos',
         'msst_stft': '_msst_stft', 'multi_squeeze_gpu': 'algos',
         'reassign_stft': '_reassign_stft', 'reassign2d_gpu': 'algos',
+        'reassign_cwt': '_reassign_cwt', 'reassign_cwt_gpu': 'algos', 'wavelet_time_std': 'wavelets',
         'ssqueeze_fast': 'algos', 'indexed_sum_onfly': 'algos', 'buffer': 'algos',
         'replace_under_abs': 'algos', 'phase_cwt_gpu': 'algos',
         'phase_stft_gpu': 'algos', 'phase_stft2_gpu': 'algos', 'phase_cwt2_gpu': 'algos',

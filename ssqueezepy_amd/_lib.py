@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get('SSQ_HIP_LIB') or os.path.join(HERE, 'libssq_hip.so')
 F32, F64 = 0, 1
 GRID_LOG, GRID_LOG_PIECEWISE, GRID_LIN = 0, 1, 2
 REASSIGN2D_FREQ, REASSIGN2D_NO_WINDOW = 1, 2
+REASSIGN_CWT_FREQ, REASSIGN_CWT_TIME, REASSIGN_CWT_NO_WINDOW = 1, 2, 4
 PAD = {None: -1, 'zero': 0, 'reflect': 1, 'symmetric': 2, 'replicate': 3,
        'wrap': 4}
 
@@ -91,6 +92,10 @@ _PROTOS = {
                                c_int64, c_int64, c_int64, c_double, c_double, c_int64, c_int64, c_double, c_int,
                                c_void_p]),
     'ssq_reassign2d_tile': (c_int, [c_int]),
+    'ssq_reassign_cwt': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int,
+                                 c_int, c_void_p]),
+    'ssq_reassign_cwt_tile': (c_int, [c_int]),
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
@@ -178,7 +183,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 116    # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 117    # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

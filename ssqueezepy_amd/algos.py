@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `reassign_cwt_gpu` (the reassigned scalogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'reassign2d_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -491,6 +491,138 @@ def reassign2d_gpu(Sx, dSx, Vtg, n_fft, hop_len, fs, gamma, kmax=None, dmax=None
     check(lib.ssq_reassign2d(_CDT[Sx.dtype], _ptr(Sx), _ptr(dSx), _ptr(Vtg), _ptr(out), _ptr(acc), _ptr(peak), B, rows, n,
                              n_fft, hop_len, float(fs), float(fs) / hop_len, int(kmax), int(dmax), float(gamma), flags,
                              stream()))
+    return (out, acc, peak) if return_acc else out
+
+
+TSSQ_MAX_DMAX = 1 << 20        # ssq_time_reassign_max_dmax(): the largest displacement the reassignment entries accept
+
+
+def reassign_cwt_dmax(scales, time_std, max_shift=4.):
+    """The largest displacement `reassign_cwt_gpu` keeps per row, in columns, int32: ``min(ceil(max_shift time_std
+    scales[i]), 2^20)`` -- `time_std` the standard deviation of ``|psi(t)|^2`` at scale 1 in samples
+    (`wavelets.wavelet_time_std`), `scales` in samples. A centre of gravity further out than a few standard deviations
+    of the wavelet is no estimate: ``Re(T / W)`` of a noise-dominated point is Cauchy-like."""
+    if not (np.isfinite(max_shift) and max_shift >= 0 and np.isfinite(time_std) and time_std >= 0):
+        raise ValueError("`max_shift` and `time_std` must be finite and >= 0 (got %r, %r)" % (max_shift, time_std))
+    sc = np.asarray(scales, dtype=np.float64).reshape(-1)
+    return np.minimum(np.ceil(float(max_shift) * float(time_std) * sc), TSSQ_MAX_DMAX).astype(np.int32)
+
+
+def _host_bins(w, kind, p, omax):
+    """`bin_from_w` (csrc/ssq_point_math.inl) for a host vector of positive finite frequencies, before `flipud`."""
+    w = np.asarray(w, dtype=np.float64)
+    p = [float(v) for v in p]
+    if kind == _lib.GRID_LIN:
+        t = (w - p[0]) / p[1]
+    elif kind == _lib.GRID_LOG:
+        t = (np.log2(w) - p[0]) / p[1]
+    else:
+        wl = np.log2(w)
+        t = np.where(wl > p[1], (wl - p[1]) / p[3] + np.trunc(p[4]), (wl - p[0]) / p[2])
+    return np.clip(np.rint(t), 0, omax).astype(np.int32)
+
+
+def reassign_cwt_home(scales, ssq_freqs, flipud=False, freq=True, wc=None, fs=1.):
+    """`reassign_cwt_gpu`'s default `home`: per row the bin of its own centre frequency, ``wc fs / (2 pi scales[i])``
+    with `wc` the wavelet's peak radian frequency at scale 1 (`wavelets.center_frequency`, ``kind='peak-ct'``), after
+    `flipud`; the row itself with the frequency axis off. Without `wc` the centre frequency is taken as the grid's top
+    frequency times ``scales.min() / scales[i]``, which is how `ssq_cwt` lays its grid out (``maprange='peak'``) up to
+    the clip at Nyquist. int32, host."""
+    from .scales import infer_scaletype
+    from .ssqueezing import ssq_grid_params
+    sc = np.asarray(scales, dtype=np.float64).reshape(-1)
+    if not freq:
+        return np.arange(sc.size, dtype=np.int32)
+    v = np.asarray(ssq_freqs, dtype=np.float64).reshape(-1)
+    kind, p = ssq_grid_params(v, v.size > 2 and infer_scaletype(v)[0].startswith('log'))
+    fc = v.max() * sc.min() / sc if wc is None else float(wc) * float(fs) / (2 * np.pi * sc)
+    k = _host_bins(fc, kind, p, sc.size - 1)
+    return (sc.size - 1 - k).astype(np.int32) if flipud else k
+
+
+def reassign_cwt_gpu(W, dW, Wd, scales, cst, dmax, ssq_freqs, gamma, flipud=False, out=None, return_acc=False,
+                     window=True, home=None):
+    """The reassigned scalogram in three launches (`ssq_reassign_cwt`, include/ssq_hip.h states the definition;
+    DESIGN.md 4.5.10): the CWT counterpart of `reassign2d_gpu`. `W`, `dW`, `Wd`: (rows, n) or (B, rows, n) complex --
+    the CWT of one signal over ``psih(w)``, its time derivative, and the CWT over ``psih'(w)``
+    (`wavelets.derived_wavelets`); `scales` (rows,) in samples; `cst` the rows' weights, a scalar or (rows,), sent as
+    float64; `dmax` (rows,) integers, the largest displacement kept per row (`reassign_cwt_dmax`); `ssq_freqs` (rows,),
+    linear, 'log' or 'log-piecewise' (inferred from its values, as `ssqueeze` does). The weighted energy
+    ``|W|^2 cst[i]`` of every point with ``|W| >= gamma`` moves to the bin of ``|Im(dW / W)| / 2pi`` on the grid
+    (`flipud`: mirrored) and by ``d = rint(Im(Wd / W) scales[i])`` columns -- ``Re(T / W)`` with ``T = -1j r Wd`` -- if
+    ``|d| <= dmax[i]`` and the target is a column of the plane. ``dW=None`` turns the frequency axis off (a point stays in
+    its row; `ssq_freqs` may be None), ``Wd=None`` the time axis (`dmax` may be None). Returns `Rx`, real, of `W`'s
+    shape; with `return_acc` ``(Rx, acc, peak)``: the int64 fixed-point sums and, per signal, the bits of the largest
+    kept term.
+
+    Float64 arithmetic for both precisions; the sum is `reassign2d_gpu`'s fixed-point sum with ``C = sum_i min(2 dmax[i]
+    + 1, n)`` (``max_i`` with the frequency axis off), so the result is bit-reproducible and below the exact sum by less
+    than (the cell's terms) x ``2^-sh``. `home` (rows,) integers: where the energy of row `i` is expected to land
+    (None: `reassign_cwt_home`); it places the LDS windows and affects speed only, as does ``window=False`` (every term
+    through a global atomic)."""
+    if gamma is None:
+        raise ValueError("`gamma` must not be None")
+    lib = _lib.load()
+    W = to_device(W)
+    if W.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`W` must be complex64 or complex128 (got %s)" % W.dtype)
+    B, rows, n = _shape3(W)
+    planes = []
+    for name, P in (('dW', dW), ('Wd', Wd)):
+        if P is not None:
+            P = to_device(P, W.dtype)
+            if P.shape != W.shape:
+                raise ValueError("`W` and `%s` must share one shape (got %s and %s)"
+                                 % (name, tuple(W.shape), tuple(P.shape)))
+        planes.append(P)
+    dW, Wd = planes
+    freq, time = dW is not None, Wd is not None
+
+    def host(name, v, dt, scalar_ok=False):
+        v = v.detach().cpu().numpy() if hasattr(v, 'detach') else v
+        v = np.asarray(v).reshape(-1)
+        if not (v.size == rows or (scalar_ok and v.size == 1)):
+            raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
+        return np.ascontiguousarray(np.broadcast_to(v, (rows,)), dtype=dt)
+    c = host('cst', cst, np.float64, scalar_ok=True)
+    if not (np.isfinite(c).all() and (c >= 0).all()):
+        raise ValueError("`cst` must be finite and >= 0")
+    sc = host('scales', scales, np.float64)
+    dm = None
+    if time:
+        dm = host('dmax', dmax, np.int64)
+        if (dm < np.iinfo(np.int32).min).any() or (dm > np.iinfo(np.int32).max).any():
+            raise ValueError("`dmax` must fit 32 bits")
+        dm = dm.astype(np.int32)
+    kind, p = 0, None
+    if freq:
+        from .scales import infer_scaletype
+        if hasattr(ssq_freqs, 'detach'):
+            ssq_freqs = ssq_freqs.detach().cpu().numpy()
+        ssq_freqs = np.asarray(ssq_freqs).reshape(-1)
+        if ssq_freqs.size != rows:
+            raise ValueError("`ssq_freqs` must have one entry per row (%d != %d)" % (ssq_freqs.size, rows))
+        # (two values are evenly spaced in any metric: they are taken as a linear grid)
+        kind, p = _grid(ssq_freqs, rows > 2 and infer_scaletype(ssq_freqs)[0].startswith('log'))
+    if home is None:
+        home = reassign_cwt_home(sc, ssq_freqs, flipud, freq)
+    else:
+        home = np.clip(host('home', home, np.int64), np.iinfo(np.int32).min, np.iinfo(np.int32).max).astype(np.int32)
+    rdt = _real_of(W.dtype)
+    if out is None:
+        out = torch.empty(W.shape, dtype=rdt, device=W.device)
+    elif not (isinstance(out, torch.Tensor) and out.shape == W.shape and out.dtype == rdt and out.is_cuda
+              and out.is_contiguous()):
+        raise ValueError("`out` must be a contiguous real GPU tensor of `W`'s shape and precision")
+    acc = torch.empty(W.shape, dtype=torch.int64, device=W.device)
+    peak = torch.empty((B,), dtype=torch.int64, device=W.device)
+    cst_d, rsc_d = to_device(c), to_device(sc)
+    home_d = to_device(np.ascontiguousarray(home))
+    flags = ((_lib.REASSIGN_CWT_FREQ if freq else 0) | (_lib.REASSIGN_CWT_TIME if time else 0)
+             | (0 if window else _lib.REASSIGN_CWT_NO_WINDOW))
+    check(lib.ssq_reassign_cwt(_CDT[W.dtype], _ptr(W), _ptr(dW), _ptr(Wd), _ptr(cst_d), _ptr(rsc_d),
+                               dm.ctypes.data if time else None, _ptr(home_d), _ptr(out), _ptr(acc), _ptr(peak), B, rows,
+                               n, float(gamma), kind, p, int(bool(flipud)), flags, stream()))
     return (out, acc, peak) if return_acc else out
 
 

@@ -56,9 +56,11 @@ __device__ __forceinline__ void reassign2d_load(const T* __restrict__ P, size_t 
     }
 }
 
-template <typename T, bool VEC>
+// (WGT: the energy of a point of row i counts as e * cst[i], the term ssq_reassign_cwt adds; n = the row's length)
+template <typename T, bool VEC, bool WGT>
 __global__ __launch_bounds__(256) void reassign2d_peak_kernel(const T* __restrict__ Sx, unsigned long long* __restrict__ peak,
-                                                               unsigned batch, unsigned plane, double gamma) {
+                                                               unsigned batch, unsigned plane, double gamma,
+                                                               const double* __restrict__ cst, unsigned n) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     unsigned long long* top = reinterpret_cast<unsigned long long*>(lds_raw);
     for (unsigned b = blockIdx.y; b < batch; b += gridDim.y) {
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(256) void reassign2d_peak_kernel(const T* __restric
             double gr, gi, e;
             reassign2d_load<T, VEC>(Sx, off + t, gr, gi);
             if (reassign2d_kept<T>(gr, gi, gamma, e)) {
+                if constexpr (WGT) e = e * cst[t / n];
                 const unsigned long long bits = __builtin_bit_cast(unsigned long long, e);
                 best = bits > best ? bits : best;
             }
@@ -79,6 +82,37 @@ __global__ __launch_bounds__(256) void reassign2d_peak_kernel(const T* __restric
         if (threadIdx.x == 0 && top[0])
             __scoped_atomic_fetch_max(peak + b, top[0], __ATOMIC_RELAXED, __MEMORY_SCOPE_DEVICE);
         __syncthreads();                                        // (thread 0 has read top[0] before the next signal clears it)
+    }
+}
+
+// The end of a tile, shared with reassign_cwt_scatter_kernel (ssq_reassign_cwt.inl): the window of WR x WC cells whose
+// first cell is (wr0, wc0) of the plane is added to `acc` and left cleared. A wavefront per line of 64 cells, CHUNK lines
+// at a time: the lines are read first, then the non-zero cells are cleared and added -- runs of neighbouring cells, as
+// the terms of a ridge or of noise leave them. Only cells of the plane hold anything. (All of a wavefront's lines at once
+// cost 120 VGPRs against 72 in the STFT form: two workgroups per CU in place of three, and a slower float32 call --
+// profiles/reassign_stft.txt.) Between two workgroup barriers of the caller.
+template <int WR, int WC, int CHUNK>
+__device__ __forceinline__ void reassign2d_flush_window(unsigned long long* win, unsigned long long* __restrict__ acc,
+                                                        size_t boff, int64_t wr0, int64_t wc0, unsigned rows, unsigned n,
+                                                        int wave, int lane) {
+    constexpr int LINES = WR * (WC / 64) / R2D_NW;
+    static_assert(WC % 64 == 0 && (WR * (WC / 64)) % R2D_NW == 0 && LINES % CHUNK == 0, "a line of the window is a wavefront wide");
+#pragma unroll 1
+    for (int i0 = 0; i0 < LINES; i0 += CHUNK) {
+        unsigned long long v[CHUNK];
+#pragma unroll
+        for (int i = 0; i < CHUNK; ++i) v[i] = win[(wave + R2D_NW * (i0 + i)) * 64 + lane];
+#pragma unroll
+        for (int i = 0; i < CHUNK; ++i) {
+            if (!v[i]) continue;
+            const int line = wave + R2D_NW * (i0 + i), wr = line / (WC / 64), ws = line - wr * (WC / 64);
+            const int64_t k2 = wr0 + wr;
+            const int64_t c2 = wc0 + ws * 64 + lane;
+            win[line * 64 + lane] = 0ull;
+            if (k2 >= 0 && k2 < (int64_t)rows && c2 >= 0 && c2 < (int64_t)n)
+                __scoped_atomic_fetch_add(acc + boff + (size_t)k2 * n + (size_t)c2, v[i], __ATOMIC_RELAXED,
+                                          __MEMORY_SCOPE_DEVICE);
+        }
     }
 }
 
@@ -161,27 +195,7 @@ __global__ __launch_bounds__(R2D_NT) void reassign2d_scatter_kernel(
 
         if constexpr (WIN) {
             __syncthreads();
-            // a wavefront per line of 64 cells, R2D_CHUNK lines at a time: the lines are read first, then the non-zero
-            // cells are cleared and added -- runs of neighbouring cells, as the terms of a ridge or of noise leave them.
-            // Only cells of the plane hold anything. (All R2D_LINES lines at once cost 120 VGPRs against 72: two
-            // workgroups per CU in place of three, and a slower float32 call -- profiles/reassign_stft.txt.)
-#pragma unroll 1
-            for (int i0 = 0; i0 < R2D_LINES; i0 += R2D_CHUNK) {
-                unsigned long long v[R2D_CHUNK];
-#pragma unroll
-                for (int i = 0; i < R2D_CHUNK; ++i) v[i] = win[(wave + R2D_NW * (i0 + i)) * 64 + lane];
-#pragma unroll
-                for (int i = 0; i < R2D_CHUNK; ++i) {
-                    if (!v[i]) continue;
-                    const int line = wave + R2D_NW * (i0 + i), wr = line / (R2D_WC / 64), ws = line - wr * (R2D_WC / 64);
-                    const int64_t k2 = wr0 + wr;
-                    const int64_t c2 = wc0 + ws * 64 + lane;
-                    win[line * 64 + lane] = 0ull;
-                    if (k2 >= 0 && k2 < (int64_t)rows && c2 >= 0 && c2 < (int64_t)n)
-                        __scoped_atomic_fetch_add(acc + boff + (size_t)k2 * n + (size_t)c2, v[i], __ATOMIC_RELAXED,
-                                                  __MEMORY_SCOPE_DEVICE);
-                }
-            }
+            reassign2d_flush_window<R2D_WR, R2D_WC, R2D_CHUNK>(win, acc, boff, wr0, wc0, rows, n, wave, lane);
             __syncthreads();                                    // the next unit adds into the cleared window
         }
     }
@@ -214,8 +228,9 @@ static int launch_reassign2d(const void* Sx, const void* dSx, const void* Vtg, v
 
     int64_t gx = (plane + 256 * 16 - 1) / (256 * 16);           // 16 points per work-item or more
     gx = gx < 1 ? 1 : (gx > 4096 ? 4096 : gx);
-    int rc = launch_lds(vec ? reassign2d_peak_kernel<T, true> : reassign2d_peak_kernel<T, false>, dim3((unsigned)gx, by),
-                        dim3(256), 16, stream, (const T*)Sx, peakp, (unsigned)batch, (unsigned)plane, gamma);
+    int rc = launch_lds(vec ? reassign2d_peak_kernel<T, true, false> : reassign2d_peak_kernel<T, false, false>,
+                        dim3((unsigned)gx, by), dim3(256), 16, stream, (const T*)Sx, peakp, (unsigned)batch, (unsigned)plane,
+                        gamma, (const double*)nullptr, 0u);
     if (rc) return rc;
 
     const int64_t rtiles = (rows + R2D_TR - 1) / R2D_TR, ctiles = (n + R2D_TC - 1) / R2D_TC, units = batch * rtiles * ctiles;

@@ -188,3 +188,5 @@ int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* ro
 // ssq_reassign2d (the reassigned spectrogram: both axes at once, a fixed-point scatter) shares this unit's flags and point
 // types
 #include "ssq_reassign2d.inl"
+// ssq_reassign_cwt (the reassigned scalogram: the CWT form of that scatter) shares ssq_reassign2d's kernels and helpers
+#include "ssq_reassign_cwt.inl"

@@ -26,7 +26,7 @@ from .configs import fill_defaults
 pi = np.pi
 
 __all__ = ['Wavelet', 'center_frequency', 'xi_grid', 'find_maximum',
-           'find_first_occurrence', 'morsefreq', 'derived_wavelets', 'morse_wavelets']
+           'find_first_occurrence', 'morsefreq', 'derived_wavelets', 'morse_wavelets', 'wavelet_time_std']
 
 
 # --------------------------------------------------------------------- grids
@@ -461,6 +461,42 @@ def derived_wavelets(wavelet):
     if len(_DERIVED) >= 16:
         _DERIVED.pop(next(iter(_DERIVED)))
     _DERIVED[key] = out
+    return out
+
+
+_TIME_STD = {}
+
+
+def wavelet_time_std(wavelet):
+    """The standard deviation of ``|psi(t)|^2`` at scale 1, in samples: ``sqrt(int |psih'|^2 dw / int |psih|^2 dw)``
+    (Parseval: ``t psi(t)`` has the transform ``1j psih'(w)``; `psih` is real, so the time mean is 0). ``psih'`` is
+    `derived_wavelets`' closed form; both integrals are taken in float64 by the trapezoid rule on the wavelet's
+    support, whatever the wavelet's dtype, and the value is kept per wavelet configuration. ``sqrt(1/2)`` for a Morlet
+    wavelet; the wavelets are `derived_wavelets`' (others raise as they do there). `reassign_cwt` bounds a row's time
+    displacement by a multiple of this times the row's scale."""
+    wavelet = Wavelet._init_if_not_isinstance(wavelet)
+    derived_wavelets(wavelet)                   # raises for a wavelet without a closed form
+    key = wavelet.key()
+    if key in _TIME_STD:
+        return _TIME_STD[key]
+    cfg = {k: v for k, v in wavelet.config.items() if k != 'dtype'}
+    psih = _FAMILIES[wavelet.family](**dict(cfg, dtype='float64'))[0]
+    dpsih = (_gmw_derivative if wavelet.family == 'gmw' else _morlet_derivative)(cfg, 'float64')
+    lo_sign = 0. if wavelet.family == 'gmw' else -1.        # (a GMW is 0 for w <= 0)
+    hi = 1.
+    while hi < 2. ** 20:                        # the support: where psih and psih' have fallen to nothing at both ends
+        w = np.linspace(lo_sign * hi, hi, 2049)
+        a, b = np.abs(psih(w)), np.abs(dpsih(w))
+        ends = [-1] if lo_sign == 0. else [0, -1]
+        if all(a[e] <= 1e-18 * a.max() and b[e] <= 1e-18 * b.max() for e in ends):
+            break
+        hi *= 2.
+    w = np.linspace(lo_sign * hi, hi, (1 << 18) + 1)
+    a, b = np.asarray(psih(w), dtype=np.float64) ** 2, np.asarray(dpsih(w), dtype=np.float64) ** 2
+    out = float(np.sqrt((b.sum() - .5 * (b[0] + b[-1])) / (a.sum() - .5 * (a[0] + a[-1]))))
+    if len(_TIME_STD) >= 16:
+        _TIME_STD.pop(next(iter(_TIME_STD)))
+    _TIME_STD[key] = out
     return out
 
 
