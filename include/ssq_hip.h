@@ -387,6 +387,39 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx,
                     int64_t n, int grid, const double* params, int flipud,
                     void* stream);
 
+/* Same accumulate, bins given by the caller (ABI 118): `kidx` uint16 (batch, na, n), the bin of every point AFTER any
+ * flip, 0xFFFF = skip. This is the source that carries the default reassignment of every float64 ssq_cwt; na < 65535.
+ * By default the sums are accumulate_f64_kernel's where its tile fits (ssq_reassign_route): a cell is the float64 sum
+ * of its terms in the order the hardware served them, rounded once to `dtype`; SSQ_TILE_ORDER=ordered (environment)
+ * selects the ordered kernels, ascending i in `dtype`'s arithmetic, bit for bit ssq_indexed_sum's. Tx is OVERWRITTEN.
+ * THE ENTRY DOES NOT CHECK THE MAP: the kernels index their LDS tile with it, so every entry must be 0xFFFF or < na
+ * (the Python wrapper, algos.indexed_sum_bins, refuses any other map before the launch). */
+int ssq_indexed_sum_bins(int dtype, const void* Wx, const void* kidx, void* Tx,
+                         const void* cst, int cst_f64, int64_t batch, int64_t na,
+                         int64_t n, void* stream);
+
+/* Which kernel and build the three entries above (and every plan that reassigns through them) run for a shape, without
+ * a device call (ABI 118). `binsrc`: 0 bins from dWx (ssq_ssqueeze), 1 from a stored w (ssq_indexed_sum), 2 from a
+ * bin map (ssq_indexed_sum_bins, the plans' kidx); `ordered`: SSQ_TILE_ORDER=ordered is in force; `want_kmap`: the
+ * caller asks for the bin map back. Outputs (any may be NULL): *kernel, one of SSQ_REASSIGN_*; *cols, the tile's
+ * columns (1 for the global kernel: a thread walks one column); *wavefronts per workgroup. With cell = 8 / 16 bytes
+ * (complex float32 / float64) and LDS = 160 KiB:
+ *   SSQ_REASSIGN_F64     binsrc 2, not ordered, no kmap, na * n < 2^31: 32 columns while na * 32 * 16 <= LDS / 2, 16 while
+ *                        na * 16 * 16 <= LDS, float64 data 8 while na * 8 * 16 <= LDS (8 wavefronts); else as below
+ *   SSQ_REASSIGN_TILE16  na * 16 * cell <= LDS and na * n < 2^31: float32 32 columns while na * 32 * cell <= LDS / 2
+ *                        (4 wavefronts), else 16 (2); float64 16 columns (4 wavefronts)
+ *   SSQ_REASSIGN_TILE    one wavefront: 16, 8 columns while the tile fits LDS / 2, then 16, 8, 4 while it fits LDS
+ *                        (16 and the half-capacity 8 are reached with na * n >= 2^31 only)
+ *   SSQ_REASSIGN_GLOBAL  no LDS tile: Tx cleared, one thread per column (256-thread workgroups)
+ * Returns 0, or -1 (outputs -1, 0, 0) for an unknown dtype or binsrc, an empty shape, or a bin map with na >= 65535.
+ * Tests assert on it. */
+#define SSQ_REASSIGN_TILE16 0     /* accumulate_tile16_kernel: ordered, DPP-combined row-lanes              */
+#define SSQ_REASSIGN_TILE   1     /* accumulate_tile_kernel: ordered, one wavefront per tile               */
+#define SSQ_REASSIGN_F64    2     /* accumulate_f64_kernel: unordered float64 LDS sums from a bin map      */
+#define SSQ_REASSIGN_GLOBAL 3     /* accumulate_global_kernel: ordered, in global memory                   */
+int ssq_reassign_route(int dtype, int binsrc, int64_t na, int64_t n, int ordered, int want_kmap,
+                       int* kernel, int* cols, int* wavefronts);
+
 /* Multisynchrosqueezing, MSST (ABI 114; Yu, Wang, Zhao 2019): the first-order frequency map
  * applied to its own output n_iter - 1 times within a column, on real-valued frequencies, then ssq_indexed_sum's
  * accumulate from the final frequency of every point.

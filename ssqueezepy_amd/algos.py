@@ -3,7 +3,7 @@
 
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
-`indexed_sum_onfly` (153-169), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
+`indexed_sum_onfly` (153-169), `indexed_sum_bins` (the same sum from a caller's bin map: no counterpart in the reference), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
 (818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `reassign_cwt_gpu` (the reassigned scalogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'indexed_sum_bins', 'reassign_route', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -204,6 +204,65 @@ def indexed_sum_onfly(Wx, w, ssq_freqs, const=1, logscale=False, flipud=False,
                               _ptr(cst), c64, B, na, n, kind, p,
                               int(bool(flipud)), stream()))
     return out
+
+
+SKIP_BIN = 0xFFFF               # `indexed_sum_bins`: the map's "no bin" entry
+
+
+def indexed_sum_bins(Wx, k, const=1, out=None):
+    """Accumulate into bins the caller supplies: ``Tx[k[i, j], j] += Wx[i, j] * const[i]`` (`ssq_indexed_sum_bins`,
+    include/ssq_hip.h). `Wx`: (na, n) or (B, na, n) complex; `k`: a uint16 array or tensor of `Wx`'s shape, the bin of
+    every point after any flip, ``SKIP_BIN`` (0xFFFF) = skip; `const` as `indexed_sum_onfly`'s. This is the bin source
+    of every float64 `ssq_cwt`: by default a cell is the float64 sum of its terms in arrival order, rounded once, where
+    `reassign_route` says 'f64'; ``SSQ_TILE_ORDER=ordered`` gives `indexed_sum_onfly`'s ordered sums. The kernels trust
+    the map, so a map with an entry that is neither ``SKIP_BIN`` nor ``< na`` is refused here, before any launch."""
+    lib = _lib.load()
+    Wx = to_device(Wx)
+    if Wx.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Wx` must be complex64 or complex128 (got %s)" % Wx.dtype)
+    if isinstance(k, np.ndarray):
+        if k.dtype != np.uint16:
+            raise TypeError("`k` must be uint16 (got %s)" % k.dtype)
+        k = torch.from_numpy(np.ascontiguousarray(k))
+    elif not isinstance(k, torch.Tensor):
+        raise TypeError("expected numpy array or torch Tensor (got %s)" % type(k))
+    if k.dtype != torch.uint16:
+        raise TypeError("`k` must be uint16 (got %s)" % k.dtype)
+    if Wx.shape != k.shape:
+        raise ValueError("`Wx` and `k` shapes differ: %s vs %s" % (tuple(Wx.shape), tuple(k.shape)))
+    B, na, n = _shape3(Wx)
+    if na >= SKIP_BIN:
+        raise ValueError("a bin map addresses fewer than %d rows (got %d)" % (SKIP_BIN, na))
+    if out is not None:
+        _check_out(out, Wx)
+    k = k.to(device()).contiguous()
+    # one reduction on the device: the largest entry that is not the skip mark (int16's bit pattern: torch reduces no
+    # uint16; a mark becomes -1, entries of 0x8000 and more become negative and are caught below)
+    ks = k.view(torch.int16)
+    bad = ((ks != -1) & ((ks < 0) | (ks >= na))).any()
+    if bool(bad):
+        raise ValueError("`k` holds a bin that is neither 0x%X (skip) nor < %d" % (SKIP_BIN, na))
+    if out is None:
+        out = torch.empty_like(Wx)
+    cst, c64 = _const_vector(const, na, Wx.dtype)
+    check(lib.ssq_indexed_sum_bins(_CDT[Wx.dtype], _ptr(Wx), _ptr(k), _ptr(out), _ptr(cst), c64, B, na, n, stream()))
+    return out
+
+
+def reassign_route(dtype, binsrc, na, n, ordered=None, kmap=False):
+    """What `ssqueeze_fast` (``binsrc='dwx'``), `indexed_sum_onfly` (``'w'``) and `indexed_sum_bins` / the plans' bin
+    maps (``'bins'``) launch for a shape: ``(kernel, cols, wavefronts)`` with `kernel` one of 'tile16', 'tile', 'f64',
+    'global' (`ssq_reassign_route`, include/ssq_hip.h; no device call). `ordered`: None -> what ``SSQ_TILE_ORDER`` says
+    now; `kmap`: the caller asks for the bin map (`get_k`)."""
+    import os
+    code = F32 if str(dtype) in ('float32', 'torch.float32', 'torch.complex64', 'complex64') else F64
+    src = {'dwx': _lib.BIN_FROM_DWX, 'w': _lib.BIN_FROM_W, 'bins': _lib.BIN_FROM_KIDX}[binsrc]
+    if ordered is None:
+        ordered = os.environ.get('SSQ_TILE_ORDER') == 'ordered'
+    kern, cols, waves = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    check(_lib.load().ssq_reassign_route(code, src, int(na), int(n), int(bool(ordered)), int(bool(kmap)),
+                                         ctypes.byref(kern), ctypes.byref(cols), ctypes.byref(waves)))
+    return _lib.REASSIGN_KERNELS[kern.value], cols.value, waves.value
 
 
 def phase_cwt_gpu(Wx, dWx, gamma):

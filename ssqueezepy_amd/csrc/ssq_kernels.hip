@@ -411,15 +411,57 @@ __global__ __launch_bounds__(64 * NW) void accumulate_f64_kernel(
     }
 }
 
-// columns per tile: rows of at least 128 bytes of data per tile, two or more workgroups per CU
+// ------------------------------------------------- the routing rule (ssq_reassign_route, include/ssq_hip.h)
+// Which kernel and build launch_accumulate runs for a shape: the one place that decides, no device call. `real_bytes` is
+// sizeof(T); a cell of the ordered tiles is a complex<T>, a cell of the unordered float64 tile 16 bytes for both types.
+struct ReassignRoute { int kernel, cols, wavefronts; };
+
+// accumulate_f64_kernel's columns per tile: rows of at least 128 bytes of data per tile, two or more workgroups per CU
 // when the tile allows; 0 = the tile does not fit the LDS
-template <typename T> static int f64_tile_cols(int64_t na, size_t lds_cap) {
+static int f64_tile_cols(size_t real_bytes, int64_t na) {
     for (int cols = 32; cols >= 16; cols >>= 1)
-        if ((size_t)na * cols * 16 <= lds_cap / 2) return cols;
+        if ((size_t)na * cols * 16 <= LDS_CAP / 2) return cols;
     // (float64 data, 512 rows: 16 columns in one workgroup per CU 4.3 ms, 8 columns in two 4.9 ms)
-    if ((size_t)na * 16 * 16 <= lds_cap) return 16;
-    if (sizeof(T) == 8 && (size_t)na * 8 * 16 <= lds_cap) return 8;
+    if ((size_t)na * 16 * 16 <= LDS_CAP) return 16;
+    if (real_bytes == 8 && (size_t)na * 8 * 16 <= LDS_CAP) return 8;
     return 0;
+}
+
+static ReassignRoute reassign_route(size_t real_bytes, int binsrc, int64_t na, int64_t n, bool ordered, bool want_kmap) {
+    const size_t cell = 2 * real_bytes;
+    const bool small = (size_t)na * (size_t)n < ((size_t)1 << 31);     // 32-bit offsets inside the fast kernels
+    if (binsrc == BIN_FROM_KIDX) {
+        // known bins: the unordered float64 tile (see accumulate_f64_kernel) unless the caller
+        // asked for the ordered sums or wants the bin map back
+        const int cols = f64_tile_cols(real_bytes, na);
+        if (!ordered && !want_kmap && cols && small) return {SSQ_REASSIGN_F64, cols, 8};
+    }
+    // the DPP-combined, double-buffered kernel: U row batches in flight, RL row-lanes x 64 / RL columns per wavefront,
+    // TC-column tiles
+    if ((size_t)na * 16 * cell <= LDS_CAP && small) {
+        // Row batches in flight per lane. Measured (config 2, float32), 16 row-lanes:
+        // U = 2: 257 us, 3: 263, 4: 259, 8: 278; 8 row-lanes: U = 1: 314, 2: 246, 3: 240,
+        // 4: 243, 8: 267 -- the resident wavefronts cover most of the latency, and a
+        // deep prefetch spreads each wavefront's requests over more DRAM pages.
+        // float32: 8 row-lanes x 8 columns per wavefront, 2 wavefronts per 16-column tile (240 us
+        // at config 2 vs 250 with 16 row-lanes); float64: 16 row-lanes x 4 columns, 4 wavefronts
+        // (config 5: 22.7 vs 23.6 ms).
+        if (real_bytes == 4) {
+            // 32-column tiles of four 8-lane wavefronts (256-byte row segments per workgroup,
+            // 2 workgroups per CU): 232 us at config 2 vs 240 with 16-column tiles (64-column
+            // tiles, one workgroup per CU: 231)
+            if ((size_t)na * 32 * cell <= LDS_CAP / 2) return {SSQ_REASSIGN_TILE16, 32, 4};
+            return {SSQ_REASSIGN_TILE16, 16, 2};
+        }
+        return {SSQ_REASSIGN_TILE16, 16, 4};
+    }
+    // larger `na` (or 2^31 points and more): one wavefront per tile, the tile shrunk before giving up on LDS
+    if ((size_t)na * 16 * cell <= LDS_CAP / 2) return {SSQ_REASSIGN_TILE, 16, 1};
+    if ((size_t)na * 8 * cell <= LDS_CAP / 2) return {SSQ_REASSIGN_TILE, 8, 1};
+    if ((size_t)na * 16 * cell <= LDS_CAP) return {SSQ_REASSIGN_TILE, 16, 1};
+    if ((size_t)na * 8 * cell <= LDS_CAP) return {SSQ_REASSIGN_TILE, 8, 1};
+    if ((size_t)na * 4 * cell <= LDS_CAP) return {SSQ_REASSIGN_TILE, 4, 1};
+    return {SSQ_REASSIGN_GLOBAL, 1, 4};
 }
 
 template <typename T, bool CST64>
@@ -472,13 +514,10 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
                                const void* cst, const SsqParams& sp, int64_t batch,
                                int64_t na, int64_t n, int32_t* kmap, hipStream_t stream) {
     const size_t cell = 2 * sizeof(T);
-    const size_t lds_cap = LDS_CAP;
+    const ReassignRoute route = reassign_route(sizeof(T), BINSRC, na, n, reassign_ordered(), kmap != nullptr);
     if constexpr (BINSRC == BIN_FROM_KIDX) {
-        // known bins: the unordered float64 tile (see accumulate_f64_kernel) unless the caller
-        // asked for the ordered sums or wants the bin map back
-        const int cols = f64_tile_cols<T>(na, lds_cap);
-        if (!reassign_ordered() && !kmap && cols && (size_t)na * (size_t)n < ((size_t)1 << 31))
-            return launch_accumulate_f64<T, CST64>(Wx, src, Tx, cst, sp, batch, na, n, cols, stream);
+        if (route.kernel == SSQ_REASSIGN_F64)
+            return launch_accumulate_f64<T, CST64>(Wx, src, Tx, cst, sp, batch, na, n, route.cols, stream);
     }
     auto launch_tile = [&](auto tc) -> int {
         constexpr int TC = decltype(tc)::value;
@@ -486,39 +525,25 @@ static int launch_accumulate_t(const void* Wx, const void* src, const void* Sfs,
                           dim3(64), (size_t)na * TC * cell, stream, (const T*)Wx, src, (const T*)Sfs, (T*)Tx, cst, sp, na, n,
                           kmap);
     };
-    // the DPP-combined, double-buffered kernel: U row batches in flight, RL row-lanes x 64 / RL columns per wavefront,
-    // TC-column tiles
     auto launch_tile16 = [&](auto u, auto wps, auto rl, auto tc) -> int {
         constexpr int U = decltype(u)::value, WPS = decltype(wps)::value, RL = decltype(rl)::value, TC = decltype(tc)::value;
         return launch_lds(accumulate_tile16_kernel<T, BINSRC, STFT, CST64, U, WPS, RL, TC>,
                           dim3((unsigned)(((n + TC - 1) / TC + 7) / 8 * 8), (unsigned)batch), dim3(64 * (TC / (64 / RL))),
                           (size_t)na * TC * cell, stream, (const T*)Wx, src, (const T*)Sfs, (T*)Tx, cst, sp, na, n, kmap);
     };
-    // 32-bit offsets inside
-    if ((size_t)na * 16 * cell <= lds_cap && (size_t)na * (size_t)n < ((size_t)1 << 31)) {
-        // Row batches in flight per lane. Measured (config 2, float32), 16 row-lanes:
-        // U = 2: 257 us, 3: 263, 4: 259, 8: 278; 8 row-lanes: U = 1: 314, 2: 246, 3: 240,
-        // 4: 243, 8: 267 -- the resident wavefronts cover most of the latency, and a
-        // deep prefetch spreads each wavefront's requests over more DRAM pages.
-        // float32: 8 row-lanes x 8 columns per wavefront, 2 wavefronts per 16-column tile (240 us
-        // at config 2 vs 250 with 16 row-lanes); float64: 16 row-lanes x 4 columns, 4 wavefronts
-        // (config 5: 22.7 vs 23.6 ms).
+    if (route.kernel == SSQ_REASSIGN_TILE16) {
         if constexpr (sizeof(T) == 4) {
-            // 32-column tiles of four 8-lane wavefronts (256-byte row segments per workgroup,
-            // 2 workgroups per CU): 232 us at config 2 vs 240 with 16-column tiles (64-column
-            // tiles, one workgroup per CU: 231)
-            if ((size_t)na * 32 * cell <= lds_cap / 2) return launch_tile16(int_c<3>{}, int_c<2>{}, int_c<8>{}, int_c<32>{});
+            if (route.cols == 32) return launch_tile16(int_c<3>{}, int_c<2>{}, int_c<8>{}, int_c<32>{});
             return launch_tile16(int_c<3>{}, int_c<2>{}, int_c<8>{}, int_c<16>{});
         } else {
             return launch_tile16(int_c<4>{}, int_c<4>{}, int_c<16>{}, int_c<16>{});
         }
     }
-    // larger `na`: shrink the tile before giving up on LDS
-    if ((size_t)na * 16 * cell <= lds_cap / 2) return launch_tile(int_c<16>{});
-    if ((size_t)na * 8 * cell <= lds_cap / 2) return launch_tile(int_c<8>{});
-    if ((size_t)na * 16 * cell <= lds_cap) return launch_tile(int_c<16>{});
-    if ((size_t)na * 8 * cell <= lds_cap) return launch_tile(int_c<8>{});
-    if ((size_t)na * 4 * cell <= lds_cap) return launch_tile(int_c<4>{});
+    if (route.kernel == SSQ_REASSIGN_TILE) {
+        if (route.cols == 16) return launch_tile(int_c<16>{});
+        if (route.cols == 8) return launch_tile(int_c<8>{});
+        return launch_tile(int_c<4>{});
+    }
     SSQ_CHECK_HIP(hipMemsetAsync(Tx, 0, (size_t)batch * na * n * cell, stream));
     dim3 grid((unsigned)((n + 255) / 256), (unsigned)batch);
     hipLaunchKernelGGL((accumulate_global_kernel<T, BINSRC, STFT, CST64>), grid, dim3(256), 0,
@@ -845,7 +870,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 117; }   // 117: ssq_reassign_cwt, ssq_reassign_cwt_tile; 116: ssq_stft_generic_shape; 115: ssq_reassign2d, ssq_reassign2d_tile; 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 118; }   // 118: ssq_reassign_route, ssq_indexed_sum_bins; 117: ssq_reassign_cwt, ssq_reassign_cwt_tile; 116: ssq_stft_generic_shape; 115: ssq_reassign2d, ssq_reassign2d_tile; 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -1022,6 +1047,33 @@ int ssq_indexed_sum(int dtype, const void* Wx, const void* w, void* Tx, const vo
     SsqParams sp;
     if (fill_params(sp, grid, params, flipud, 0.0, cst_f64)) return -1;
     return launch_accumulate(dtype, BIN_FROM_W, Wx, w, nullptr, Tx, cst, sp, batch, na, n, nullptr, as_stream(stream));
+}
+
+int ssq_indexed_sum_bins(int dtype, const void* Wx, const void* kidx, void* Tx, const void* cst, int cst_f64,
+                         int64_t batch, int64_t na, int64_t n, void* stream) {
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(Wx && kidx && Tx && cst, "ssq_indexed_sum_bins: null pointer");
+    const double no_grid[5] = {0.0, 1.0, 0.0, 0.0, 0.0};        // (the bins are given: no grid is read)
+    SsqParams sp;
+    if (fill_params(sp, SSQ_GRID_LIN, no_grid, 0, 0.0, cst_f64)) return -1;
+    return launch_accumulate(dtype, BIN_FROM_KIDX, Wx, kidx, nullptr, Tx, cst, sp, batch, na, n, nullptr, as_stream(stream));
+}
+
+int ssq_reassign_route(int dtype, int binsrc, int64_t na, int64_t n, int ordered, int want_kmap, int* kernel, int* cols,
+                       int* wavefronts) {
+    if (kernel) *kernel = -1;
+    if (cols) *cols = 0;
+    if (wavefronts) *wavefronts = 0;
+    if (check_dtype(dtype)) return -1;
+    SSQ_REQUIRE(binsrc == BIN_FROM_DWX || binsrc == BIN_FROM_W || binsrc == BIN_FROM_KIDX,
+                "ssq_reassign_route: binsrc = %d, 0 (dWx), 1 (stored w) or 2 (bin map)", binsrc);
+    SSQ_REQUIRE(na >= 1 && n >= 1, "ssq_reassign_route: empty shape (%lld, %lld)", (long long)na, (long long)n);
+    SSQ_REQUIRE(binsrc != BIN_FROM_KIDX || na < 65535, "bin map needs na < 65535");
+    const ReassignRoute r = reassign_route(dtype == SSQ_F32 ? 4 : 8, binsrc, na, n, ordered != 0, want_kmap != 0);
+    if (kernel) *kernel = r.kernel;
+    if (cols) *cols = r.cols;
+    if (wavefronts) *wavefronts = r.wavefronts;
+    return 0;
 }
 
 int ssq_multi_squeeze_max_rows(int dtype) {

@@ -50,10 +50,49 @@ __device__ __forceinline__ int64_t bin_from_w(double w, const SsqParams& sp, int
     return bin_from_wl(log2(w), sp, omax);
 }
 
+// log2 of a float32 with the CPU path's bits. The CPU path takes glibc's log2f (numba types np.log2(float32) as
+// float32), which is not correctly rounded, and the device library's log2f differs from it by an ulp on some arguments:
+// a stored w within an ulp of a bin edge then lands in the neighbouring bin, and a grid of `na` rows has `na` edges
+// (from 1280 rows on, tests/test_gpu_reassign_rows.py found such points in planes of 1e5). This is glibc's own
+// algorithm (the log2f of ARM's optimized-routines, MIT, in glibc since 2.27): a 16-entry table of 1 / c and log2 c, a
+// degree-4 polynomial in r = z / c - 1, all in float64, one rounding. Compiled without contraction it returns glibc's
+// value for EVERY positive normal float32 (all 2^31 - 2^24 of them compared on the host, with and without fused
+// multiply-adds in glibc's build); anything else -- 0, subnormal, negative, inf, NaN -- goes to the library's log2f,
+// whose special values are the same.
+__device__ __forceinline__ float log2f_cpu_bits(float x) {
+    constexpr double tab[16][2] = {                  // {1 / c, log2 c}
+        {0x1.661ec79f8f3bep+0, -0x1.efec65b963019p-2}, {0x1.571ed4aaf883dp+0, -0x1.b0b6832d4fca4p-2},
+        {0x1.49539f0f010bp+0, -0x1.7418b0a1fb77bp-2},  {0x1.3c995b0b80385p+0, -0x1.39de91a6dcf7bp-2},
+        {0x1.30d190c8864a5p+0, -0x1.01d9bf3f2b631p-2}, {0x1.25e227b0b8eap+0, -0x1.97c1d1b3b7afp-3},
+        {0x1.1bb4a4a1a343fp+0, -0x1.2f9e393af3c9fp-3}, {0x1.12358f08ae5bap+0, -0x1.960cbbf788d5cp-4},
+        {0x1.0953f419900a7p+0, -0x1.a6f9db6475fcep-5}, {0x1p+0, 0x0p+0},
+        {0x1.e608cfd9a47acp-1, 0x1.338ca9f24f53dp-4},  {0x1.ca4b31f026aap-1, 0x1.476a9543891bap-3},
+        {0x1.b2036576afce6p-1, 0x1.e840b4ac4e4d2p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.40645f0c6651cp-2},
+        {0x1.886e6037841edp-1, 0x1.88e9c2c1b9ff8p-2},  {0x1.767dcf5534862p-1, 0x1.ce0a44eb17bccp-2}};
+    constexpr double A0 = -0x1.712b6f70a7e4dp-2, A1 = 0x1.ecabf496832ep-2, A2 = -0x1.715479ffae3dep-1,
+                     A3 = 0x1.715475f35c8b8p0;
+    unsigned ix;
+    memcpy(&ix, &x, 4);
+    if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) return log2f(x);     // not a positive normal number
+    if (ix == 0x3f800000u) return 0.f;
+    const unsigned tmp = ix - 0x3f330000u;           // x = 2^k z with z in [0.7, 1.4): k and the table entry from the bits
+    const int i = (int)((tmp >> 19) & 15u);
+    const unsigned iz = ix - (tmp & 0xff800000u);
+    const int k = (int)tmp >> 23;
+    float zf;
+    memcpy(&zf, &iz, 4);
+    const double r = (double)zf * tab[i][0] - 1.0, y0 = tab[i][1] + (double)k, r2 = r * r;
+    double y = A1 * r + A2;
+    y = A0 * r2 + y;
+    const double p = A3 * r + y0;
+    y = y * r2 + p;
+    return (float)y;
+}
+
 // bins from a stored phase transform: numba types np.log2(float32) as float32
 __device__ __forceinline__ int64_t bin_from_stored_w(float w, const SsqParams& sp, int64_t omax) {
     if (sp.grid == SSQ_GRID_LIN) return clamp_round(((double)w - sp.p[0]) / sp.p[1], omax);
-    return bin_from_wl((double)log2f(w), sp, omax);
+    return bin_from_wl((double)log2f_cpu_bits(w), sp, omax);
 }
 __device__ __forceinline__ int64_t bin_from_stored_w(double w, const SsqParams& sp, int64_t omax) {
     return bin_from_w(w, sp, omax);

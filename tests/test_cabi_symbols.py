@@ -48,6 +48,34 @@ def test_stft_generic_shape_needs_no_device():
         assert (list(radix), npass.value, G.value) == ([0] * 10, 0, 0)
 
 
+def test_reassign_route_and_bins_entry_need_no_device():
+    """`ssq_reassign_route` and `ssq_indexed_sum_bins` (ABI 118): the route of the reassignment kernels for a shape,
+    answered on the host -- both sides of the float32 32- to 16-column edge, the unordered float64 tile's last row
+    count, the global kernel, a refusal (tests/test_reassign_rows_design.py: every row count against the rule)."""
+    from ssqueezepy_amd import build, _lib
+    lib = ctypes.CDLL(build.build(verbose=False))
+    lib.ssq_version.restype = ctypes.c_int
+    assert lib.ssq_version() >= 118 and _lib.ABI_VERSION >= 118
+    assert 'ssq_reassign_route' in _lib.EXPORTS and 'ssq_indexed_sum_bins' in _lib.EXPORTS
+    assert hasattr(lib, 'ssq_indexed_sum_bins')
+    fn = lib.ssq_reassign_route
+    fn.restype, fn.argtypes = _lib._PROTOS['ssq_reassign_route']
+    kernel, cols, waves = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    out = (ctypes.byref(kernel), ctypes.byref(cols), ctypes.byref(waves))
+    names = _lib.REASSIGN_KERNELS
+    assert names == ('tile16', 'tile', 'f64', 'global')
+    for args, want in (((_lib.F32, _lib.BIN_FROM_DWX, 320, 100, 0, 0), ('tile16', 32, 4)),
+                       ((_lib.F32, _lib.BIN_FROM_DWX, 321, 100, 0, 0), ('tile16', 16, 2)),
+                       ((_lib.F64, _lib.BIN_FROM_KIDX, 1280, 100, 0, 0), ('f64', 8, 8)),
+                       ((_lib.F64, _lib.BIN_FROM_KIDX, 1280, 100, 1, 0), ('tile', 8, 1)),
+                       ((_lib.F64, _lib.BIN_FROM_KIDX, 1280, 100, 0, 1), ('tile', 8, 1)),
+                       ((_lib.F32, _lib.BIN_FROM_W, 5121, 100, 0, 0), ('global', 1, 4)),
+                       ((_lib.F32, _lib.BIN_FROM_W, 640, 1 << 22, 0, 0), ('tile', 16, 1))):
+        assert fn(*args, *out) == 0
+        assert (names[kernel.value], cols.value, waves.value) == want, args
+    assert fn(7, 0, 10, 10, 0, 0, *out) == -1 and (kernel.value, cols.value, waves.value) == (-1, 0, 0)
+
+
 def test_product_path_never_imports_the_oracle():
     pkg = os.path.join(ROOT, 'ssqueezepy_amd')
     for dirpath, _, files in os.walk(pkg):
