@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 117 (116: without ssq_reassign_cwt; 115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 119 (118: without ssq_multi_squeeze_cwt; 117: without ssq_reassign_route / ssq_indexed_sum_bins; 116: without ssq_reassign_cwt; 115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -459,6 +459,53 @@ int ssq_multi_squeeze(int dtype, const void* Sx, const void* w, void* Tx, void* 
 /* The most rows ssq_multi_squeeze takes: what a 4-column tile holds in 160 KiB of LDS, 160 KiB / (4 * 3 * sizeof real) =
  * 3413 (float32) or 1706 (float64); 0 for an unknown dtype. */
 int ssq_multi_squeeze_max_rows(int dtype);
+
+/* Multisynchrosqueezing on a table of rows (ABI 119): ssq_multi_squeeze for planes whose rows
+ * are not evenly spaced -- the CWT, whose row i sits at wc fs / (2 pi scales[i]): descending, geometric on 'log' scales,
+ * two geometric pieces on 'log-piecewise', hyperbolic on linear scales.
+ *   Wx, w, Tx, wf, cst, cst_f64, batch, rows, n, n_iter, interp, grid, params, flipud, stream   ssq_multi_squeeze's
+ *           (w: the phase transform ssq_phase_cwt or ssq_cwt2_phase wrote)
+ *   fr      HOST array of `rows` float64: the rows' centre frequencies, finite and strictly monotone in either
+ *           direction. Uploaded once per (device, contents) and kept; a call that finds its table enqueues no copy.
+ *           The iteration runs on it, the final binning on `params`; the two need not coincide
+ * Per signal and column, for every row i ascending with w[i] finite, in float64 for both dtypes (a float32 w is
+ * promoted), basic IEEE operations only, no contraction; lo, hi the smaller and larger of fr[0], fr[rows - 1]:
+ *       f = w[i]
+ *       repeat at most n_iter - 1 times:
+ *           if not (f >= lo and f <= hi): break                 NaN included
+ *           i0 = the largest i <= rows - 2 with fr[i] >= f      (descending table; fr[i] <= f for an ascending one)
+ *           a  = (f - fr[i0]) / (fr[i0 + 1] - fr[i0])           in [0, 1]
+ *           r  = i0 + 1 if a > 0.5 or (a == 0.5 and i0 is odd), else i0        half to the even row
+ *           g  = w[r]
+ *           interp = 1:  if w[i0] and w[i0 + 1] are both finite:  g = w[i0] + a * (w[i0 + 1] - w[i0])
+ *           if g is not finite: break
+ *           if g == f: break
+ *           f = g
+ *       fT = f rounded once to `dtype`;  wf[i] = fT  (inf where w[i] was not finite)
+ *       k  = the bin of fT exactly as ssq_indexed_sum bins a stored w (flipud included)
+ *       Tx[k] += Wx[i] * cst[i]                                 term, sum type and order (ascending i): ssq_indexed_sum's
+ * i0 is defined by comparisons against the table alone: the kernel finds it by a branch-free binary search of
+ * ceil(log2(rows - 1)) reads, or, on a table that is geometric in one or two pieces, from a closed-form guess that it
+ * checks against the table and abandons for the search when it is off by more than a row; however it is found, the bits
+ * are the same. With n_iter = 1, Tx is ssq_indexed_sum's bit
+ * for bit. Bit-reproducible from call to call; `batch` signals in one call equal `batch` calls of one signal. The
+ * kernel is ssq_multi_squeeze's with another position rule: the table sits in LDS once per workgroup as float64, so a
+ * row costs cols * 3 * sizeof(real) + 8 bytes. Refused, with Tx and wf unwritten and a message that begins with the
+ * entry's name: a null Wx, w, Tx, cst, fr or params; batch or n < 1, or rows < 2; rows >
+ * ssq_multi_squeeze_cwt_max_rows(dtype); batch rows n >= 2^32; n_iter outside 1 .. 1024; interp outside {0, 1}; an fr
+ * entry that is not finite, or a table that is not strictly monotone; an unknown `grid`. No counterpart in the
+ * reference. */
+int ssq_multi_squeeze_cwt(int dtype, const void* Wx, const void* w, void* Tx, void* wf,
+                          const void* cst, int cst_f64, const double* fr,
+                          int64_t batch, int64_t rows, int64_t n, int64_t n_iter, int interp,
+                          int grid, const double* params, int flipud, void* stream);
+/* The most rows ssq_multi_squeeze_cwt takes: what a 4-column tile holds next to the table, 160 KiB / (4 * 3 * sizeof
+ * real + 8) = 2925 (float32) or 1575 (float64); 0 for an unknown dtype. */
+int ssq_multi_squeeze_cwt_max_rows(int dtype);
+/* The columns of the tile the launcher takes for `rows` rows, the widest that fits: 16 up to 819 (float32) / 417
+ * (float64) rows, 8 up to 1575 / 819, 4 up to the most rows; 0 = refused (rows < 2, too many rows, an unknown dtype).
+ * No device needed. */
+int ssq_multi_squeeze_cwt_tile(int dtype, int64_t rows);
 
 /* w[q] = replacement where |ref[q]| < value.
  * replaces replace_under_abs (algos.py:498-579). */

@@ -29,6 +29,7 @@ def __getattr__(name):
         'conceft_cwt': '_conceft_cwt', 'morse_wavelets': 'wavelets', 'conceft_cwt_gpu': 'algos',
         'tssq_stft': '_tssq_stft', 'time_reassign_gpu': 'algos',
         'msst_stft': '_msst_stft', 'multi_squeeze_gpu': 'algos',
+        'msst_cwt': '_msst_cwt', 'multi_squeeze_cwt_gpu': 'algos', 'row_frequencies': 'wavelets',
         'reassign_stft': '_reassign_stft', 'reassign2d_gpu': 'algos',
         'reassign_cwt': '_reassign_cwt', 'reassign_cwt_gpu': 'algos', 'wavelet_time_std': 'wavelets',
         'ssqueeze_fast': 'algos', 'indexed_sum_onfly': 'algos', 'buffer': 'algos',

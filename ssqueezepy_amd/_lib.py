@@ -115,6 +115,10 @@ _PROTOS = {
                                   c_int64, c_double, c_double, c_int64, c_int, c_int, POINTER(c_double), c_int,
                                   c_void_p]),
     'ssq_multi_squeeze_max_rows': (c_int, [c_int]),
+    'ssq_multi_squeeze_cwt': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                      c_int64, c_int64, c_int64, c_int, c_int, POINTER(c_double), c_int, c_void_p]),
+    'ssq_multi_squeeze_cwt_max_rows': (c_int, [c_int]),
+    'ssq_multi_squeeze_cwt_tile': (c_int, [c_int, c_int64]),
     'ssq_replace_under_abs': (c_int, [c_int, c_void_p, c_void_p, c_int64,
                                       c_double, c_double, c_void_p]),
     'ssq_buffer': (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64,
@@ -189,7 +193,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 118    # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 119    # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

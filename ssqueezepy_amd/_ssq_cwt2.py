@@ -22,6 +22,57 @@ from .wavelets import Wavelet, derived_wavelets
 __all__ = ['ssq_cwt2']
 
 
+def _cwt_phase_map(x, wavelet, scales, nv, fs, t, ssq_freqs, padtype, maprange, gamma, chirp_tol,
+                   cache_wavelet, get_w, order=2):
+    """The host steps of `ssq_cwt2` up to its reassignment, for it and for `msst_cwt`: the
+    checks, the design, the default of `gamma`, the plans, the executions and the map.
+    ``order=2``: three executions and `phase_cwt2_gpu` (a wavelet with closed-form companions);
+    ``order=1``: one and `phase_cwt_gpu` (any wavelet). Returns ``(Wx, w, ssq_freqs, scales_dt, const,
+    grid, wavelet, fs)`` with `ssq_freqs` ascending, as the bins are taken."""
+    if order not in (1, 2):
+        raise ValueError("`order` must be 1 or 2 (got %r)" % (order,))
+    if not hasattr(x, 'ndim'):
+        raise TypeError("`x` must be a numpy array or torch Tensor "
+                        "(got %s)" % type(x))
+    elif x.ndim not in (1, 2):
+        raise ValueError("`x` must be 1D or 2D (got x.ndim == %s)" % x.ndim)
+    _check_ssqueezing_args('sum', maprange, wavelet, 'trig', None, get_w, transform='cwt')
+    if padtype is not None and padtype not in PADTYPES:
+        raise ValueError("`padtype` must be one of: %s (got %s)"
+                         % (', '.join(PADTYPES), padtype))
+    if nv is None and not isinstance(scales, np.ndarray):
+        nv = 32
+    N = x.shape[-1]
+    dt, fs, t = _process_fs_and_t(fs, t, N)
+
+    wavelet = _process_gmw_wavelet(wavelet, True)
+    wavelet = Wavelet._init_if_not_isinstance(wavelet, N=N)
+    # (raises for a wavelet without a closed form)
+    companions = derived_wavelets(wavelet) if order == 2 else ()
+    dtype = wavelet.dtype
+    if gamma is None:
+        gamma = 10 * (EPS64 if dtype == 'float64' else EPS32)
+
+    scales_dt, ssq_freqs, const, grid, _ = _ssq_design(wavelet, scales, nv, N, dt, ssq_freqs,
+                                                       maprange, bool(padtype is not None))
+    use_cache = True if cache_wavelet is None else bool(cache_wavelet)
+    xd = algos.to_device(x, _TDT[dtype]).detach()
+    B = xd.shape[0] if xd.ndim == 2 else 1
+    plans = [get_cwt_plan(wv, scales_dt, N, padtype, dt, True, B, cache=use_cache)
+             for wv in (wavelet,) + companions]
+
+    out = plans[0].execute(xd, want_dWx=True)
+    Wx, dW = out['Wx'], out['dWx']
+    if order == 1:
+        return Wx, algos.phase_cwt_gpu(Wx, dW, gamma), ssq_freqs, scales_dt, const, grid, wavelet, fs
+    out = plans[1].execute(xd, want_dWx=True)
+    Wd, dWd = out['Wx'], out['dWx']
+    dW3 = plans[2].execute(xd, want_dWx=True)['dWx']
+    w = algos.phase_cwt2_gpu(Wx, dW, Wd, dWd, dW3, scales_dt, fs, gamma, chirp_tol)
+    del dW, Wd, dWd, dW3, out
+    return Wx, w, ssq_freqs, scales_dt, const, grid, wavelet, fs
+
+
 def ssq_cwt2(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None,
              ssq_freqs=None, padtype='reflect', maprange='peak', gamma=None,
              chirp_tol=1e-3, astensor=True, flipud=True, cache_wavelet=None, get_w=False):
@@ -50,42 +101,9 @@ def ssq_cwt2(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None,
 
     Costs three plan executions (five planes are needed, six are made), the map and the
     reassignment. The outputs carry no `grad_fn`, whatever `x` requires."""
-    if not hasattr(x, 'ndim'):
-        raise TypeError("`x` must be a numpy array or torch Tensor "
-                        "(got %s)" % type(x))
-    elif x.ndim not in (1, 2):
-        raise ValueError("`x` must be 1D or 2D (got x.ndim == %s)" % x.ndim)
-    _check_ssqueezing_args('sum', maprange, wavelet, 'trig', None, get_w, transform='cwt')
-    if padtype is not None and padtype not in PADTYPES:
-        raise ValueError("`padtype` must be one of: %s (got %s)"
-                         % (', '.join(PADTYPES), padtype))
-    if nv is None and not isinstance(scales, np.ndarray):
-        nv = 32
-    N = x.shape[-1]
-    dt, fs, t = _process_fs_and_t(fs, t, N)
-
-    wavelet = _process_gmw_wavelet(wavelet, True)
-    wavelet = Wavelet._init_if_not_isinstance(wavelet, N=N)
-    companions = derived_wavelets(wavelet)      # raises for a wavelet without a closed form
-    dtype = wavelet.dtype
-    if gamma is None:
-        gamma = 10 * (EPS64 if dtype == 'float64' else EPS32)
-
-    scales_dt, ssq_freqs, const, grid, _ = _ssq_design(wavelet, scales, nv, N, dt, ssq_freqs,
-                                                       maprange, bool(padtype is not None))
-    use_cache = True if cache_wavelet is None else bool(cache_wavelet)
-    xd = algos.to_device(x, _TDT[dtype]).detach()
-    B = xd.shape[0] if xd.ndim == 2 else 1
-    plans = [get_cwt_plan(wv, scales_dt, N, padtype, dt, True, B, cache=use_cache)
-             for wv in (wavelet,) + companions]
-
-    out = plans[0].execute(xd, want_dWx=True)
-    Wx, dW = out['Wx'], out['dWx']
-    out = plans[1].execute(xd, want_dWx=True)
-    Wd, dWd = out['Wx'], out['dWx']
-    dW3 = plans[2].execute(xd, want_dWx=True)['dWx']
-    w = algos.phase_cwt2_gpu(Wx, dW, Wd, dWd, dW3, scales_dt, fs, gamma, chirp_tol)
-    del dW, Wd, dWd, dW3, out
+    Wx, w, ssq_freqs, scales_dt, const, grid, _, _ = _cwt_phase_map(
+        x, wavelet, scales, nv, fs, t, ssq_freqs, padtype, maprange, gamma, chirp_tol,
+        cache_wavelet, get_w)
     Tx = algos.indexed_sum_onfly(Wx, w, ssq_freqs, const, grid != GRID_LIN, flipud)
 
     # `scales` go high -> low, so frequencies are returned high -> low

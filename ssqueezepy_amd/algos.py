@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `indexed_sum_bins` (the same sum from a caller's bin map: no counterpart in the reference), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `reassign_cwt_gpu` (the reassigned scalogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` and `multi_squeeze_cwt_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `reassign_cwt_gpu` (the reassigned scalogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'indexed_sum_bins', 'reassign_route', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'indexed_sum_bins', 'reassign_route', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'multi_squeeze_cwt_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -734,6 +734,65 @@ def multi_squeeze_gpu(Sx, w, Sfs, ssq_freqs, const=1, n_iter=10, interp='linear'
     check(lib.ssq_multi_squeeze(_CDT[Sx.dtype], _ptr(Sx), _ptr(w), _ptr(out), _ptr(wf), _ptr(cst), c64, B, rows, n,
                                 float(sfs[0]), float(sfs[1] - sfs[0]), int(n_iter), int(interp == 'linear'), kind, p,
                                 int(bool(flipud)), stream()))
+    return (out, wf) if get_w else out
+
+
+def _row_table(name, v, rows):
+    """`v` as a contiguous float64 host vector of `rows` finite, strictly monotone values (`name` in the message)."""
+    if hasattr(v, 'detach'):
+        v = v.detach().cpu().numpy()
+    v = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.float64)
+    if v.size != rows:
+        raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
+    if not np.isfinite(v).all():
+        raise ValueError("`%s` must be finite" % name)
+    d = np.diff(v)
+    if not ((d > 0).all() or (d < 0).all()):
+        raise ValueError("`%s` must be strictly monotone" % name)
+    return v
+
+
+def multi_squeeze_cwt_gpu(Wx, w, row_freqs, ssq_freqs, const=1, n_iter=10, interp='linear', flipud=False, out=None,
+                          get_w=False):
+    """Multisynchrosqueezing on a table of rows in one kernel (`ssq_multi_squeeze_cwt`, include/ssq_hip.h states the
+    definition): `multi_squeeze_gpu` for the CWT. `Wx`: (rows, n) or (B, rows, n) complex; `w`: its
+    phase transform (`phase_cwt_gpu`, `phase_cwt2_gpu`; ``inf`` = skip), same shape; `row_freqs`: (rows,), the rows'
+    centre frequencies (`wavelets.row_frequencies`), finite and strictly monotone in either direction, sent as float64;
+    `ssq_freqs`: (rows,), the grid the bins are taken on -- linear, 'log' or 'log-piecewise' (inferred from its values,
+    as `reassign_cwt_gpu` does); `const` as `indexed_sum_onfly`'s. Per column, every point's frequency ``f = w[i]`` is
+    replaced ``n_iter - 1`` times by `w` at the place `f` takes between two rows of the table -- interpolated between
+    them (``interp='linear'``) or taken from the nearer (``'nearest'``) --, stopping at a fixed point, outside the
+    table's range or in front of an ``inf``; the point is then added to the bin of its final frequency, a cell's terms
+    in ascending row order. ``n_iter=1`` is `indexed_sum_onfly`. The iteration runs in float64 for both precisions,
+    the final frequency is rounded once; bit-reproducible. Returns `Tx`, or ``(Tx, w_final)`` with `get_w`."""
+    if interp not in ('linear', 'nearest'):
+        raise ValueError("`interp` must be 'linear' or 'nearest' (got %r)" % (interp,))
+    from .scales import infer_scaletype
+    lib = _lib.load()
+    Wx = to_device(Wx)
+    if Wx.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`Wx` must be complex64 or complex128 (got %s)" % Wx.dtype)
+    w = to_device(w, _real_of(Wx.dtype))
+    if Wx.shape != w.shape:
+        raise ValueError("`Wx` and `w` shapes differ")
+    B, rows, n = _shape3(Wx)
+    fr = _row_table('row_freqs', row_freqs, rows)
+    if hasattr(ssq_freqs, 'detach'):
+        ssq_freqs = ssq_freqs.detach().cpu().numpy()
+    ssq_freqs = np.asarray(ssq_freqs).reshape(-1)
+    if ssq_freqs.size != rows:
+        raise ValueError("`ssq_freqs` must have one entry per row (%d != %d)" % (ssq_freqs.size, rows))
+    # (two values are evenly spaced in any metric: they are taken as a linear grid)
+    kind, p = _grid(ssq_freqs, rows > 2 and infer_scaletype(ssq_freqs)[0].startswith('log'))
+    if out is None:
+        out = torch.empty_like(Wx)
+    else:
+        _check_out(out, Wx)
+    wf = torch.empty_like(w) if get_w else None
+    cst, c64 = _const_vector(const, rows, Wx.dtype)
+    check(lib.ssq_multi_squeeze_cwt(_CDT[Wx.dtype], _ptr(Wx), _ptr(w), _ptr(out), _ptr(wf), _ptr(cst), c64,
+                                    fr.ctypes.data, B, rows, n, int(n_iter), int(interp == 'linear'), kind, p,
+                                    int(bool(flipud)), stream()))
     return (out, wf) if get_w else out
 
 

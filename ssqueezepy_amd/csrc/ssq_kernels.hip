@@ -17,7 +17,9 @@
 //       Tx once -- no read-modify-write, no atomics, deterministic.
 //   accumulate_global_kernel fallback for `na` too large for an LDS tile.
 //   multi_squeeze_kernel     (ssq_multi_squeeze.inl) the ordered accumulate from `w` iterated on itself: a second LDS
-//       slab per wavefront holds its columns of `w`, the iteration is a loop of LDS gathers.
+//       slab per wavefront holds its columns of `w`, the iteration is a loop of LDS gathers. Templated on how a
+//       frequency becomes a row position: rows at f0 + i df (ssq_multi_squeeze) or at a monotone table kept in LDS and
+//       searched per pass (ssq_multi_squeeze_cwt).
 //   phase_kernel             w = |Im(dWx/Wx)|/2pi (CWT) or |Sfs - ...| (STFT).
 //   stft2_phase_kernel       second-order w of the STFT from five transform planes, float64 in registers.
 //   cwt2_phase_kernel        second-order w of the CWT from five transform planes and the rows' scales, likewise.
@@ -870,7 +872,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 118; }   // 118: ssq_reassign_route, ssq_indexed_sum_bins; 117: ssq_reassign_cwt, ssq_reassign_cwt_tile; 116: ssq_stft_generic_shape; 115: ssq_reassign2d, ssq_reassign2d_tile; 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 119; }   // 119: ssq_multi_squeeze_cwt, ssq_multi_squeeze_cwt_max_rows, ssq_multi_squeeze_cwt_tile; 118: ssq_reassign_route, ssq_indexed_sum_bins; 117: ssq_reassign_cwt, ssq_reassign_cwt_tile; 116: ssq_stft_generic_shape; 115: ssq_reassign2d, ssq_reassign2d_tile; 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {
@@ -1102,7 +1104,59 @@ int ssq_multi_squeeze(int dtype, const void* Sx, const void* w, void* Tx, void* 
         using T = decltype(t);
         return dispatch_bool(cst_f64 != 0, [&](auto c) {
             constexpr bool C64 = decltype(c)::value && sizeof(T) == 4;    // (as launch_accumulate_b)
-            return launch_multi_squeeze<T, C64>(Sx, w, Tx, wf, cst, sp, batch, rows, n, f0, df, n_iter, interp,
+            return launch_multi_squeeze<T, C64>(Sx, w, Tx, wf, cst, sp, batch, rows, n, MsstLinearRows{f0, df}, n_iter,
+                                                interp, as_stream(stream));
+        });
+    });
+}
+
+int ssq_multi_squeeze_cwt_max_rows(int dtype) {
+    if (dtype == SSQ_F32) return (int)msst_tile_rows<float>(MSST_WC, MsstTableRows::ROW_BYTES);
+    return dtype == SSQ_F64 ? (int)msst_tile_rows<double>(MSST_WC, MsstTableRows::ROW_BYTES) : 0;
+}
+
+int ssq_multi_squeeze_cwt_tile(int dtype, int64_t rows) {
+    if (rows < 2) return 0;
+    if (dtype == SSQ_F32) return msst_tile_cols<float, MsstTableRows>(rows);
+    return dtype == SSQ_F64 ? msst_tile_cols<double, MsstTableRows>(rows) : 0;
+}
+
+// The rows' centre frequencies on the current device: checked on the host, uploaded once per (device, contents), kept
+static DeviceTableCache g_msst_cwt_tables;
+
+int ssq_multi_squeeze_cwt(int dtype, const void* Wx, const void* w, void* Tx, void* wf, const void* cst, int cst_f64,
+                          const double* fr, int64_t batch, int64_t rows, int64_t n, int64_t n_iter, int interp, int grid,
+                          const double* params, int flipud, void* stream) {
+    SSQ_REQUIRE(dtype == SSQ_F32 || dtype == SSQ_F64, "ssq_multi_squeeze_cwt: dtype must be SSQ_F32 or SSQ_F64 (got %d)", dtype);
+    SSQ_REQUIRE(Wx && w && Tx && cst && fr && params, "ssq_multi_squeeze_cwt: null pointer");
+    SSQ_REQUIRE(batch >= 1 && rows >= 2 && n >= 1, "ssq_multi_squeeze_cwt: bad shape (%lld, %lld, %lld): rows >= 2, batch, n >= 1",
+                (long long)batch, (long long)rows, (long long)n);
+    SSQ_REQUIRE(rows <= ssq_multi_squeeze_cwt_max_rows(dtype),
+                "ssq_multi_squeeze_cwt: %lld rows, at most %d (a 4-column tile of Tx and w and the rows' table in LDS)",
+                (long long)rows, ssq_multi_squeeze_cwt_max_rows(dtype));
+    if (check_point_count("ssq_multi_squeeze_cwt", batch, rows, n)) return -1;
+    SSQ_REQUIRE(n_iter >= 1 && n_iter <= MSST_MAX_ITER, "ssq_multi_squeeze_cwt: n_iter = %lld, 1 .. %lld", (long long)n_iter,
+                (long long)MSST_MAX_ITER);
+    SSQ_REQUIRE(interp == 0 || interp == 1, "ssq_multi_squeeze_cwt: interp = %d, 0 (nearest row) or 1 (linear)", interp);
+    const int desc = fr[1] < fr[0];
+    for (int64_t i = 0; i < rows; ++i) {
+        SSQ_REQUIRE(fabs(fr[i]) <= DBL_MAX, "ssq_multi_squeeze_cwt: fr[%lld] = %g: the rows' frequencies must be finite",
+                    (long long)i, fr[i]);
+        SSQ_REQUIRE(i == 0 || (desc ? fr[i] < fr[i - 1] : fr[i] > fr[i - 1]),
+                    "ssq_multi_squeeze_cwt: fr[%lld] = %g after %g: the rows' frequencies must be strictly monotone",
+                    (long long)i, fr[i], fr[i - 1]);
+    }
+    SsqParams sp;
+    if (fill_params(sp, grid, params, flipud, 0.0, cst_f64, "ssq_multi_squeeze_cwt")) return -1;
+    const double* fr_dev = nullptr;
+    if (g_msst_cwt_tables.get(fr, (size_t)rows, &fr_dev)) return -1;
+    const MsstTableRows pos{fr_dev, desc ? fr[rows - 1] : fr[0], desc ? fr[0] : fr[rows - 1], desc, msst_fit_hint(fr, rows),
+                            nullptr};
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return dispatch_bool(cst_f64 != 0, [&](auto c) {
+            constexpr bool C64 = decltype(c)::value && sizeof(T) == 4;    // (as launch_accumulate_b)
+            return launch_multi_squeeze<T, C64>(Wx, w, Tx, wf, cst, sp, batch, rows, n, pos, n_iter, interp,
                                                 as_stream(stream));
         });
     });

@@ -26,7 +26,8 @@ from .configs import fill_defaults
 pi = np.pi
 
 __all__ = ['Wavelet', 'center_frequency', 'xi_grid', 'find_maximum',
-           'find_first_occurrence', 'morsefreq', 'derived_wavelets', 'morse_wavelets', 'wavelet_time_std']
+           'find_first_occurrence', 'morsefreq', 'derived_wavelets', 'morse_wavelets', 'wavelet_time_std',
+           'row_frequencies']
 
 
 # --------------------------------------------------------------------- grids
@@ -603,3 +604,16 @@ def center_frequency(wavelet, scale=None, N=1024, kind='energy', force_int=None)
     # accepted for signature compatibility only
     w, e = sampled(scale)
     return float(integrate.trapezoid(e * w) / integrate.trapezoid(e))
+
+
+def row_frequencies(wavelet, scales, fs=1.):
+    """The centre frequencies of the rows of a CWT, float64, in the unit of `fs`:
+    ``center_frequency(wavelet, kind='peak-ct') * fs / (2 pi scales[i])`` with `scales` in samples
+    -- the wavelet's continuous-time peak over the scale. They are what a row stands for (and what
+    `msst_cwt` iterates on); `ssq_freqs` is what a bin of `ssq_cwt` stands for, and the two differ:
+    the grid's top is clipped at Nyquist."""
+    wc = center_frequency(wavelet, kind='peak-ct')
+    if hasattr(scales, 'detach'):
+        scales = scales.detach().cpu().numpy()
+    sc = np.asarray(scales, dtype=np.float64).reshape(-1)
+    return float(wc) * float(fs) / (2 * np.pi * sc)
