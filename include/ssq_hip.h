@@ -59,7 +59,7 @@ extern "C" {
 #define SSQ_PAD_WRAP 4
 
 /* ------------------------------------------------------------------ runtime */
-int         ssq_version(void);          /* 119 (118: without ssq_multi_squeeze_cwt; 117: without ssq_reassign_route / ssq_indexed_sum_bins; 116: without ssq_reassign_cwt; 115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
+int         ssq_version(void);          /* 120 (119: without ssq_time_reassign_cwt; 118: without ssq_multi_squeeze_cwt; 117: without ssq_reassign_route / ssq_indexed_sum_bins; 116: without ssq_reassign_cwt; 115: without ssq_stft_generic_shape; 114: without ssq_reassign2d; 113: without ssq_multi_squeeze; 112: without ssq_time_reassign; 111: without ssq_conceft_cwt; 110: without ssq_conceft; 109: without ssq_cwt2_phase; 108: without ssq_stft2_phase; 107: without ssq_cwt_adjoint; 106: without the batched inverses and their adjoints: ssq_istft_batch / ssq_istft_adjoint / ssq_istft_algo / ssq_colsum_adjoint / ssq_band_colsum_batch / ssq_band_colsum_adjoint; 105: without ssq_stft_adjoint / ssq_ssqueeze_adjoint; 104: without ssq_cwt_plan_tile_kernel; 103: without ssq_build_sha / ssq_cwt_plan_set_bin_dump; 102: without ssq_ridge_*_batch; 101: without ssq_cwt_plan_tile_cols; 100: block classes without the `analytic` column) */
 /* The git commit of the device code this library was built from: the last commit that touched
  * ssqueezepy_amd/csrc or include/ ("<sha>-dirty" when the build tree had uncommitted changes there,
  * "unknown" when built outside a git checkout). Measurement records carry it (bench.py, profiles/):
@@ -349,6 +349,60 @@ int ssq_reassign_cwt(int dtype, const void* W, const void* dW, const void* Wd, c
  * smallest home and above it + the tile's rows) and in columns (on either side); 4: the most workgroups of the windowed
  * scatter; 5, 6: the window's bins and columns; anything else: 0. */
 int ssq_reassign_cwt_tile(int which);
+
+/* The time-reassigned synchrosqueezed CWT (ABI 120): the CWT counterpart of ssq_time_reassign.
+ * Every coefficient of a CWT moves along its row to its group delay, rotated to the signal's origin first, and the complex
+ * terms that meet in a cell are added in signed fixed point: ssq_reassign_cwt's accumulator, re and im summed separately.
+ *   W, Wd   (batch, rows, n) complex `dtype`, device: the CWT over psih(w) and the CWT over psih'(w)
+ *   rsc     (rows,) float64, device: the scale of row i in samples (columns)
+ *   dmax    (rows,) int32, HOST: the largest displacement kept in row i, in columns; uploaded once per content
+ *   rot_lo  (rows, P) and rot_hi (rows, ceil(n / P)) complex128, device, P = SSQ_TSSQ_CWT_ROT_P: the two-level table of
+ *           the rotation of row i, rot(i, c) = rot_hi[i, c / P] * rot_lo[i, c mod P] = e^{-2 pi i phi_i c}, phi_i the
+ *           row's centre frequency in cycles per column: rot_lo[i, p] = exp(-2 pi i frac(phi_i p)), rot_hi[i, q] =
+ *           exp(-2 pi i frac(phi_i P q)), the fractional parts exact. Both NULL: no rotation
+ *   Tx      (batch, rows, n) complex `dtype`; overwritten
+ *   acc     (batch, rows, n, 2) int64 and peak (batch,) uint64: caller-owned scratch, overwritten; readable afterwards
+ *   flags   SSQ_TSSQ_CWT_NO_WINDOW: every term goes to `acc` with global atomics, none through the LDS window -- the same
+ *           bits; for measurements
+ * Evaluated in float64 for both dtypes (float32 planes are promoted per point), basic IEEE operations only, no
+ * contraction. Per signal b, for every point of row i, column c:
+ *       gr, gi = W[b,i,c];  e = gr*gr + gi*gi
+ *       kept   = not (|W| < gamma) and e finite          |W| as ssq_time_reassign takes it
+ *       d      = rint(((ti*gr - tr*gi) / e) * rsc[i])    tr, ti = Wd[b,i,c]; round half to even: ssq_reassign_cwt's d
+ *       dropped: not (|d| <= dmax[i]) (NaN included);  c + d outside [0, n)
+ *       (ur,ui) = (hr*lr - hi*li, hr*li + hi*lr)         (hr,hi) = rot_hi[i, c / P], (lr,li) = rot_lo[i, c mod P];
+ *                                                        (1, 0) when the tables are NULL
+ *       (zr,zi) = (ur*gr - ui*gi, ur*gi + ui*gr)
+ *       Tx[b, i, c + d] += (zr, zi)                      a point stays in its row
+ * The sum of a cell is a signed fixed-point sum, re and im separately:
+ *       emax = the largest e over the kept points of signal b (dropped ones included);  peak[b] = its bits, 0 if none
+ *       ex   = frexp(emax)'s exponent;  hx = ceil(ex / 2):  |zr|, |zi| <= |u| sqrt(emax) < 2^hx (1 + a few ulp)
+ *       C    = max_i min(2 dmax[i] + 1, n), the most terms a cell can receive;  H = bit_length(C)
+ *       sh   = 61 - H - hx
+ *       q    = (int64) ldexp(z, sh), truncated toward zero, per component; a zero component adds nothing
+ *       acc[b,i,c2,0..1] = the int64 sums;  |sum| <= C 2^(61 - H) (1 + a few ulp) < 2^61 (1 + a few ulp) < 2^62
+ *       Tx   = (dtype) ldexp((double) acc, -sh), per component
+ * The spare bit (61, not 62) pays for |u| not being exactly 1 and for an odd ex. A cell that received t terms is within
+ * t 2^-sh of the exact sum in each component, before the one rounding to `dtype`; 2^-sh <= sqrt(emax) 2^(H - 60). A
+ * signal without a kept point gives zeros. Bit-reproducible, independent of grid, tiling and schedule; `batch` signals in
+ * one call equal `batch` calls of one signal bit for bit. Three launches and two clears on `stream`, no host
+ * synchronisation once the dmax table is on the device: the peak (ssq_reassign2d's), the scatter (a workgroup per tile of
+ * ssq_time_reassign_cwt_tile(0) x ssq_time_reassign_cwt_tile(1) sources, tiles starting at multiples of P, adds into an
+ * LDS window of the tile's rows x ssq_time_reassign_cwt_tile(3) columns that starts ssq_time_reassign_cwt_tile(2) columns
+ * left of the tile; a term outside it is two global 64-bit integer atomics) and the conversion. Planes that do not start
+ * on a 16-byte boundary take an element-load instance. Refused, with nothing written and a message that begins with the
+ * entry's name: a null W, Wd, rsc, dmax, Tx, acc or peak; exactly one of rot_lo and rot_hi null; batch, rows or n < 1;
+ * batch rows n >= 2^31 (a cell is two words of a (rows, 2 n) view indexed in 32 bits); gamma < 0 or NaN; a dmax[i] < 0 or
+ * > ssq_time_reassign_max_dmax(); unknown flags. No counterpart in the reference. */
+#define SSQ_TSSQ_CWT_NO_WINDOW 1
+#define SSQ_TSSQ_CWT_ROT_P 256
+int ssq_time_reassign_cwt(int dtype, const void* W, const void* Wd, const double* rsc, const int32_t* dmax,
+                          const void* rot_lo, const void* rot_hi, void* Tx, void* acc, void* peak, int64_t batch,
+                          int64_t rows, int64_t n, double gamma, int flags, void* stream);
+/* The scatter's sizes: which = 0, 1: the rows and columns of a tile of sources; 2: the window's halo in columns, on either
+ * side; 3: the window's columns (the tile's plus the halo twice); 4: the most workgroups of the windowed scatter; 5: P, the columns of rot_lo
+ * (= SSQ_TSSQ_CWT_ROT_P = which 1); anything else: 0. */
+int ssq_time_reassign_cwt_tile(int which);
 
 /* Fused phase transform + bin search + accumulate:
  *   for every (i, j) with |Wx[i,j]| > gamma:  Tx[k(i,j), j] += Wx[i,j] * cst[i]

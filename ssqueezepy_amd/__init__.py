@@ -32,6 +32,7 @@ def __getattr__(name):
         'msst_cwt': '_msst_cwt', 'multi_squeeze_cwt_gpu': 'algos', 'row_frequencies': 'wavelets',
         'reassign_stft': '_reassign_stft', 'reassign2d_gpu': 'algos',
         'reassign_cwt': '_reassign_cwt', 'reassign_cwt_gpu': 'algos', 'wavelet_time_std': 'wavelets',
+        'tssq_cwt': '_tssq_cwt', 'time_reassign_cwt_gpu': 'algos', 'cwt_rotation_tables': 'algos',
         'ssqueeze_fast': 'algos', 'indexed_sum_onfly': 'algos', 'buffer': 'algos',
         'replace_under_abs': 'algos', 'phase_cwt_gpu': 'algos',
         'phase_stft_gpu': 'algos', 'phase_stft2_gpu': 'algos', 'phase_cwt2_gpu': 'algos',

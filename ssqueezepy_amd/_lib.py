@@ -18,6 +18,7 @@ F32, F64 = 0, 1
 GRID_LOG, GRID_LOG_PIECEWISE, GRID_LIN = 0, 1, 2
 REASSIGN2D_FREQ, REASSIGN2D_NO_WINDOW = 1, 2
 REASSIGN_CWT_FREQ, REASSIGN_CWT_TIME, REASSIGN_CWT_NO_WINDOW = 1, 2, 4
+TSSQ_CWT_NO_WINDOW, TSSQ_CWT_ROT_P = 1, 256                # ssq_time_reassign_cwt's flag; the columns of its `rot_lo`
 BIN_FROM_DWX, BIN_FROM_W, BIN_FROM_KIDX = 0, 1, 2            # ssq_reassign_route's `binsrc`
 REASSIGN_KERNELS = ('tile16', 'tile', 'f64', 'global')        # SSQ_REASSIGN_*, by value
 PAD = {None: -1, 'zero': 0, 'reflect': 1, 'symmetric': 2, 'replicate': 3,
@@ -98,6 +99,9 @@ _PROTOS = {
                                  c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int, POINTER(c_double), c_int,
                                  c_int, c_void_p]),
     'ssq_reassign_cwt_tile': (c_int, [c_int]),
+    'ssq_time_reassign_cwt': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_int, c_void_p]),
+    'ssq_time_reassign_cwt_tile': (c_int, [c_int]),
     'ssq_ssqueeze': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_int, c_int64, c_int64, c_int64, c_double,
                              c_int, POINTER(c_double), c_int, c_void_p, c_void_p]),
@@ -193,7 +197,7 @@ EXPORTS = tuple(_PROTOS)
 _lib = None
 
 
-ABI_VERSION = 119    # include/ssq_hip.h: ssq_version()
+ABI_VERSION = 120    # include/ssq_hip.h: ssq_version()
 
 
 def load(build_if_missing=True):

@@ -4,7 +4,7 @@
 Same names, argument meaning and error behaviour as the functions the reference's
 transforms call (ssqueezepy/algos.py): `ssqueeze_fast` (126-150),
 `indexed_sum_onfly` (153-169), `indexed_sum_bins` (the same sum from a caller's bin map: no counterpart in the reference), `phase_cwt_gpu` (743-781), `phase_stft_gpu`
-(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` and `multi_squeeze_cwt_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `reassign_cwt_gpu` (the reassigned scalogram, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
+(818-856), `phase_stft2_gpu` and `phase_cwt2_gpu` (the second-order maps: no counterpart in the reference), `conceft_gpu` and `conceft_cwt_gpu` (multitaper synchrosqueezing, likewise), `time_reassign_gpu` (time-reassigned synchrosqueezing, likewise), `multi_squeeze_gpu` and `multi_squeeze_cwt_gpu` (multisynchrosqueezing, likewise), `reassign2d_gpu` (the reassigned spectrogram, likewise), `reassign_cwt_gpu` (the reassigned scalogram, likewise), `time_reassign_cwt_gpu` (the time-reassigned synchrosqueezed CWT, likewise), `replace_under_abs` (498-579) and `buffer` (utils/stft_utils.py:20-66).
 Inputs may be NumPy arrays (uploaded) or torch tensors; outputs are torch tensors
 on the GPU. Every function is a thin marshalling layer over one C-ABI call of
 libssq_hip.so, launched on torch's current stream -- there is no CPU
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import check, params5, F32, F64
 
-__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'indexed_sum_bins', 'reassign_route', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'multi_squeeze_cwt_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu',
+__all__ = ['ssqueeze_fast', 'ssqueeze_adjoint', 'indexed_sum_onfly', 'indexed_sum_bins', 'reassign_route', 'phase_cwt_gpu', 'phase_stft_gpu', 'phase_stft2_gpu', 'phase_cwt2_gpu', 'conceft_gpu', 'conceft_cwt_gpu', 'time_reassign_gpu', 'multi_squeeze_gpu', 'multi_squeeze_cwt_gpu', 'reassign2d_gpu', 'reassign_cwt_gpu', 'time_reassign_cwt_gpu', 'cwt_rotation_tables', 'time_reassign_cwt_shift',
            'replace_under_abs', 'buffer', 'pad_signal_gpu', 'to_device', 'colsum_real', 'colsum_adjoint',
            'band_colsum', 'band_colsum_adjoint', 'istft_gpu', 'istft_adjoint_gpu', 'istft_algo']
 
@@ -682,6 +682,126 @@ def reassign_cwt_gpu(W, dW, Wd, scales, cst, dmax, ssq_freqs, gamma, flipud=Fals
     check(lib.ssq_reassign_cwt(_CDT[W.dtype], _ptr(W), _ptr(dW), _ptr(Wd), _ptr(cst_d), _ptr(rsc_d),
                                dm.ctypes.data if time else None, _ptr(home_d), _ptr(out), _ptr(acc), _ptr(peak), B, rows,
                                n, float(gamma), kind, p, int(bool(flipud)), flags, stream()))
+    return (out, acc, peak) if return_acc else out
+
+
+_CWT_ROT_TABLES = {}
+
+
+def _exact_turns(freqs, mult, count):
+    """``frac(freqs[i] * mult * k)`` for ``k = 0 .. count-1``, float64 (rows, count): the fractional part of the exact
+    product, every frequency taken as the float64 it is (a ratio of Python integers), rounded once at the end."""
+    out = np.empty((len(freqs), count), dtype=np.float64)
+    for i, f in enumerate(freqs):
+        num, den = float(f).as_integer_ratio()
+        num *= int(mult)
+        out[i] = [((num * k) % den) / den for k in range(count)]
+    return out
+
+
+def cwt_rotation_tables(row_freqs, n, fs=1.):
+    """``(rot_lo, rot_hi)``, complex128 on the current device: the two-level table of `time_reassign_cwt_gpu`'s rotation
+    ``rot(i, c) = exp(-2j pi phi_i c) = rot_hi[i, c // P] rot_lo[i, c % P]`` with ``phi_i = row_freqs[i] / fs`` cycles
+    per column and ``P = 256``: ``rot_lo`` is (rows, P), ``rot_hi`` (rows, ceil(n / P)), and an entry is ``exp(-2j pi
+    frac)`` with `frac` the exact fractional part of ``phi_i p`` (``phi_i P q``), `phi_i` taken as the float64 it is.
+    ``phi_i`` is not rational in `n`, so no table indexed ``mod n`` serves, and a direct ``exp(-2j pi phi c)`` loses
+    ``c eps`` of a turn; the product of two exactly reduced entries stays within a few ulp. `row_freqs`:
+    `wavelets.row_frequencies`; must be finite and positive. Cached per content (the eight most recent)."""
+    f = row_freqs.detach().cpu().numpy() if hasattr(row_freqs, 'detach') else row_freqs
+    f = np.ascontiguousarray(np.asarray(f, dtype=np.float64).reshape(-1))
+    fs, n = float(fs), int(n)
+    if n < 1:
+        raise ValueError("`n` must be >= 1 (got %d)" % n)
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError("`fs` must be finite and positive (got %r)" % (fs,))
+    phi = f / fs
+    if f.size < 1 or not (np.isfinite(phi).all() and (phi > 0).all()):
+        raise ValueError("`row_freqs` must be finite and positive")
+    P = _lib.TSSQ_CWT_ROT_P
+    nq = -(-n // P)
+    key = (str(device()), phi.tobytes(), nq)
+    if key not in _CWT_ROT_TABLES:
+        if len(_CWT_ROT_TABLES) >= 8:
+            _CWT_ROT_TABLES.pop(next(iter(_CWT_ROT_TABLES)))
+        lo, hi = _exact_turns(phi, 1, P), _exact_turns(phi, P, nq)
+        _CWT_ROT_TABLES[key] = (to_device(np.exp(-2j * np.pi * lo)), to_device(np.exp(-2j * np.pi * hi)))
+    return _CWT_ROT_TABLES[key]
+
+
+def time_reassign_cwt_shift(emax, dmax, n):
+    """`sh` of `time_reassign_cwt_gpu`'s fixed-point sum for one signal, as the entry takes it: ``61 - bit_length(max_i
+    min(2 dmax[i] + 1, n)) - ceil(frexp(emax)[1] / 2)``, `emax` the largest kept ``|W|^2`` (the float64 whose bits
+    `return_acc` hands back as `peak`). ``ldexp(acc, -sh)`` is the sum `acc` stands for; a term is within ``2^-sh`` of its
+    value per component."""
+    dm = np.asarray(dmax, dtype=np.int64).reshape(-1)
+    C = int(np.minimum(2 * dm + 1, int(n)).max())
+    ex = int(np.frexp(np.float64(emax))[1])
+    return 61 - C.bit_length() + (-ex) // 2
+
+
+def time_reassign_cwt_gpu(W, Wd, scales, dmax, gamma, rot=None, out=None, return_acc=False, window=True):
+    """The time-reassigned synchrosqueezed CWT in three launches (`ssq_time_reassign_cwt`, include/ssq_hip.h states the
+    definition): the CWT counterpart of `time_reassign_gpu`. `W`, `Wd`: (rows, n) or (B, rows, n)
+    complex -- the CWT of one signal over ``psih(w)`` and over ``psih'(w)`` (`wavelets.derived_wavelets`); `scales`
+    (rows,) in samples; `dmax` (rows,) integers, the largest displacement kept per row (`reassign_cwt_dmax`). Every point
+    with ``|W| >= gamma`` moves along its row by ``d = rint(Im(Wd / W) scales[i])`` columns, if ``|d| <= dmax[i]`` and the
+    target is a column of the plane, and is added there as ``W[i, c] rot(i, c)``. `rot`: the ``(rot_lo, rot_hi)`` pair
+    of `cwt_rotation_tables` for the rows' frequencies, or False for no rotation; None is refused -- the kernel cannot
+    know the rows' frequencies. Returns `Tx`, complex, of `W`'s shape; with `return_acc` ``(Tx, acc, peak)``: the int64
+    fixed-point sums, ``W.shape + (2,)``, and, per signal, the bits of the largest kept ``|W|^2``.
+
+    Float64 arithmetic for both precisions. A cell's sum is taken in signed fixed point, real and imaginary parts
+    apart: a term's component is scaled by ``2^sh`` and truncated toward zero, ``sh = 61 - bit_length(max_i min(2
+    dmax[i] + 1, n)) - ceil(frexp(max |W|^2)[1] / 2)`` per signal, so the result does not depend on the order of the
+    additions: bit-reproducible, and within (the cell's terms) x ``2^-sh`` of the exact sum per component, before the
+    one rounding to the output's precision. ``window=False`` sends every term through global atomics (the same bits;
+    for measurements)."""
+    if gamma is None:
+        raise ValueError("`gamma` must not be None")
+    if rot is None:
+        raise ValueError("`rot` must be the (rot_lo, rot_hi) pair of `cwt_rotation_tables` for the rows' frequencies, "
+                         "or False for no rotation: the kernel cannot know them")
+    lib = _lib.load()
+    W = to_device(W)
+    if W.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`W` must be complex64 or complex128 (got %s)" % W.dtype)
+    Wd = to_device(Wd, W.dtype)
+    if Wd.shape != W.shape:
+        raise ValueError("`W` and `Wd` must share one shape (got %s and %s)" % (tuple(W.shape), tuple(Wd.shape)))
+    B, rows, n = _shape3(W)
+
+    def host(name, v, dt):
+        v = v.detach().cpu().numpy() if hasattr(v, 'detach') else v
+        v = np.asarray(v).reshape(-1)
+        if v.size != rows:
+            raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
+        return np.ascontiguousarray(v, dtype=dt)
+    sc = host('scales', scales, np.float64)
+    dm = host('dmax', dmax, np.int64)
+    if (dm < np.iinfo(np.int32).min).any() or (dm > np.iinfo(np.int32).max).any():
+        raise ValueError("`dmax` must fit 32 bits")
+    dm = dm.astype(np.int32)
+    lo = hi = None
+    if rot is not False:
+        try:
+            lo, hi = rot
+        except (TypeError, ValueError):
+            raise ValueError("`rot` must be a (rot_lo, rot_hi) pair (`cwt_rotation_tables`) or False")
+        lo, hi = to_device(lo, torch.complex128), to_device(hi, torch.complex128)
+        P = _lib.TSSQ_CWT_ROT_P
+        if lo.shape != (rows, P) or hi.shape != (rows, -(-n // P)):
+            raise ValueError("`rot` must be (rows, %d) and (rows, ceil(n / %d)) = (%d, %d) (got %s and %s)"
+                             % (P, P, rows, -(-n // P), tuple(lo.shape), tuple(hi.shape)))
+    if out is None:
+        out = torch.empty(W.shape, dtype=W.dtype, device=W.device)
+    else:
+        _check_out(out, W)
+    acc = torch.empty(tuple(W.shape) + (2,), dtype=torch.int64, device=W.device)
+    peak = torch.empty((B,), dtype=torch.int64, device=W.device)
+    rsc_d = to_device(sc)
+    check(lib.ssq_time_reassign_cwt(_CDT[W.dtype], _ptr(W), _ptr(Wd), _ptr(rsc_d), dm.ctypes.data, _ptr(lo), _ptr(hi),
+                                    _ptr(out), _ptr(acc), _ptr(peak), B, rows, n, float(gamma),
+                                    0 if window else _lib.TSSQ_CWT_NO_WINDOW, stream()))
     return (out, acc, peak) if return_acc else out
 
 

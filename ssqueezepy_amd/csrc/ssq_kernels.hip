@@ -872,7 +872,7 @@ extern "C" __attribute__((weak)) const char ssq_build_sha_value[] = "unknown";
 extern "C" {
 
 const char* ssq_build_sha(void) { return ssq_build_sha_value; }
-int ssq_version(void) { return 119; }   // 119: ssq_multi_squeeze_cwt, ssq_multi_squeeze_cwt_max_rows, ssq_multi_squeeze_cwt_tile; 118: ssq_reassign_route, ssq_indexed_sum_bins; 117: ssq_reassign_cwt, ssq_reassign_cwt_tile; 116: ssq_stft_generic_shape; 115: ssq_reassign2d, ssq_reassign2d_tile; 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
+int ssq_version(void) { return 120; }   // 120: ssq_time_reassign_cwt, ssq_time_reassign_cwt_tile; 119: ssq_multi_squeeze_cwt, ssq_multi_squeeze_cwt_max_rows, ssq_multi_squeeze_cwt_tile; 118: ssq_reassign_route, ssq_indexed_sum_bins; 117: ssq_reassign_cwt, ssq_reassign_cwt_tile; 116: ssq_stft_generic_shape; 115: ssq_reassign2d, ssq_reassign2d_tile; 114: ssq_multi_squeeze, ssq_multi_squeeze_max_rows; 113: ssq_time_reassign, ssq_time_reassign_segment, ssq_time_reassign_max_dmax; 112: ssq_conceft_cwt; 111: ssq_conceft; 110: ssq_cwt2_phase; 109: ssq_stft2_phase; 108: ssq_cwt_adjoint; 107: ssq_istft_batch, ssq_istft_adjoint, ssq_istft_algo, ssq_colsum_adjoint, ssq_band_colsum_batch, ssq_band_colsum_adjoint; 106: ssq_stft_adjoint, ssq_ssqueeze_adjoint; 105: ssq_cwt_plan_tile_kernel; 104: ssq_build_sha, ssq_cwt_plan_set_bin_dump; 103: ssq_ridge_*_batch; 102: ssq_cwt_plan_tile_cols; 101: ssq_cwt_blocks_desc.classes has 5 columns (analytic classes)
 const char* ssq_last_error(void) { return g_last_error.c_str(); }
 
 int ssq_device_count(int* count) {

@@ -190,3 +190,6 @@ int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* ro
 #include "ssq_reassign2d.inl"
 // ssq_reassign_cwt (the reassigned scalogram: the CWT form of that scatter) shares ssq_reassign2d's kernels and helpers
 #include "ssq_reassign_cwt.inl"
+// ssq_time_reassign_cwt (the time-reassigned synchrosqueezed CWT: that accumulator with signed complex terms) shares
+// ssq_reassign2d's peak kernel, point test and window write-out
+#include "ssq_time_reassign_cwt.inl"
