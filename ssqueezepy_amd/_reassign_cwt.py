@@ -25,6 +25,52 @@ from .wavelets import Wavelet, center_frequency, derived_wavelets, wavelet_time_
 __all__ = ['reassign_cwt']
 
 
+def _derived_cwt_prelude(x, wavelet, scales, nv, fs, t, ssq_freqs, padtype, maprange, gamma, cache_wavelet):
+    """What `reassign_cwt` and `tssq_cwt` do ahead of their kernel: the checks of `x` and `padtype`, the defaults of
+    `nv`, `fs` / `t` and `gamma`, the wavelet with its ``psih'(w)`` companion and the design. Returns ``(wavelet, dt, fs,
+    gamma, design, sc, execute)``: `design` is `_ssq_design`'s, `sc` the scales as float64, and ``execute(derived=False,
+    **kw)`` runs the plan of the wavelet -- of the companion with `derived` -- on `x` and hands back its planes."""
+    if not hasattr(x, 'ndim'):
+        raise TypeError("`x` must be a numpy array or torch Tensor "
+                        "(got %s)" % type(x))
+    elif x.ndim not in (1, 2):
+        raise ValueError("`x` must be 1D or 2D (got x.ndim == %s)" % x.ndim)
+    if padtype is not None and padtype not in PADTYPES:
+        raise ValueError("`padtype` must be one of: %s (got %s)"
+                         % (', '.join(PADTYPES), padtype))
+    if nv is None and not isinstance(scales, np.ndarray):
+        nv = 32
+    N = x.shape[-1]
+    dt, fs, t = _process_fs_and_t(fs, t, N)
+
+    wavelet = _process_gmw_wavelet(wavelet, True)
+    wavelet = Wavelet._init_if_not_isinstance(wavelet, N=N)
+    companion = derived_wavelets(wavelet)[0]    # raises for a wavelet without a closed form
+    if gamma is None:
+        gamma = 10 * (EPS64 if wavelet.dtype == 'float64' else EPS32)
+
+    design = _ssq_design(wavelet, scales, nv, N, dt, ssq_freqs, maprange, bool(padtype is not None))
+    use_cache = True if cache_wavelet is None else bool(cache_wavelet)
+    xd = algos.to_device(x, _TDT[wavelet.dtype]).detach()
+    B = xd.shape[0] if xd.ndim == 2 else 1
+    sc = np.asarray(design[0], dtype=np.float64).reshape(-1)
+
+    def execute(derived=False, **kw):
+        return get_cwt_plan(companion if derived else wavelet, design[0], N, padtype, dt, True, B,
+                            cache=use_cache).execute(xd, **kw)
+    return wavelet, dt, fs, gamma, design, sc, execute
+
+
+def _t_hat(Wx, Wd, sc, dt, gamma):
+    """``times + Re(T / W)``, the reassigned time of every point, ``inf`` where ``|Wx| < gamma``: ``T = -1j r Wd``, ``r =
+    sc dt``, so ``Re(T / W) = r Im(Wd / W)``."""
+    dtype = np.float32 if Wx.dtype == torch.complex64 else np.float64
+    times = torch.as_tensor((np.arange(Wx.shape[-1]) * dt).astype(dtype), device=Wx.device)
+    r = torch.as_tensor((sc * dt).astype(dtype), device=Wx.device)[:, None]
+    t_hat = times + (Wd / Wx).imag * r
+    return torch.where(torch.abs(Wx) < gamma, torch.full_like(t_hat, float('inf')), t_hat)
+
+
 def reassign_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None, ssq_freqs=None,
                  padtype='reflect', maprange='peak', gamma=None, reassign='both', max_shift=4.,
                  astensor=True, flipud=True, cache_wavelet=None, get_maps=False):
@@ -54,40 +100,17 @@ def reassign_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=N
     output's precision. The outputs carry no `grad_fn`, whatever `x` requires."""
     if reassign not in ('both', 'freq', 'time'):
         raise ValueError("`reassign` must be 'both', 'freq' or 'time' (got %r)" % (reassign,))
-    if not hasattr(x, 'ndim'):
-        raise TypeError("`x` must be a numpy array or torch Tensor "
-                        "(got %s)" % type(x))
-    elif x.ndim not in (1, 2):
-        raise ValueError("`x` must be 1D or 2D (got x.ndim == %s)" % x.ndim)
     _check_ssqueezing_args('sum', maprange, wavelet, 'trig', None, False, transform='cwt')
-    if padtype is not None and padtype not in PADTYPES:
-        raise ValueError("`padtype` must be one of: %s (got %s)"
-                         % (', '.join(PADTYPES), padtype))
-    if nv is None and not isinstance(scales, np.ndarray):
-        nv = 32
-    N = x.shape[-1]
-    dt, fs, t = _process_fs_and_t(fs, t, N)
-
-    wavelet = _process_gmw_wavelet(wavelet, True)
-    wavelet = Wavelet._init_if_not_isinstance(wavelet, N=N)
-    companion = derived_wavelets(wavelet)[0]    # raises for a wavelet without a closed form
-    dtype = wavelet.dtype
-    if gamma is None:
-        gamma = 10 * (EPS64 if dtype == 'float64' else EPS32)
+    wavelet, dt, fs, gamma, design, sc, execute = _derived_cwt_prelude(x, wavelet, scales, nv, fs, t, ssq_freqs, padtype,
+                                                                        maprange, gamma, cache_wavelet)
+    scales_dt, ssq_freqs, const = design[:3]
     freq, time = reassign != 'time', reassign != 'freq'
 
-    scales_dt, ssq_freqs, const, grid, _ = _ssq_design(wavelet, scales, nv, N, dt, ssq_freqs,
-                                                       maprange, bool(padtype is not None))
-    use_cache = True if cache_wavelet is None else bool(cache_wavelet)
-    xd = algos.to_device(x, _TDT[dtype]).detach()
-    B = xd.shape[0] if xd.ndim == 2 else 1
-    sc = np.asarray(scales_dt, dtype=np.float64).reshape(-1)
-
-    out = get_cwt_plan(wavelet, scales_dt, N, padtype, dt, True, B, cache=use_cache).execute(xd, want_dWx=freq)
+    out = execute(want_dWx=freq)
     Wx, dW = out['Wx'], out.get('dWx')
     Wd = dmax = None
     if time:
-        Wd = get_cwt_plan(companion, scales_dt, N, padtype, dt, True, B, cache=use_cache).execute(xd)['Wx']
+        Wd = execute(derived=True)['Wx']
         dmax = algos.reassign_cwt_dmax(sc, wavelet_time_std(wavelet), max_shift)
     # (the LDS windows go where the rows' own centre frequencies lie on the grid: `maprange` and a caller's `ssq_freqs`
     # may put them anywhere)
@@ -96,15 +119,11 @@ def reassign_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=N
 
     f_hat = t_hat = None
     if get_maps:
-        low = torch.abs(Wx) < gamma
         if freq:
             f_hat = torch.abs((dW / Wx).imag) / (2 * np.pi)
-            f_hat = torch.where(low, torch.full_like(f_hat, float('inf')), f_hat)
+            f_hat = torch.where(torch.abs(Wx) < gamma, torch.full_like(f_hat, float('inf')), f_hat)
         if time:
-            times = torch.as_tensor((np.arange(N) * dt).astype(dtype), device=Wx.device)
-            r = torch.as_tensor((sc * dt).astype(dtype), device=Wx.device)[:, None]
-            t_hat = times + (Wd / Wx).imag * r                  # Re(-1j r Wd / W) = r Im(Wd / W)
-            t_hat = torch.where(low, torch.full_like(t_hat, float('inf')), t_hat)
+            t_hat = _t_hat(Wx, Wd, sc, dt, gamma)
     del dW, Wd, out
 
     # `scales` go high -> low, so frequencies are returned high -> low

@@ -9,16 +9,9 @@ coefficient of every point along its row to its group delay, after referring its
 the terms that meet in a cell add coherently. DESIGN.md section 4.5.12 states the definition; `ssq_time_reassign_cwt`
 (include/ssq_hip.h) computes it.
 """
-import numpy as np
-import torch
-
 from . import algos
-from .configs import EPS32, EPS64
-from ._cwt import get_cwt_plan, _process_gmw_wavelet, _TDT
-from ._ssq_cwt import _ssq_design
-from .padding import PADTYPES
-from .scales import _process_fs_and_t
-from .wavelets import Wavelet, derived_wavelets, row_frequencies, wavelet_time_std
+from ._reassign_cwt import _derived_cwt_prelude, _t_hat
+from .wavelets import row_frequencies, wavelet_time_std
 
 __all__ = ['tssq_cwt']
 
@@ -48,48 +41,18 @@ def tssq_cwt(x, wavelet='gmw', scales='log-piecewise', nv=None, fs=None, t=None,
     The arithmetic is float64 for both precisions and a cell's sum is taken in signed fixed point
     (`algos.time_reassign_cwt_gpu`): it does not depend on the order of the additions, so the result is
     bit-reproducible. The outputs carry no `grad_fn`, whatever `x` requires."""
-    if not hasattr(x, 'ndim'):
-        raise TypeError("`x` must be a numpy array or torch Tensor "
-                        "(got %s)" % type(x))
-    elif x.ndim not in (1, 2):
-        raise ValueError("`x` must be 1D or 2D (got x.ndim == %s)" % x.ndim)
-    if padtype is not None and padtype not in PADTYPES:
-        raise ValueError("`padtype` must be one of: %s (got %s)"
-                         % (', '.join(PADTYPES), padtype))
-    if nv is None and not isinstance(scales, np.ndarray):
-        nv = 32
-    N = x.shape[-1]
-    dt, fs, t = _process_fs_and_t(fs, t, N)
-
-    wavelet = _process_gmw_wavelet(wavelet, True)
-    wavelet = Wavelet._init_if_not_isinstance(wavelet, N=N)
-    companion = derived_wavelets(wavelet)[0]    # raises for a wavelet without a closed form
-    dtype = wavelet.dtype
-    if gamma is None:
-        gamma = 10 * (EPS64 if dtype == 'float64' else EPS32)
-
-    scales_dt = _ssq_design(wavelet, scales, nv, N, dt, None, 'peak', bool(padtype is not None))[0]
-    use_cache = True if cache_wavelet is None else bool(cache_wavelet)
-    xd = algos.to_device(x, _TDT[dtype]).detach()
-    B = xd.shape[0] if xd.ndim == 2 else 1
-    sc = np.asarray(scales_dt, dtype=np.float64).reshape(-1)
-
-    Wx = get_cwt_plan(wavelet, scales_dt, N, padtype, dt, True, B, cache=use_cache).execute(xd, want_dWx=False)['Wx']
-    Wd = get_cwt_plan(companion, scales_dt, N, padtype, dt, True, B, cache=use_cache).execute(xd)['Wx']
+    wavelet, dt, fs, gamma, design, sc, execute = _derived_cwt_prelude(x, wavelet, scales, nv, fs, t, None, padtype, 'peak',
+                                                                        gamma, cache_wavelet)
+    Wx = execute(want_dWx=False)['Wx']
+    Wd = execute(derived=True)['Wx']
     dmax = algos.reassign_cwt_dmax(sc, wavelet_time_std(wavelet), max_shift)
     freqs = row_frequencies(wavelet, sc, fs)
-    Tx = algos.time_reassign_cwt_gpu(Wx, Wd, sc, dmax, gamma, rot=algos.cwt_rotation_tables(freqs, N, fs))
+    Tx = algos.time_reassign_cwt_gpu(Wx, Wd, sc, dmax, gamma, rot=algos.cwt_rotation_tables(freqs, Wx.shape[-1], fs))
 
-    t_hat = None
-    if get_t:
-        low = torch.abs(Wx) < gamma
-        times = torch.as_tensor((np.arange(N) * dt).astype(dtype), device=Wx.device)
-        r = torch.as_tensor((sc * dt).astype(dtype), device=Wx.device)[:, None]
-        t_hat = times + (Wd / Wx).imag * r                      # Re(-1j r Wd / W) = r Im(Wd / W)
-        t_hat = torch.where(low, torch.full_like(t_hat, float('inf')), t_hat)
+    t_hat = _t_hat(Wx, Wd, sc, dt, gamma) if get_t else None
     del Wd
 
-    scales_out = scales_dt.squeeze()
+    scales_out = design[0].squeeze()
     if not astensor:
         Tx, Wx = Tx.cpu().numpy(), Wx.cpu().numpy()
         t_hat = t_hat.cpu().numpy() if t_hat is not None else None

@@ -58,11 +58,12 @@ def to_device(x, dtype=None):
     return x.to(dev).resolve_conj().resolve_neg().contiguous()
 
 
-def _check_out(out, like):
-    """An `out=` argument is written through its raw pointer as a dense array of `like`'s shape."""
-    if not (isinstance(out, torch.Tensor) and out.shape == like.shape and out.dtype == like.dtype
+def _check_out(out, like, dtype=None, message="`out` must be a contiguous GPU tensor of `Wx`'s shape and dtype"):
+    """An `out=` argument is written through its raw pointer as a dense array of `like`'s shape, of `like`'s dtype
+    or of `dtype`."""
+    if not (isinstance(out, torch.Tensor) and out.shape == like.shape and out.dtype == (dtype or like.dtype)
             and out.is_cuda and out.is_contiguous() and not out.is_conj()):
-        raise ValueError("`out` must be a contiguous GPU tensor of `Wx`'s shape and dtype")
+        raise ValueError(message)
 
 
 def ones_like(x):
@@ -87,6 +88,49 @@ def _shape3(t):
     if t.ndim == 3:
         return t.shape
     raise ValueError("expected a 2D or 3D array (got ndim=%d)" % t.ndim)
+
+
+def _complex_planes(name, first, **optional):
+    """``(first, [optional planes], (B, rows, n))``: `first` on the device, complex, and the `optional` planes in its
+    dtype and of its shape; None passes through (`name` and the keywords in the messages)."""
+    first = to_device(first)
+    if first.dtype not in (torch.complex64, torch.complex128):
+        raise TypeError("`%s` must be complex64 or complex128 (got %s)" % (name, first.dtype))
+    shape = _shape3(first)
+    planes = []
+    for key, P in optional.items():
+        if P is not None:
+            P = to_device(P, first.dtype)
+            if P.shape != first.shape:
+                raise ValueError("`%s` and `%s` must share one shape (got %s and %s)"
+                                 % (name, key, tuple(first.shape), tuple(P.shape)))
+        planes.append(P)
+    return first, planes, shape
+
+
+def _row_vector(name, v, rows, dtype=None, scalar_ok=False):
+    """`v` as a contiguous host vector with one entry per row, of `dtype` (None: its own); with `scalar_ok` one value
+    stands for every row (`name` in the message)."""
+    v = v.detach().cpu().numpy() if hasattr(v, 'detach') else v
+    v = np.asarray(v).reshape(-1)
+    if not (v.size == rows or (scalar_ok and v.size == 1)):
+        raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
+    return np.array(np.broadcast_to(v, (rows,)), dtype=dtype)      # (a copy: contiguous and writable)
+
+
+def _row_dmax(dmax, rows):
+    """The rows' largest displacements as the fixed-point entries take them: int32, host."""
+    dm = _row_vector('dmax', dmax, rows, np.int64)
+    if (dm < np.iinfo(np.int32).min).any() or (dm > np.iinfo(np.int32).max).any():
+        raise ValueError("`dmax` must fit 32 bits")
+    return dm.astype(np.int32)
+
+
+def _fixed_point_buffers(like, B, words=1):
+    """``(acc, peak)`` of a fixed-point scatter: the int64 sums, `words` per point of `like`, and a word per signal."""
+    shape = tuple(like.shape) + ((words,) if words > 1 else ())
+    return (torch.empty(shape, dtype=torch.int64, device=like.device),
+            torch.empty((B,), dtype=torch.int64, device=like.device))
 
 
 def _const_vector(const, na, cdtype):
@@ -342,11 +386,7 @@ def phase_cwt2_gpu(W, dW, Wd, dWd, dW3, scales, fs, gamma, chirp_tol=1e-3):
     the points that fall back are `phase_cwt_gpu`'s bit for bit (complex64: its float32 numerator and ``|W|^2``)."""
     lib = _lib.load()
     planes, (B, na, n), w = _five_planes('W', W, dW, Wd, dWd, dW3)
-    if hasattr(scales, 'detach'):
-        scales = scales.detach().cpu().numpy()
-    sc = np.ascontiguousarray(np.asarray(scales).reshape(-1), dtype=np.float64)     # a host array: the entry checks it
-    if sc.size != na:
-        raise ValueError("`scales` must have one entry per row (%d != %d)" % (sc.size, na))
+    sc = _row_vector('scales', scales, na, np.float64)      # a host array: the entry checks it
     check(lib.ssq_cwt2_phase(_CDT[w.dtype], *[_ptr(V) for V in planes], sc.ctypes.data, _ptr(w), B, na, n,
                              float(fs), float(gamma), float(chirp_tol), stream()))
     return w
@@ -384,9 +424,8 @@ def _conceft_call(entry, V, dV, row_values, proj, ssq_freqs, logscale, gamma, fl
     odt = rdt if average == 'abs' else first.dtype
     if out is None:
         out = torch.empty(first.shape, dtype=odt, device=first.device)
-    elif not (isinstance(out, torch.Tensor) and out.shape == first.shape and out.dtype == odt and out.is_cuda
-              and out.is_contiguous() and not out.is_conj()):
-        raise ValueError("`out` must be a contiguous GPU tensor of the planes' shape, %s" % odt)
+    else:
+        _check_out(out, first, odt, "`out` must be a contiguous GPU tensor of the planes' shape, %s" % odt)
     kind, p = _grid(ssq_freqs, logscale)
     ptrs = ctypes.c_void_p * J
     check(getattr(lib, entry)(_CDT[first.dtype], ptrs(*[_ptr(t) for t in planes[:J]]),
@@ -516,19 +555,7 @@ def reassign2d_gpu(Sx, dSx, Vtg, n_fft, hop_len, fs, gamma, kmax=None, dmax=None
     if gamma is None:
         raise ValueError("`gamma` must not be None")
     lib = _lib.load()
-    Sx = to_device(Sx)
-    if Sx.dtype not in (torch.complex64, torch.complex128):
-        raise TypeError("`Sx` must be complex64 or complex128 (got %s)" % Sx.dtype)
-    B, rows, n = _shape3(Sx)
-    planes = []
-    for name, P in (('dSx', dSx), ('Vtg', Vtg)):
-        if P is not None:
-            P = to_device(P, Sx.dtype)
-            if P.shape != Sx.shape:
-                raise ValueError("`Sx` and `%s` must share one shape (got %s and %s)"
-                                 % (name, tuple(Sx.shape), tuple(P.shape)))
-        planes.append(P)
-    dSx, Vtg = planes
+    Sx, (dSx, Vtg), (B, rows, n) = _complex_planes('Sx', Sx, dSx=dSx, Vtg=Vtg)
     n_fft, hop_len = int(n_fft), int(hop_len)
     if n_fft < 1 or hop_len < 1:
         raise ValueError("`n_fft` and `hop_len` must be >= 1 (got %d, %d)" % (n_fft, hop_len))
@@ -541,11 +568,9 @@ def reassign2d_gpu(Sx, dSx, Vtg, n_fft, hop_len, fs, gamma, kmax=None, dmax=None
     rdt = _real_of(Sx.dtype)
     if out is None:
         out = torch.empty(Sx.shape, dtype=rdt, device=Sx.device)
-    elif not (isinstance(out, torch.Tensor) and out.shape == Sx.shape and out.dtype == rdt and out.is_cuda
-              and out.is_contiguous()):
-        raise ValueError("`out` must be a contiguous real GPU tensor of `Sx`'s shape and precision")
-    acc = torch.empty(Sx.shape, dtype=torch.int64, device=Sx.device)
-    peak = torch.empty((B,), dtype=torch.int64, device=Sx.device)
+    else:
+        _check_out(out, Sx, rdt, "`out` must be a contiguous real GPU tensor of `Sx`'s shape and precision")
+    acc, peak = _fixed_point_buffers(Sx, B)
     flags = (_lib.REASSIGN2D_FREQ if dSx is not None else 0) | (0 if window else _lib.REASSIGN2D_NO_WINDOW)
     check(lib.ssq_reassign2d(_CDT[Sx.dtype], _ptr(Sx), _ptr(dSx), _ptr(Vtg), _ptr(out), _ptr(acc), _ptr(peak), B, rows, n,
                              n_fft, hop_len, float(fs), float(fs) / hop_len, int(kmax), int(dmax), float(gamma), flags,
@@ -622,59 +647,30 @@ def reassign_cwt_gpu(W, dW, Wd, scales, cst, dmax, ssq_freqs, gamma, flipud=Fals
     if gamma is None:
         raise ValueError("`gamma` must not be None")
     lib = _lib.load()
-    W = to_device(W)
-    if W.dtype not in (torch.complex64, torch.complex128):
-        raise TypeError("`W` must be complex64 or complex128 (got %s)" % W.dtype)
-    B, rows, n = _shape3(W)
-    planes = []
-    for name, P in (('dW', dW), ('Wd', Wd)):
-        if P is not None:
-            P = to_device(P, W.dtype)
-            if P.shape != W.shape:
-                raise ValueError("`W` and `%s` must share one shape (got %s and %s)"
-                                 % (name, tuple(W.shape), tuple(P.shape)))
-        planes.append(P)
-    dW, Wd = planes
+    W, (dW, Wd), (B, rows, n) = _complex_planes('W', W, dW=dW, Wd=Wd)
     freq, time = dW is not None, Wd is not None
-
-    def host(name, v, dt, scalar_ok=False):
-        v = v.detach().cpu().numpy() if hasattr(v, 'detach') else v
-        v = np.asarray(v).reshape(-1)
-        if not (v.size == rows or (scalar_ok and v.size == 1)):
-            raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
-        return np.ascontiguousarray(np.broadcast_to(v, (rows,)), dtype=dt)
-    c = host('cst', cst, np.float64, scalar_ok=True)
+    c = _row_vector('cst', cst, rows, np.float64, scalar_ok=True)
     if not (np.isfinite(c).all() and (c >= 0).all()):
         raise ValueError("`cst` must be finite and >= 0")
-    sc = host('scales', scales, np.float64)
-    dm = None
-    if time:
-        dm = host('dmax', dmax, np.int64)
-        if (dm < np.iinfo(np.int32).min).any() or (dm > np.iinfo(np.int32).max).any():
-            raise ValueError("`dmax` must fit 32 bits")
-        dm = dm.astype(np.int32)
+    sc = _row_vector('scales', scales, rows, np.float64)
+    dm = _row_dmax(dmax, rows) if time else None
     kind, p = 0, None
     if freq:
         from .scales import infer_scaletype
-        if hasattr(ssq_freqs, 'detach'):
-            ssq_freqs = ssq_freqs.detach().cpu().numpy()
-        ssq_freqs = np.asarray(ssq_freqs).reshape(-1)
-        if ssq_freqs.size != rows:
-            raise ValueError("`ssq_freqs` must have one entry per row (%d != %d)" % (ssq_freqs.size, rows))
+        ssq_freqs = _row_vector('ssq_freqs', ssq_freqs, rows)
         # (two values are evenly spaced in any metric: they are taken as a linear grid)
         kind, p = _grid(ssq_freqs, rows > 2 and infer_scaletype(ssq_freqs)[0].startswith('log'))
     if home is None:
         home = reassign_cwt_home(sc, ssq_freqs, flipud, freq)
     else:
-        home = np.clip(host('home', home, np.int64), np.iinfo(np.int32).min, np.iinfo(np.int32).max).astype(np.int32)
+        home = np.clip(_row_vector('home', home, rows, np.int64), np.iinfo(np.int32).min,
+                       np.iinfo(np.int32).max).astype(np.int32)
     rdt = _real_of(W.dtype)
     if out is None:
         out = torch.empty(W.shape, dtype=rdt, device=W.device)
-    elif not (isinstance(out, torch.Tensor) and out.shape == W.shape and out.dtype == rdt and out.is_cuda
-              and out.is_contiguous()):
-        raise ValueError("`out` must be a contiguous real GPU tensor of `W`'s shape and precision")
-    acc = torch.empty(W.shape, dtype=torch.int64, device=W.device)
-    peak = torch.empty((B,), dtype=torch.int64, device=W.device)
+    else:
+        _check_out(out, W, rdt, "`out` must be a contiguous real GPU tensor of `W`'s shape and precision")
+    acc, peak = _fixed_point_buffers(W, B)
     cst_d, rsc_d = to_device(c), to_device(sc)
     home_d = to_device(np.ascontiguousarray(home))
     flags = ((_lib.REASSIGN_CWT_FREQ if freq else 0) | (_lib.REASSIGN_CWT_TIME if time else 0)
@@ -762,25 +758,9 @@ def time_reassign_cwt_gpu(W, Wd, scales, dmax, gamma, rot=None, out=None, return
         raise ValueError("`rot` must be the (rot_lo, rot_hi) pair of `cwt_rotation_tables` for the rows' frequencies, "
                          "or False for no rotation: the kernel cannot know them")
     lib = _lib.load()
-    W = to_device(W)
-    if W.dtype not in (torch.complex64, torch.complex128):
-        raise TypeError("`W` must be complex64 or complex128 (got %s)" % W.dtype)
-    Wd = to_device(Wd, W.dtype)
-    if Wd.shape != W.shape:
-        raise ValueError("`W` and `Wd` must share one shape (got %s and %s)" % (tuple(W.shape), tuple(Wd.shape)))
-    B, rows, n = _shape3(W)
-
-    def host(name, v, dt):
-        v = v.detach().cpu().numpy() if hasattr(v, 'detach') else v
-        v = np.asarray(v).reshape(-1)
-        if v.size != rows:
-            raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
-        return np.ascontiguousarray(v, dtype=dt)
-    sc = host('scales', scales, np.float64)
-    dm = host('dmax', dmax, np.int64)
-    if (dm < np.iinfo(np.int32).min).any() or (dm > np.iinfo(np.int32).max).any():
-        raise ValueError("`dmax` must fit 32 bits")
-    dm = dm.astype(np.int32)
+    W, (Wd,), (B, rows, n) = _complex_planes('W', W, Wd=to_device(Wd))     # (`Wd` is not optional: None raises)
+    sc = _row_vector('scales', scales, rows, np.float64)
+    dm = _row_dmax(dmax, rows)
     lo = hi = None
     if rot is not False:
         try:
@@ -796,8 +776,7 @@ def time_reassign_cwt_gpu(W, Wd, scales, dmax, gamma, rot=None, out=None, return
         out = torch.empty(W.shape, dtype=W.dtype, device=W.device)
     else:
         _check_out(out, W)
-    acc = torch.empty(tuple(W.shape) + (2,), dtype=torch.int64, device=W.device)
-    peak = torch.empty((B,), dtype=torch.int64, device=W.device)
+    acc, peak = _fixed_point_buffers(W, B, words=2)
     rsc_d = to_device(sc)
     check(lib.ssq_time_reassign_cwt(_CDT[W.dtype], _ptr(W), _ptr(Wd), _ptr(rsc_d), dm.ctypes.data, _ptr(lo), _ptr(hi),
                                     _ptr(out), _ptr(acc), _ptr(peak), B, rows, n, float(gamma),
@@ -859,11 +838,7 @@ def multi_squeeze_gpu(Sx, w, Sfs, ssq_freqs, const=1, n_iter=10, interp='linear'
 
 def _row_table(name, v, rows):
     """`v` as a contiguous float64 host vector of `rows` finite, strictly monotone values (`name` in the message)."""
-    if hasattr(v, 'detach'):
-        v = v.detach().cpu().numpy()
-    v = np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.float64)
-    if v.size != rows:
-        raise ValueError("`%s` must have one entry per row (%d != %d)" % (name, v.size, rows))
+    v = _row_vector(name, v, rows, np.float64)
     if not np.isfinite(v).all():
         raise ValueError("`%s` must be finite" % name)
     d = np.diff(v)
@@ -897,11 +872,7 @@ def multi_squeeze_cwt_gpu(Wx, w, row_freqs, ssq_freqs, const=1, n_iter=10, inter
         raise ValueError("`Wx` and `w` shapes differ")
     B, rows, n = _shape3(Wx)
     fr = _row_table('row_freqs', row_freqs, rows)
-    if hasattr(ssq_freqs, 'detach'):
-        ssq_freqs = ssq_freqs.detach().cpu().numpy()
-    ssq_freqs = np.asarray(ssq_freqs).reshape(-1)
-    if ssq_freqs.size != rows:
-        raise ValueError("`ssq_freqs` must have one entry per row (%d != %d)" % (ssq_freqs.size, rows))
+    ssq_freqs = _row_vector('ssq_freqs', ssq_freqs, rows)
     # (two values are evenly spaced in any metric: they are taken as a linear grid)
     kind, p = _grid(ssq_freqs, rows > 2 and infer_scaletype(ssq_freqs)[0].startswith('log'))
     if out is None:

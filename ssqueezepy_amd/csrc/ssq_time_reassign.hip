@@ -185,11 +185,12 @@ int ssq_time_reassign(int dtype, const void* Sx, const void* Vtg, const void* ro
 
 }  // extern "C"
 
-// ssq_reassign2d (the reassigned spectrogram: both axes at once, a fixed-point scatter) shares this unit's flags and point
-// types
+// The fixed-point scatter (peak, windowed 64-bit integer scatter, finish: one kernel skeleton, one launcher) shares this
+// unit's flags and point types; its three rules and their entries follow it:
+#include "ssq_fixed_scatter.inl"
+// ssq_reassign2d, the reassigned spectrogram: the energy moves along both axes at once
 #include "ssq_reassign2d.inl"
-// ssq_reassign_cwt (the reassigned scalogram: the CWT form of that scatter) shares ssq_reassign2d's kernels and helpers
+// ssq_reassign_cwt, the reassigned scalogram: the CWT form, rows to bins of the synchrosqueezing grid
 #include "ssq_reassign_cwt.inl"
-// ssq_time_reassign_cwt (the time-reassigned synchrosqueezed CWT: that accumulator with signed complex terms) shares
-// ssq_reassign2d's peak kernel, point test and window write-out
+// ssq_time_reassign_cwt, the time-reassigned synchrosqueezed CWT: signed complex terms, two words per cell
 #include "ssq_time_reassign_cwt.inl"
